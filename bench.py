@@ -14,9 +14,15 @@ FOV head).  With N > 1 every rank runs the same per-GPU batch on its own images 
 parallel, no collective in the timed loop); rank 0 builds the synthetic checkpoint and ships the
 packed weight arena to the others with ONE RCCL broadcast before the timed region.
 
-Rank 0 prints ONE JSON line.  `roofline` is for the kernel with the largest share of the step
-(measured live with HIP events on the launch stream); `cpu_baseline` is the CPU oracle timed on this
-box's host cores on a bounded sample of the same workload (rank 0, N = 1 only).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`); everything else it can measure runs only with --full, after the timed region: `roofline` is for the
+kernel with the largest share of the step (measured live with HIP events on the launch stream, in a pass of its own),
+`kernels` the ten largest, `end_to_end_ms_per_step` the host-buffer form, `calibration` the box's two fixed loops,
+`cpu_baseline` the CPU oracle timed on this box's host cores (rank 0, N = 1 only), and with --chain the per-leg pass.
+
+--dump-outputs DIR writes what the last timed step computed -- the arrays a caller of the step receives: the inverse
+depth [B,S,S], with --chain also the stereograms [B,S,S,3] -- as DIR/<name>.npy in float32 (DIR/<name>_rank<r>.npy on
+every rank when N > 1), so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -158,28 +164,58 @@ def calibration_object(cal, value):
     return out
 
 
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def write_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: every array of `arrays` (name -> numpy array) as out_dir/<name>.npy in float32, at most
+    `max_bytes` in all.  When the arrays do not fit, each keeps the same share of its elements: those at sorted flat
+    indices drawn with seed 0, the same for the same shape in every run, so that two builds compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    header = 128                                   # an .npy header of a plain array
+    total = sum(a.size for a in arrays.values())
+    room = (max_bytes - header * len(arrays)) // 4
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if total > room:
+            keep = a.size * room // total
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the roofline pass, the per-kernel rows, the end-to-end "
+                         "host-buffer form, the box calibration, the CPU baseline and (--chain) the per-leg pass; a "
+                         "plain run prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--batch", type=int, default=1, help="images per GPU per step")
     ap.add_argument("--dtype", default="f16", choices=["f16", "bf16", "fp8"],
                     help="MFMA operand type: f16 (default; BASELINE configs[1], the fp16 checkpoint bit for bit), bf16, "
                          "or fp8 (BASELINE configs[3]: the ViT linears on MX block-scaled fp8, the rest f16)")
     ap.add_argument("--no-fov", action="store_true", help="pass f_norm = 1 instead of the FOV head")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--graph", action="store_true",
                     help="replay the step as one captured hipGraph (me_ctx_set_graph); default: eager launches, "
                          "measured equal (f16) to 1 %% faster (fp8): the GPU is never starved by the host")
     ap.add_argument("--cpu-windows", type=int, default=0,
-                    help="cpu_baseline all-cores leg: 0 (default) = the oracle's WHOLE path on one 1536x1536 image, timed "
+                    help="with --full, the cpu_baseline all-cores leg: 0 (default) = the oracle's WHOLE path on one 1536x1536 image, timed "
                          "once (about 75 s on a 128-thread host); n > 0 = a bounded sample of n ViT windows scaled by "
                          "FLOP share (quick runs)")
     ap.add_argument("--chain", action="store_true",
                     help="BASELINE configs[4]: time depth -> DepthMap::new (clamp + range) -> stereogram -> textured OBJ per "
-                         "image instead of the depth step alone; reports images/s with the OBJ leg split out")
-    return ap.parse_args()
+                         "image instead of the depth step alone; reports images/s (with --full the OBJ leg split out)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_ranks(args, child_cmd=None, timeout_s=None):
@@ -471,46 +507,57 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     my_step_ms = elapsed / args.steps * 1e3
+    if args.dump_outputs:
+        # the last timed step's results, before any leg below reuses the buffers (--chain: step k's depth is in buffer
+        # k & 1, clamped in place by DepthMap::new as its caller receives it)
+        last = depth_bufs[(args.steps - 1) & 1] if args.chain else depth
+        outputs = {"depth": last.cpu().numpy()}
+        if args.chain:
+            outputs["stereogram"] = stereo.cpu().numpy()
+        suffix = f"_rank{rank}" if distributed else ""
+        write_outputs(args.dump_outputs, {k + suffix: v for k, v in outputs.items()}, DUMP_MAX_BYTES // world)
+    chain_report = None
     if args.chain:
-        # per-leg diagnostic: a separate pass, synchronised between legs (never the timed region of the pipelined form)
-        n_diag = max(2, min(5, args.steps))
-        chain_serial(n_diag, True)
-        ctx.output_flush()
-        chain_report = {k: (v / (n_diag * B) if k != "obj_bytes" else v) for k, v in chain_ms.items()}
+        if args.full:
+            # per-leg diagnostic: a separate pass, synchronised between legs (never the timed region of the pipelined form)
+            n_diag = max(2, min(5, args.steps))
+            chain_serial(n_diag, True)
+            ctx.output_flush()
+            chain_report = {k: (v / (n_diag * B) if k != "obj_bytes" else v) for k, v in chain_ms.items()}
         shutil.rmtree(out_dir, ignore_errors=True)
         ctx.set_output_overlap(False)
         args_chain, args.chain = True, False      # the roofline / end-to-end legs below time the depth step itself
     else:
-        chain_report = {}
         args_chain = False
     graph_replays = ctx.graph_launch_count
-    # roofline leg: the same steps once more with every GEMM / attention / LayerNorm launch bracketed
-    # by HIP events on the launch stream (an event costs ~5 us of queue time, so it is kept out of the
-    # timed region above)
-    ctx.profile_enable(True)
-    for _ in range(args.steps):
-        step()
-    prof = ctx.profile_report()
-    ctx.profile_enable(False)
-    # end to end as the boundary hands buffers over when the caller keeps them on the host: u8 image in pageable
-    # host memory in, f32 depth in host memory out, H2D + D2H and their synchronisation included (never `value`)
-    e2e_ms = None
-    if rank == 0:
-        rgb_host = rgb.cpu().numpy()
-        ctx.extract_depth(rgb_host, f_norm)
-        t1 = time.perf_counter()
-        n_e2e = max(3, min(10, args.steps))
-        for _ in range(n_e2e):
+    if args.full:
+        # roofline leg: the same steps once more with every GEMM / attention / LayerNorm launch bracketed
+        # by HIP events on the launch stream (an event costs ~5 us of queue time, so it is kept out of the
+        # timed region above)
+        ctx.profile_enable(True)
+        for _ in range(args.steps):
+            step()
+        prof = ctx.profile_report()
+        ctx.profile_enable(False)
+        # end to end as the boundary hands buffers over when the caller keeps them on the host: u8 image in pageable
+        # host memory in, f32 depth in host memory out, H2D + D2H and their synchronisation included (never `value`)
+        e2e_ms = None
+        if rank == 0:
+            rgb_host = rgb.cpu().numpy()
             ctx.extract_depth(rgb_host, f_norm)
-        e2e_ms = (time.perf_counter() - t1) / n_e2e * 1e3
-    # calibration leg: outside the timed region, on a chip as warm as the steps left it.  FIVE passes of the two loops (about
-    # 0.25 s): one 25 ms pass reads +-3 % on the same box depending on the clock state it starts in (tools/calib_probe.py:
-    # 1885 / 1997 / 1911 TFLOP/s within one process), the median of five is what the normalisation uses
-    cal_runs = [ctx.calibrate() for _ in range(5)]
-    cal = dict(sorted(cal_runs, key=lambda c: c["mfma_tflops"])[2])
-    cal["copy_gbs"] = sorted(c["copy_gbs"] for c in cal_runs)[2]
-    cal["mfma_runs"] = [round(c["mfma_tflops"], 1) for c in cal_runs]
-    cal["copy_runs"] = [round(c["copy_gbs"], 1) for c in cal_runs]
+            t1 = time.perf_counter()
+            n_e2e = max(3, min(10, args.steps))
+            for _ in range(n_e2e):
+                ctx.extract_depth(rgb_host, f_norm)
+            e2e_ms = (time.perf_counter() - t1) / n_e2e * 1e3
+        # calibration leg: outside the timed region, on a chip as warm as the steps left it.  FIVE passes of the two loops (about
+        # 0.25 s): one 25 ms pass reads +-3 % on the same box depending on the clock state it starts in (tools/calib_probe.py:
+        # 1885 / 1997 / 1911 TFLOP/s within one process), the median of five is what the normalisation uses
+        cal_runs = [ctx.calibrate() for _ in range(5)]
+        cal = dict(sorted(cal_runs, key=lambda c: c["mfma_tflops"])[2])
+        cal["copy_gbs"] = sorted(c["copy_gbs"] for c in cal_runs)[2]
+        cal["mfma_runs"] = [round(c["mfma_tflops"], 1) for c in cal_runs]
+        cal["copy_runs"] = [round(c["copy_gbs"], 1) for c in cal_runs]
     per_rank_ms = [my_step_ms]
     if distributed:
         elapsed, per_rank_ms = reduce_over_ranks(elapsed, my_step_ms, world, "cuda")
@@ -521,15 +568,7 @@ def main():
     if rank == 0:
         value = whole_job_rate(world, B, args.steps, elapsed)
         tflop_img = TFLOP_PER_IMAGE_NOFOV if args.no_fov else TFLOP_PER_IMAGE_FOV
-        # dominant kernel: largest total time over the timed region
-        dom = max(prof, key=lambda k: k["total_ms"])
-        prof_ms = sum(k["total_ms"] for k in prof)
-        dom_ms = dom["total_ms"] / dom["launches"]
-        traffic, alg_bytes, mfma_util, pmc_note = pmc_traffic(dom["kernel"])
-        achieved = dom["flops"] / dom["launches"] / (dom_ms * 1e-3) / 1e12
-        peak = MFMA_PEAK_TFLOPS_FP8 if "<fp8," in dom["kernel"] else MFMA_PEAK_TFLOPS
         step_ms = elapsed / args.steps * 1e3
-        kernels = sorted(prof, key=lambda k: -k["total_ms"])
         out = {
             "metric": "1536x1536 depth-maps/sec",
             "value": round(value, 3),
@@ -538,7 +577,10 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(step_ms, 3),
-            "end_to_end_ms_per_step": None if e2e_ms is None else round(e2e_ms, 3),
+        }
+        if args.full:
+            out["end_to_end_ms_per_step"] = None if e2e_ms is None else round(e2e_ms, 3)
+        out.update({
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -559,8 +601,6 @@ def main():
                 "f_norm": "1.0" if args.no_fov else "FOV head (mod.rs:343-358)",
                 "parallelism": f"image-parallel, {world} process(es), one per GPU; packed weights by one RCCL "
                                f"broadcast at start-up ({t_load:.1f} s incl. synthetic init)",
-                "end_to_end": "end_to_end_ms_per_step: u8 image in pageable host memory in, f32 depth in host memory out "
-                              "(H2D 7.1 MB + D2H 9.4 MB per image and their synchronisation included), rank 0",
                 "per_rank_ms_per_step": [round(v, 3) for v in per_rank_ms],
                 "weights_broadcast": ("none (one rank)" if world == 1 else
                                       ("me_bcast_weights: the library's own RCCL communicator" if os.environ.get("ME_NATIVE_RCCL") == "1"
@@ -571,7 +611,19 @@ def main():
                 "tflop_per_image": tflop_img,
                 "model_tflops": round(value * tflop_img, 1),
             },
-            "roofline": {
+        })
+        if args.full:
+            out["config"]["end_to_end"] = ("end_to_end_ms_per_step: u8 image in pageable host memory in, f32 depth in host "
+                                           "memory out (H2D 7.1 MB + D2H 9.4 MB per image and their synchronisation included), rank 0")
+            # dominant kernel: largest total time over the profiled pass
+            dom = max(prof, key=lambda k: k["total_ms"])
+            prof_ms = sum(k["total_ms"] for k in prof)
+            dom_ms = dom["total_ms"] / dom["launches"]
+            traffic, alg_bytes, mfma_util, pmc_note = pmc_traffic(dom["kernel"])
+            achieved = dom["flops"] / dom["launches"] / (dom_ms * 1e-3) / 1e12
+            peak = MFMA_PEAK_TFLOPS_FP8 if "<fp8," in dom["kernel"] else MFMA_PEAK_TFLOPS
+            kernels = sorted(prof, key=lambda k: -k["total_ms"])
+            out["roofline"] = {
                 "bound": "mfma",
                 "kernel": dom["kernel"],
                 "launches_per_step": dom["launches"] / args.steps,
@@ -586,41 +638,44 @@ def main():
                 "mfma_util_pmc": None if mfma_util is None else round(mfma_util, 3),
                 "share_of_profiled_kernel_time": round(dom["total_ms"] / prof_ms, 3),
                 "whole_step_frac": round(value / world * tflop_img / MFMA_PEAK_TFLOPS, 4),
-            },
-            "kernels": [kernel_row(k, args.steps) for k in kernels[:10]],
-        }
-        out["calibration"] = calibration_object(cal, value)
-        out["value_normalised"] = out["calibration"]["value_normalised"]
+            }
+            out["kernels"] = [kernel_row(k, args.steps) for k in kernels[:10]]
+            out["calibration"] = calibration_object(cal, value)
+            out["value_normalised"] = out["calibration"]["value_normalised"]
         if args_chain:
-            # configs[4]: `value` is whole-chain images/s; the legs are per image, host wall clock around synchronised
+            # configs[4]: `value` is whole-chain images/s; the legs (--full) are per image, host wall clock around synchronised
             # sections (depth = the model step, raster = DepthMap::new + stereogram kernels, obj = mesh index +
             # vertex kernels + text formatting + file write on tmpfs)
             out["config"]["workload"] = (f"BASELINE.json configs[4] per GPU: {B} image(s) per step, depth -> DepthMap::new -> "
                                          "stereogram -> textured OBJ + MTL on tmpfs")
-            out["chain"] = {"depth_ms_per_image": round(chain_report["depth"], 3),
-                            "raster_ms_per_image": round(chain_report["raster"], 3),
-                            "obj_ms_per_image": round(chain_report["obj"], 3),
-                            "obj_legs_ms_per_image": {
-                                "mesh_index_and_text_kernels": round(chain_report["obj_device"], 3),
-                                "d2h_of_the_text": round(chain_report["obj_d2h"], 3),
-                                "file_write_tmpfs": round(chain_report["obj_file"], 3)},
-                            "obj_bytes": chain_report["obj_bytes"],
-                            "write_behind": bool(write_behind),
-                            "pipelined": bool(chain_pipelined),
-                            "host_ms_per_step": ({k: round(v / max(1, chain_host["steps"]), 3) for k, v in chain_host.items() if k != "steps"}
-                                                 if chain_pipelined else None),
-                            "form": ("step k + 1's me_extract_depth is queued before step k's output calls, which run on the "
-                                     "context's output stream behind the step that wrote their depth buffer "
-                                     "(me_ctx_set_output_overlap); nothing is synchronised between legs inside the timed region; "
-                                     "the *_ms_per_image legs are a separate, synchronised diagnostic pass"
-                                     if chain_pipelined else "serial: every leg synchronised (ME_CHAIN_SERIAL=1)"),
-                            "node_write_ceiling": chain_ceiling_note(world, value),
-                            "note": "the file write is the host kernel's page-cache copy (about 2.8 GB/s on tmpfs whatever the "
-                                    "thread count); everything before it runs on the GPU.  With write_behind "
-                                    "(me_ctx_set_write_behind) a host thread writes image i's file while the GPU works on "
-                                    "image i + 1; file_write_tmpfs is then what the CALLER waited (hand-over, or an earlier "
-                                    "file still being written), and every file is flushed inside the timed region"}
-        if world == 1 and not args.no_cpu_baseline:
+            out["chain"] = {}
+            if chain_report is not None:
+                out["chain"].update({
+                    "depth_ms_per_image": round(chain_report["depth"], 3),
+                    "raster_ms_per_image": round(chain_report["raster"], 3),
+                    "obj_ms_per_image": round(chain_report["obj"], 3),
+                    "obj_legs_ms_per_image": {
+                        "mesh_index_and_text_kernels": round(chain_report["obj_device"], 3),
+                        "d2h_of_the_text": round(chain_report["obj_d2h"], 3),
+                        "file_write_tmpfs": round(chain_report["obj_file"], 3)},
+                    "obj_bytes": chain_report["obj_bytes"]})
+            out["chain"].update({
+                "write_behind": bool(write_behind),
+                "pipelined": bool(chain_pipelined),
+                "host_ms_per_step": ({k: round(v / max(1, chain_host["steps"]), 3) for k, v in chain_host.items() if k != "steps"}
+                                     if chain_pipelined else None),
+                "form": ("step k + 1's me_extract_depth is queued before step k's output calls, which run on the "
+                         "context's output stream behind the step that wrote their depth buffer "
+                         "(me_ctx_set_output_overlap); nothing is synchronised between legs inside the timed region; "
+                         "the *_ms_per_image legs (--full) are a separate, synchronised diagnostic pass"
+                         if chain_pipelined else "serial: every leg synchronised (ME_CHAIN_SERIAL=1)"),
+                "node_write_ceiling": chain_ceiling_note(world, value),
+                "note": "the file write is the host kernel's page-cache copy (about 2.8 GB/s on tmpfs whatever the "
+                        "thread count); everything before it runs on the GPU.  With write_behind "
+                        "(me_ctx_set_write_behind) a host thread writes image i's file while the GPU works on "
+                        "image i + 1; file_write_tmpfs is then what the CALLER waited (hand-over, or an earlier "
+                        "file still being written), and every file is flushed inside the timed region"})
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, weights, args.cpu_windows)
         print(json.dumps(out), flush=True)
     if distributed:

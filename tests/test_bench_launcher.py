@@ -146,3 +146,22 @@ def test_calibration_object_restates_the_rate_for_the_reference_box():
     dead = dict(cal, mfma_tflops=0.0)
     out = bench.calibration_object(dead, 44.0)
     assert out["value_normalised"] is None and out["box_speed_vs_reference"] is None
+
+
+def test_dumped_outputs_keep_to_the_budget(tmp_path):
+    """--dump-outputs: arrays that fit are written whole in float32; arrays that do not keep the same share of their
+    elements each, drawn with a fixed seed -- the same sample in every run -- and stay within the byte budget."""
+    import numpy as np
+    depth = np.random.default_rng(1).random((1, 64, 64), dtype=np.float32)
+    stereo = np.random.default_rng(2).integers(0, 256, (1, 64, 64, 3), dtype=np.uint8)
+    bench.write_outputs(str(tmp_path / "whole"), {"depth": depth, "stereogram": stereo})
+    got = np.load(tmp_path / "whole" / "stereogram.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, stereo) and np.array_equal(np.load(tmp_path / "whole" / "depth.npy"), depth)
+    budget = 20000
+    for run in ("a", "b"):
+        bench.write_outputs(str(tmp_path / run), {"depth": depth, "stereogram": stereo}, max_bytes=budget)
+        assert sum(f.stat().st_size for f in (tmp_path / run).iterdir()) <= budget
+    a, b = np.load(tmp_path / "a" / "depth.npy"), np.load(tmp_path / "b" / "depth.npy")
+    assert a.dtype == np.float32 and 0 < a.size < depth.size and np.array_equal(a, b)
+    assert np.isin(a, depth).all()
+    assert np.load(tmp_path / "a" / "stereogram.npy").size == 3 * a.size      # each array keeps the same share

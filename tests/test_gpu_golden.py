@@ -31,14 +31,14 @@ def test_against_golden(dtype, tol):
 
 
 def test_bench_line_contract():
-    """bench.py prints ONE JSON line with the driver's keys, a roofline object measured live and a CPU baseline."""
+    """bench.py --full prints ONE JSON line with the driver's keys, a roofline object measured live and a CPU baseline."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-windows", "1"],
-                       capture_output=True, text=True, timeout=900, cwd=root)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-windows", "1",
+                        "--full"], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -57,3 +57,30 @@ def test_bench_line_contract():
     cb = d["cpu_baseline"]
     assert cb["kind"] in ("port", "reference") and cb["cores"] >= 1 and cb["value"] > 0 and cb["sample"]
     assert d["value"] > 100 * cb["value"]
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run prints the headline only (no pass of its own after the timed steps), and --dump-outputs
+    writes what the last timed step returned: bit for bit the depth the library computes for the same seeded inputs."""
+    import json
+    import subprocess
+    import sys
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "1536x1536 depth-maps/sec" and d["unit"] == "depth-maps/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f16" and d["steps"] == 3 and d["warmup"] == 1
+    assert abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 0.02          # one image per step
+    for key in ("roofline", "kernels", "calibration", "cpu_baseline", "end_to_end_ms_per_step"):
+        assert key not in d, key
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["depth.npy"]
+    got = np.load(tmp_path / "depth.npy")
+    assert got.dtype == np.float32 and got.shape == (1, 1536, 1536) and np.isfinite(got).all()
+    ctx = loaded_ctx("full", "f16")
+    rgb = torch.from_numpy(synthetic_images(1, ctx.cfg.img_size, "structured", seed=4321)).cuda()
+    assert np.array_equal(got, ctx.extract_depth(rgb, None))

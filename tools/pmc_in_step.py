@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """PMC counters of the kernels INSIDE the step (roofline.traffic comes from stand-alone probes of the step's
-shapes, tools/pmc_collect.py): rocprofv3 --pmc passes over `bench.py --steps 3 --warmup 1 --no-cpu-baseline` itself, one counter
+shapes, tools/pmc_collect.py): rocprofv3 --pmc passes over `bench.py --steps 3 --warmup 1 --full --no-cpu-baseline` itself, one counter
 group per pass, aggregated per kernel name.
 
     python3 tools/pmc_in_step.py out.json
@@ -32,7 +32,8 @@ def main():
     for counters in PASSES:
         out = os.path.join(work, "_".join(counters)[:60])
         cmd = ["rocprofv3", "--pmc", *counters, "--kernel-trace", "--output-format", "csv", "-d", out, "-o", "p", "--",
-               sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+               sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full",
+               "--no-cpu-baseline"]
         r = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                            timeout=600, text=True)
         if r.returncode != 0:
@@ -62,7 +63,7 @@ def main():
         result[k] = r
     sys.path.insert(0, ROOT)
     import bench
-    result["_meta"] = {"source_sha": bench.kernel_source_sha(), "command": "bench.py --steps 3 --warmup 1 --no-cpu-baseline under rocprofv3 --pmc",
+    result["_meta"] = {"source_sha": bench.kernel_source_sha(), "command": "bench.py --steps 3 --warmup 1 --full --no-cpu-baseline under rocprofv3 --pmc",
                        "note": "per-launch averages over every dispatch of the kernel in the profiled run (warm-up, timed and end-to-end steps)"}
     json.dump(result, open(out_json, "w"), indent=1)
     rows = sorted(((k, v) for k, v in result.items() if k != "_meta" and "hbm_bytes_per_launch" in v),
