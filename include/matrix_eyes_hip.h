@@ -279,6 +279,32 @@ int32_t me_depthmap_rgb(me_ctx* ctx, const float* depth, int64_t count, float mi
 int32_t me_depthmap_rgb_dev_range(me_ctx* ctx, const float* depth, int64_t count, const float* minmax_dev,
                                   uint8_t* rgb);
 
+/* ---- Lanczos3 resampling (the `image` crate's imageops::resize, FilterType::Lanczos3) ---------------------- */
+
+/* Largest width or height, in or out, that the resampler accepts (index arithmetic is 64-bit; the f32
+   intermediate of w * nh * 3 floats is the context's scratch: 3 GiB at 16384 x 16384). */
+#define ME_RESIZE_MAX_DIM 16384
+
+/* reconstruction.rs:107-113, output.rs:133-137, output.rs:206-218: DynamicImage::resize_exact(nw, nh, Lanczos3)
+   for 8-bit RGB: src [h,w,3] -> dst [nh,nw,3], byte for byte what the crate (0.25.10, imageops/sample.rs) writes:
+   vertical pass into an unclamped f32 intermediate, horizontal pass, round(clamp(t, 0, 255)); the same size in and
+   out is a copy.  Host or device pointers; enqueued on the context's stream: a device dst is not synchronised, a
+   host dst is.  Needs a context, not finalised weights.  Chained with me_extract_depth_u8 on a device dst this is
+   the photo path of reconstruction.rs:107-124.  src and dst overlapping (or equal) is ME_ERR_BAD_ARG; a
+   non-positive size or one above ME_RESIZE_MAX_DIM is ME_ERR_BAD_SHAPE.  Scratch (the staged source, the
+   intermediate, the per-axis weight tables) belongs to the context and grows to the high-water mark. */
+int32_t me_resize_lanczos3_rgb8(me_ctx* ctx, const uint8_t* src, int32_t w, int32_t h,
+                                uint8_t* dst, int32_t nw, int32_t nh);
+
+/* output.rs:123-139 output_depth_map up to the save: the colour map into RgbImage::new(data_width, data_height),
+   filled in data order (:124-131), then the resize to the original size (:133-137).  depth [data_height,data_width]
+   is DepthMap.data; rgb [out_h,out_w,3].  minmax_dev NULL: the two scalars are used; else the range
+   me_depth_clamp_minmax_async left on the device (min_depth / max_depth ignored).  Pointers, stream and errors as
+   me_resize_lanczos3_rgb8. */
+int32_t me_depthmap_rgb_resized(me_ctx* ctx, const float* depth, int32_t data_width, int32_t data_height,
+                                float min_depth, float max_depth, const float* minmax_dev,
+                                int32_t out_w, int32_t out_h, uint8_t* rgb);
+
 /* output.rs:264-363 IndexedMesh::new + for_each_face + remap_face.
    depth [height,width] (DepthMap.data, stride `width`).  vertex_index [height*width]: the
    first-use vertex id or -1.  faces [nfaces,3] remapped vertex ids in the reference's
@@ -299,7 +325,7 @@ int32_t me_mesh_vertices(me_ctx* ctx, const float* depth, int32_t width, int32_t
    anything else is ME_ERR_BAD_ARG; for ".obj" in texture mode also "<stem>.mtl" next to it).
    depth [height,width] is DepthMap.data (already clamped).  vertex_colors: NULL, or u8
    [height*width,3] = the source image resized to the depth map (only read in ME_VERTEX_COLOR
-   mode; the Lanczos resize itself is the caller's). Text output is byte-identical to
+   mode; me_resize_lanczos3_rgb8 makes it, output.rs:206-218). Text output is byte-identical to
    the reference's: numbers are printed like Rust's `{}` for f64 (shortest round-trip, never
    scientific). */
 int32_t me_output_mesh(me_ctx* ctx, const float* depth, int32_t width, int32_t height,

@@ -137,6 +137,15 @@ int32_t me_op_cast_to32(me_ctx* ctx, const void* src16, float* dst, int64_t coun
    {"kernel", "launches", "total_ms", "flops", "bytes"} (algorithmic work, summed over launches). */
 int32_t me_profile_enable(me_ctx* ctx, int32_t on);
 int32_t me_profile_report(me_ctx* ctx, char* json, int64_t capacity);
+/* The per-axis table of image 0.25.10 imageops/sample.rs (vertical_sample / horizontal_sample with the Lanczos3
+   kernel) that me_resize_lanczos3_rgb8 runs on: for each output index o of an axis resampled from len_in to len_out
+   samples, left[o], count[o] and, packed one index after the other in `weights`, its count[o] normalised weights
+   (taps left[o] .. left[o] + count[o] - 1).  Returns the number of weights; when weights_cap is smaller, the number
+   needed, writing nothing; < 0 on bad arguments (a length outside [1, ME_RESIZE_MAX_DIM], a null array).
+   Unlike the rest of this header it has no context and works on HOST arrays only (the table is built on the host,
+   with libm's sinf, whatever the device): it can be tested on a machine without a GPU. */
+int64_t me_op_lanczos3_table(int32_t len_in, int32_t len_out, int32_t* left, int32_t* count,
+                             float* weights, int64_t weights_cap);
 /* Names of the GEMM tile configurations (for reports). */
 int32_t me_op_gemm_config_count(void);
 const char* me_op_gemm_config_name(int32_t cfg);

@@ -48,6 +48,15 @@ impl HipDevice {
         self.check(unsafe { ffi::me_output_flush(self.ctx) })
     }
 
+    /// DynamicImage::resize_exact(nw, nh, FilterType::Lanczos3) for an RGB8 buffer (reconstruction.rs:107-113,
+    /// output.rs:206-218) on the GPU: the bytes `image` 0.25.10 writes.  `rgb` is `[h, w, 3]`, the result `[nh, nw, 3]`.
+    pub fn resize_exact_lanczos3(&self, rgb: &[u8], w: u32, h: u32, nw: u32, nh: u32) -> Result<Vec<u8>, HipError> {
+        assert_eq!(rgb.len(), w as usize * h as usize * 3);
+        let mut out = vec![0u8; nw as usize * nh as usize * 3];
+        self.check(unsafe { ffi::me_resize_lanczos3_rgb8(self.ctx, rgb.as_ptr(), w as i32, h as i32, out.as_mut_ptr(), nw as i32, nh as i32) })?;
+        Ok(out)
+    }
+
     fn check(&self, rc: i32) -> Result<(), HipError> {
         if rc == ffi::ME_OK {
             Ok(())
@@ -124,11 +133,23 @@ impl<'d> DepthMap<'d> {
         Ok(DepthMap { device, data, data_width: dims[0], data_height: dims[1], original_size, range: (mn, mx) })
     }
 
-    /// output.rs:123-131 output_depth_map (before resize_exact + save, which stay in Rust)
+    /// output.rs:123-131 output_depth_map before resize_exact + save (`depth_map_rgb_resized` includes the resize)
     pub fn depth_map_rgb(&self) -> Result<Vec<u8>, HipError> {
         let mut rgb = vec![0u8; self.data.len() * 3];
         self.device.check(unsafe {
             ffi::me_depthmap_rgb(self.device.ctx, self.data.as_ptr(), self.data.len() as i64, self.range.0, self.range.1, rgb.as_mut_ptr())
+        })?;
+        Ok(rgb)
+    }
+
+    /// output.rs:123-137 output_depth_map up to the save: the colour map and the resize to the original size, both on
+    /// the GPU; the result is `RgbImage::from_raw(original_size.0, original_size.1, ..)`
+    pub fn depth_map_rgb_resized(&self) -> Result<Vec<u8>, HipError> {
+        let (ow, oh) = self.original_size;
+        let mut rgb = vec![0u8; ow as usize * oh as usize * 3];
+        self.device.check(unsafe {
+            ffi::me_depthmap_rgb_resized(self.device.ctx, self.data.as_ptr(), self.data_width as i32, self.data_height as i32, self.range.0,
+                                         self.range.1, null(), ow as i32, oh as i32, rgb.as_mut_ptr())
         })?;
         Ok(rgb)
     }

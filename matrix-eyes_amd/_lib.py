@@ -78,6 +78,8 @@ SIGNATURES = {
     "me_stereogram_dev_range": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _f32, _vp, _vp]),
     "me_depthmap_rgb_dev_range": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "me_depthmap_rgb": (_i32, [_vp, _vp, _i64, _f32, _f32, _vp]),
+    "me_resize_lanczos3_rgb8": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _i32]),
+    "me_depthmap_rgb_resized": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _vp, _i32, _i32, _vp]),
     "me_mesh_index": (_i32, [_vp, _vp, _i32, _i32, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "me_mesh_vertices": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _u32, _u32, _vp, _vp]),
     "me_output_mesh": (_i32, [_vp, _vp, _i32, _i32, _u32, _u32, C.c_char_p, C.c_char_p, _i32, _vp]),
@@ -118,6 +120,7 @@ SIGNATURES = {
     "me_op_cast_to32": (_i32, [_vp, _vp, _vp, _i64]),
     "me_profile_enable": (_i32, [_vp, _i32]),
     "me_profile_report": (_i32, [_vp, C.c_char_p, _i64]),
+    "me_op_lanczos3_table": (_i64, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32), _i64]),
     "me_op_gemm_config_count": (_i32, []),
     "me_op_gemm_config_name": (C.c_char_p, [_i32]),
 }

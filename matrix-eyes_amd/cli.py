@@ -115,8 +115,14 @@ def main(argv: Optional[List[str]] = None) -> int:
         args = parse(sys.argv[1:] if argv is None else argv)
     except UsageExit as e:
         return int(e.code)
-    from .depth_pro import DepthProModelLoader
+    from ._lib import MatrixEyesError
+    from .depth_pro import DepthProModelLoader, resolve_resampler
     from .reconstruction import extract_depth
+    try:
+        resolve_resampler()                  # MATRIX_EYES_RESAMPLER = pillow | device
+    except MatrixEyesError as err:
+        print(f"MATRIX_EYES_RESAMPLER: {err.message}", file=sys.stderr)
+        return 2
     loader = DepthProModelLoader(args.checkpoint_path, args.convert_checkpoints)
     try:
         extract_depth(0, loader, args.img_src, args.img_out, args.focal_length, args.output_format,

@@ -320,6 +320,7 @@ void me_ctx_destroy(me_ctx* ctx) {
     if (me::current_status_word() == ctx->status_dev) me::set_current_status_word(nullptr);
     for (auto& kv : ctx->bufs)
         if (kv.second.p) (void)hipFree(kv.second.p);
+    me::free_resample_tables(ctx);
     if (ctx->arena) (void)hipFree(ctx->arena);
     if (ctx->arena8) (void)hipFree(ctx->arena8);
     if (ctx->status_dev) (void)hipFree(ctx->status_dev);
@@ -957,6 +958,50 @@ int32_t me_stereogram_dev_range(me_ctx* ctx, const float* depth, int32_t rows, i
     OutputScope out_scope(ctx, depth);
     ME_CHECK(minmax_dev && is_device_ptr(minmax_dev), ME_ERR_BAD_ARG, "me_stereogram_dev_range: minmax_dev");
     stereogram_impl(ctx, depth, rows, cols, 0.f, 0.f, minmax_dev, out_w, out_h, amplitude, noise, out);
+    ME_API_END(ctx)
+}
+
+namespace {
+void check_resize_shape(const char* who, int32_t w, int32_t h, int32_t nw, int32_t nh) {
+    ME_CHECK(w > 0 && h > 0 && nw > 0 && nh > 0, ME_ERR_BAD_SHAPE, "%s: %dx%d -> %dx%d", who, w, h, nw, nh);
+    ME_CHECK(w <= ME_RESIZE_MAX_DIM && h <= ME_RESIZE_MAX_DIM && nw <= ME_RESIZE_MAX_DIM && nh <= ME_RESIZE_MAX_DIM,
+             ME_ERR_BAD_SHAPE, "%s: %dx%d -> %dx%d: a side exceeds ME_RESIZE_MAX_DIM (%d)", who, w, h, nw, nh,
+             ME_RESIZE_MAX_DIM);
+}
+}  // namespace
+
+int32_t me_resize_lanczos3_rgb8(me_ctx* ctx, const uint8_t* src, int32_t w, int32_t h, uint8_t* dst, int32_t nw,
+                                int32_t nh) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(src && dst, ME_ERR_BAD_ARG, "me_resize_lanczos3_rgb8: null pointer");
+    check_resize_shape("me_resize_lanczos3_rgb8", w, h, nw, nh);
+    const size_t nin = (size_t)w * h * 3, nout = (size_t)nw * nh * 3;
+    const uintptr_t a = (uintptr_t)src, b = (uintptr_t)dst;
+    ME_CHECK(a + nin <= b || b + nout <= a, ME_ERR_BAD_ARG, "me_resize_lanczos3_rgb8: src and dst overlap");
+    const uint8_t* s = (const uint8_t*)to_device(ctx, src, nin, "resample.src");
+    OutBuf o = out_buf(ctx, dst, nout, "resample.dst");
+    resize_lanczos3_rgb8(ctx, s, w, h, (uint8_t*)o.dev, nw, nh);
+    finish(ctx, o);
+    ME_API_END(ctx)
+}
+
+int32_t me_depthmap_rgb_resized(me_ctx* ctx, const float* depth, int32_t data_width, int32_t data_height,
+                                float min_depth, float max_depth, const float* minmax_dev, int32_t out_w,
+                                int32_t out_h, uint8_t* rgb) {
+    ME_API_BEGIN(ctx)
+    OutputScope out_scope(ctx, depth);
+    ME_CHECK(depth && rgb, ME_ERR_BAD_ARG, "me_depthmap_rgb_resized: null pointer");
+    ME_CHECK(!minmax_dev || is_device_ptr(minmax_dev), ME_ERR_BAD_ARG, "me_depthmap_rgb_resized: minmax_dev");
+    check_resize_shape("me_depthmap_rgb_resized", data_width, data_height, out_w, out_h);
+    const int64_t count = (int64_t)data_width * data_height;
+    const float* d = (const float*)to_device(ctx, depth, (size_t)count * 4, "out.depth");
+    // output.rs:124-131: RgbImage::new(data_width, data_height) filled in data order, then :133-137 the resize
+    uint8_t* mapped = (uint8_t*)site_buf(ctx, "out.rgb.native", (size_t)count * 3);
+    depthmap_rgb_launch(d, count, min_depth, max_depth, minmax_dev, mapped, ctx->stream);
+    OutBuf o = out_buf(ctx, rgb, (size_t)out_w * out_h * 3, "out.rgb");
+    ME_CHECK((uint8_t*)o.dev != mapped, ME_ERR_BAD_ARG, "me_depthmap_rgb_resized: rgb is the context's own scratch");
+    resize_lanczos3_rgb8(ctx, mapped, data_width, data_height, (uint8_t*)o.dev, out_w, out_h);
+    finish(ctx, o);
     ME_API_END(ctx)
 }
 

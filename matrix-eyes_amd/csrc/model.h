@@ -109,6 +109,18 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+// One axis of the Lanczos3 resampler (resample.hip): the host-built table of lanczos_table.cpp on the device.
+// span[o] = {left, count}; the i-th weight of output index o is w[i * len_out + o] (tap-major, so that neighbouring
+// lanes of the horizontal pass read neighbouring words).
+struct ResampleTable {
+    int32_t len_in = 0, len_out = 0;
+    int32_t run = 0;          // output pixels per workgroup of the horizontal pass; 0: its span does not fit the LDS
+    int32_t lds_floats = 0;   // floats of LDS that run needs
+    int2* span = nullptr;
+    float* w = nullptr;
+    uint64_t stamp = 0;       // last use, for eviction
+};
+
 }  // namespace me
 
 // The opaque C handle.
@@ -218,6 +230,12 @@ struct me_ctx {
 
     // persistent workspaces keyed by site name (no aliasing: zero borders stay zero)
     std::map<std::string, me::DevBuf> bufs;
+
+    // Lanczos3 tables by (len_in, len_out), at most kMaxResampleTables; one is only freed behind a synchronise of
+    // both streams (resample.hip resample_table): a queued kernel may still read it
+    static constexpr size_t kMaxResampleTables = 16;
+    std::vector<me::ResampleTable> rs_tables;
+    uint64_t rs_stamp = 0;
 
     // The whole extract_depth step as one hipGraph (shapes are static per batch size).  A call whose pointers
     // all live on the device and that needs no host callback is enqueued eagerly the first time it is seen,
@@ -338,6 +356,10 @@ struct OutputScope {
     OutputScope(const OutputScope&) = delete;
     OutputScope& operator=(const OutputScope&) = delete;
 };
+
+// resample.hip: DynamicImage::resize_exact(nw, nh, Lanczos3) for 8-bit RGB, device pointers, on ctx->stream
+void resize_lanczos3_rgb8(me_ctx* ctx, const uint8_t* src_dev, int32_t w, int32_t h, uint8_t* dst_dev, int32_t nw, int32_t nh);
+void free_resample_tables(me_ctx* ctx);
 
 // calibrate.hip: the two fixed loops of bench.py's calibration leg (out[6])
 void calibrate(me_ctx* ctx, double* out);

@@ -45,6 +45,20 @@ def _out(out, shape, dtype=np.float32):
     return C.c_void_p(out.ctypes.data), out
 
 
+RESAMPLERS = ("pillow", "device")
+
+
+def resolve_resampler(resampler=None) -> str:
+    """Who makes the Lanczos3 resizes of reconstruction.rs:107-113 and output.rs:133-137, 206-218: "pillow" (the
+    default: Pillow's filter, within one code of the reference's) or "device" (me_resize_lanczos3_rgb8: the `image`
+    crate's sampler byte for byte, as the compiled CLI runs it).  None reads MATRIX_EYES_RESAMPLER; anything but the
+    two names is an argument error."""
+    value = os.environ.get("MATRIX_EYES_RESAMPLER", "pillow") if resampler is None else resampler
+    if value not in RESAMPLERS:
+        raise L.MatrixEyesError(1, f"resampler {value!r}: expected one of {', '.join(RESAMPLERS)}")
+    return value
+
+
 class Context:
     """One GPU: stream, packed weights, workspaces (`me_ctx`)."""
 
@@ -247,6 +261,24 @@ class Context:
         p, keep = _in_ptr(rgb, np.uint8)
         po, out = _out(out, (B, 3, S, S))
         self._check(self.lib.me_preprocess_u8(self._h, p, B, po))
+        return out
+
+    def resize_lanczos3(self, rgb, size, out=None):
+        """DynamicImage::resize_exact(nw, nh, Lanczos3) (reconstruction.rs:107-113, output.rs:133-137, 206-218) on the
+        GPU, the `image` crate's bytes.  rgb: uint8 [h, w, 3], numpy (-> numpy) or a CUDA torch tensor (-> a CUDA
+        tensor, queued on the context's stream, no host copy); size = (nw, nh)."""
+        nw, nh = int(size[0]), int(size[1])
+        if len(rgb.shape) != 3 or rgb.shape[2] != 3:
+            raise L.MatrixEyesError(2, f"resize_lanczos3: uint8 [h, w, 3] expected, got {tuple(rgb.shape)}")
+        if nw <= 0 or nh <= 0:
+            raise L.MatrixEyesError(2, f"resize_lanczos3: target size {nw}x{nh}")
+        h, w = int(rgb.shape[0]), int(rgb.shape[1])
+        p, keep = _in_ptr(rgb, np.uint8)
+        if out is None and _is_torch(rgb) and rgb.is_cuda:
+            import torch
+            out = torch.empty((nh, nw, 3), dtype=torch.uint8, device=rgb.device)
+        po, out = _out(out, (nh, nw, 3), np.uint8)
+        self._check(self.lib.me_resize_lanczos3_rgb8(self._h, p, w, h, po, nw, nh))
         return out
 
     def vit_forward_features(self, which: int, xs, intermediate_blocks: Sequence[int] = ()):

@@ -50,6 +50,12 @@ Device::Device() {
     const char* dev = std::getenv("MATRIX_EYES_DEVICE");
     const char* dt = std::getenv("MATRIX_EYES_DTYPE");
     const char* model = std::getenv("MATRIX_EYES_MODEL");  // "tiny": the test geometry of the parity suite
+    if (const char* rs = std::getenv("MATRIX_EYES_RESAMPLER")) {
+        if (std::strcmp(rs, "host") == 0)
+            device_resampler_ = false;
+        else if (std::strcmp(rs, "device") != 0)
+            throw ModelError(ME_ERR_BAD_ARG, std::string("MATRIX_EYES_RESAMPLER=") + rs + ": expected host or device");
+    }
     me_model_config cfg;
     me_default_config(&cfg);
     if (model && std::strcmp(model, "tiny") == 0) {
@@ -75,6 +81,19 @@ void Device::set_write_behind(int files_in_flight) const {
 
 void Device::flush_outputs() const {
     if (me_output_flush(ctx_) != ME_OK) throw output::OutputError(me_last_error(ctx_));  // OutputError::Io of a file written behind
+}
+
+RgbImage Device::resize_exact_lanczos3(const RgbImage& img, uint32_t width, uint32_t height) const {
+    if (!device_resampler_) return matrix_eyes::resize_exact_lanczos3(img, width, height);
+    if (img.width == 0 || img.height == 0 || width == 0 || height == 0 || img.width > (uint32_t)ME_RESIZE_MAX_DIM ||
+        img.height > (uint32_t)ME_RESIZE_MAX_DIM || width > (uint32_t)ME_RESIZE_MAX_DIM || height > (uint32_t)ME_RESIZE_MAX_DIM)
+        throw ImageError("cannot resize " + std::to_string(img.width) + "x" + std::to_string(img.height) + " to " +
+                         std::to_string(width) + "x" + std::to_string(height));
+    RgbImage out(width, height);
+    const int32_t rc = me_resize_lanczos3_rgb8(ctx_, img.data.data(), (int32_t)img.width, (int32_t)img.height, out.data.data(),
+                                               (int32_t)width, (int32_t)height);
+    if (rc != ME_OK) throw ImageError(std::string("cannot resize: ") + me_last_error(ctx_));
+    return out;
 }
 
 // ---- DepthProModelLoader -----------------------------------------------------------------------------
@@ -126,6 +145,18 @@ void DepthMap::output_image(const std::string& destination_path, const std::stri
 }
 
 void DepthMap::output_depth_map(const std::string& destination_path) const {
+    if (device_.device_resampler()) {  // the colour map and the resize chained on the GPU
+        RgbImage resized(original_width_, original_height_);
+        check_output(device_.ctx(), me_depthmap_rgb_resized(device_.ctx(), data_.data(), (int32_t)data_width_, (int32_t)data_height_, min_,
+                                                            max_, nullptr, (int32_t)original_width_, (int32_t)original_height_,
+                                                            resized.data.data()));
+        try {
+            save_image(resized, destination_path);
+        } catch (const ImageError& err) {
+            throw OutputError(err.what());
+        }
+        return;
+    }
     RgbImage out((uint32_t)data_width_, (uint32_t)data_height_);
     check_output(device_.ctx(), me_depthmap_rgb(device_.ctx(), data_.data(), (int64_t)data_.size(), min_, max_, out.data.data()));
     try {
@@ -164,7 +195,7 @@ void DepthMap::output_mesh(const std::string& destination_path, const std::strin
     std::vector<uint8_t> colors;
     if (mode == VertexMode::Color) {  // output.rs:206-218
         try {
-            colors = resize_exact_lanczos3(load_image(source_path), (uint32_t)data_width_, (uint32_t)data_height_).data;
+            colors = device_.resize_exact_lanczos3(load_image(source_path), (uint32_t)data_width_, (uint32_t)data_height_).data;
         } catch (const ImageError& err) {
             throw OutputError(err.what());
         }
@@ -197,6 +228,14 @@ struct ProgressReporter : ProgressListener {
 }  // namespace
 
 SourceImage SourceImage::load(const std::string& path, std::optional<float> focal_length_35mm, int size) {
+    return load_with(nullptr, path, focal_length_35mm, size);
+}
+
+SourceImage SourceImage::load(const Device& device, const std::string& path, std::optional<float> focal_length_35mm, int size) {
+    return load_with(&device, path, focal_length_35mm, size);
+}
+
+SourceImage SourceImage::load_with(const Device* device, const std::string& path, std::optional<float> focal_length_35mm, int size) {
     SourceImage s;
     RgbImage img;
     ImageMetadata meta;
@@ -210,7 +249,12 @@ SourceImage SourceImage::load(const std::string& path, std::optional<float> foca
     if (!s.focal_length_35mm && meta.focal_length_35mm) s.focal_length_35mm = (float)*meta.focal_length_35mm;
     img = apply_orientation(img, meta.orientation);  // :104-106
     s.original_width = img.width, s.original_height = img.height;
-    s.img = resize_exact_lanczos3(img, (uint32_t)size, (uint32_t)size);
+    try {
+        s.img = device ? device->resize_exact_lanczos3(img, (uint32_t)size, (uint32_t)size)
+                       : resize_exact_lanczos3(img, (uint32_t)size, (uint32_t)size);
+    } catch (const ImageError& err) {
+        throw ReconstructionError(std::string("Image error: ") + err.what());
+    }
     return s;
 }
 
@@ -226,7 +270,7 @@ void extract_depth(const Device& device, const DepthProModelLoader& model_loader
                    output::ImageOutputFormat image_format, output::VertexMode vertex_mode) {
     SourceImage img;
     try {
-        img = SourceImage::load(source_path, focal_length_35mm, device.image_size());
+        img = SourceImage::load(device, source_path, focal_length_35mm, device.image_size());
     } catch (const ReconstructionError& err) {
         std::fprintf(stderr, "Failed to load source image: %s\n", err.what());
         throw;

@@ -54,10 +54,16 @@ public:
     // threads (me_ctx_set_write_behind); flush_outputs() before the files are read -- a failed write surfaces there
     void set_write_behind(int files_in_flight) const;
     void flush_outputs() const;
+    // DynamicImage::resize_exact(width, height, FilterType::Lanczos3) (reconstruction.rs:107-113, output.rs:133-137,
+    // 206-218) on the GPU (me_resize_lanczos3_rgb8) -- or, with MATRIX_EYES_RESAMPLER=host, image_io's loop on one CPU
+    // core.  Both write the `image` crate's bytes; any other value of the variable fails the constructor.
+    bool device_resampler() const { return device_resampler_; }
+    RgbImage resize_exact_lanczos3(const RgbImage& img, uint32_t width, uint32_t height) const;
 
 private:
     me_ctx* ctx_ = nullptr;
     int image_size_ = IMG_SIZE;
+    bool device_resampler_ = true;
     mutable bool weights_loaded_ = false;
     friend class DepthProModelLoader;
 };
@@ -137,7 +143,12 @@ struct SourceImage {  // reconstruction.rs:74-81
     uint32_t original_width = 0, original_height = 0;
     std::optional<float> focal_length_35mm;
     static SourceImage load(const std::string& path, std::optional<float> focal_length_35mm, int size);  // :87-131
+    // the same with the resize made by `device` (Device::resize_exact_lanczos3)
+    static SourceImage load(const Device& device, const std::string& path, std::optional<float> focal_length_35mm, int size);
     std::optional<double> focal_length_px() const;                                                       // :145-152
+
+private:
+    static SourceImage load_with(const Device* device, const std::string& path, std::optional<float> focal_length_35mm, int size);
 };
 
 // reconstruction.rs:155-205

@@ -2,8 +2,11 @@
 //   host_selftest pt <checkpoint.pt>            one line per tensor: name dtype dims... fnv1a64(data)
 //   host_selftest png <in> <out>                decode, re-encode
 //   host_selftest resize <in> <w> <h> <out>     Lanczos3 resize_exact
+//   host_selftest resize-time <w> <h> <nw> <nh> the same loop on a picture of seeded random bytes, no files: prints
+//                                               "milliseconds fnv1a64(result)" (tools/bench_resize.py)
 //   host_selftest decode <in> <out> [oriented]  decode any supported format (optionally apply the EXIF
 //                                               orientation), write <out>; prints "orientation focal35 w h"
+#include <chrono>
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -43,6 +46,21 @@ int main(int argc, char** argv) {
             matrix_eyes::save_image(matrix_eyes::resize_exact_lanczos3(matrix_eyes::load_image(argv[2]), (uint32_t)std::atoi(argv[3]),
                                                                        (uint32_t)std::atoi(argv[4])),
                                     argv[5]);
+            return 0;
+        }
+        if (argc == 6 && !std::strcmp(argv[1], "resize-time")) {
+            matrix_eyes::RgbImage img((uint32_t)std::atoi(argv[2]), (uint32_t)std::atoi(argv[3]));
+            uint64_t state = 88172645463325252ull;  // xorshift64
+            for (uint8_t& b : img.data) {
+                state ^= state << 13, state ^= state >> 7, state ^= state << 17;
+                b = (uint8_t)(state >> 32);
+            }
+            const auto t0 = std::chrono::steady_clock::now();
+            const matrix_eyes::RgbImage out = matrix_eyes::resize_exact_lanczos3(img, (uint32_t)std::atoi(argv[4]), (uint32_t)std::atoi(argv[5]));
+            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            uint64_t h = 1469598103934665603ull;
+            for (uint8_t b : out.data) h = (h ^ b) * 1099511628211ull;
+            std::printf("%.3f %016" PRIx64 "\n", ms, h);
             return 0;
         }
     } catch (const std::exception& err) {

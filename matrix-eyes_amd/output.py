@@ -9,7 +9,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib as L
-from .depth_pro import Context, _in_ptr
+from .depth_pro import Context, _in_ptr, resolve_resampler
 
 
 class VertexMode(enum.IntEnum):   # output.rs:33-38
@@ -120,14 +120,27 @@ class DepthMap:
         return uv, xyz
 
     # -- files
+    def depth_map_rgb_resized(self) -> np.ndarray:
+        """output.rs:123-137 up to the save, on the GPU: the colour map, then the `image` crate's Lanczos3 resize to
+        the original size -> u8 [original_height, original_width, 3]"""
+        mn, mx = self._range
+        out = np.empty((self.original_height, self.original_width, 3), np.uint8)
+        self.ctx._check(self.ctx.lib.me_depthmap_rgb_resized(
+            self.ctx.handle, C.c_void_p(self.data.ctypes.data), self.data_width, self.data_height, mn, mx, None,
+            self.original_width, self.original_height, C.c_void_p(out.ctypes.data)))
+        return out
+
     def output_image(self, destination_path: str, source_path: str, image_format: ImageOutputFormat,
-                     vertex_mode: VertexMode, noise=None):
-        """output.rs:100-121: dispatch on the destination suffix."""
+                     vertex_mode: VertexMode, noise=None, resampler=None):
+        """output.rs:100-121: dispatch on the destination suffix.  resampler: depth_pro.resolve_resampler."""
+        resampler = resolve_resampler(resampler)
         low = destination_path.lower()
         if low.endswith(".ply") or low.endswith(".obj"):
-            return self.output_mesh(destination_path, source_path, vertex_mode)
+            return self.output_mesh(destination_path, source_path, vertex_mode, resampler=resampler)
         from PIL import Image
-        if image_format.kind == "depthmap":
+        if image_format.kind == "depthmap" and resampler == "device":
+            Image.fromarray(self.depth_map_rgb_resized()).save(destination_path)
+        elif image_format.kind == "depthmap":
             img = Image.fromarray(self.depth_map_rgb())
             size = (self.original_width, self.original_height)
             if img.size != size:   # output.rs:133-137 (identity at the native size)
@@ -137,14 +150,18 @@ class DepthMap:
             Image.fromarray(self.stereogram(image_format.resize_scale, image_format.amplitude,
                                             noise)).save(destination_path)
 
-    def output_mesh(self, destination_path: str, source_path: str, vertex_mode: VertexMode):
+    def output_mesh(self, destination_path: str, source_path: str, vertex_mode: VertexMode, resampler=None):
         """output.rs:195-261 with ObjWriter / PlyWriter."""
+        resampler = resolve_resampler(resampler)
         colors = None
         if vertex_mode == VertexMode.Color:   # output.rs:206-218
             from PIL import Image
-            img = Image.open(source_path).convert("RGB").resize(
-                (self.data_width, self.data_height), Image.LANCZOS)
-            colors = np.ascontiguousarray(np.asarray(img, dtype=np.uint8))
+            img = Image.open(source_path).convert("RGB")
+            if resampler == "device":
+                colors = self.ctx.resize_lanczos3(np.asarray(img, dtype=np.uint8), (self.data_width, self.data_height))
+            else:
+                colors = np.ascontiguousarray(np.asarray(
+                    img.resize((self.data_width, self.data_height), Image.LANCZOS), dtype=np.uint8))
         self.ctx._check(self.ctx.lib.me_output_mesh(
             self.ctx.handle, C.c_void_p(self.data.ctypes.data), self.data_width, self.data_height,
             self.original_width, self.original_height, destination_path.encode(), source_path.encode(),
@@ -181,6 +198,18 @@ class DeviceDepthMap:
         self.ctx._check(self.ctx.lib.me_depthmap_rgb_dev_range(
             self.ctx.handle, C.c_void_p(self.data.data_ptr()), self.data.numel(), C.c_void_p(self.range_dev.data_ptr()),
             C.c_void_p(out.data_ptr())))
+        return out
+
+    def depth_map_rgb_resized(self, out=None):
+        """output.rs:123-137 up to the save, chained on the stream: colour map, then the Lanczos3 resize to the original
+        size -> CUDA u8 [original_height, original_width, 3]"""
+        import torch
+        shape = (self.original_height, self.original_width, 3)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.data.device)
+        self.ctx._check(self.ctx.lib.me_depthmap_rgb_resized(
+            self.ctx.handle, C.c_void_p(self.data.data_ptr()), self.data_width, self.data_height, 0.0, 0.0,
+            C.c_void_p(self.range_dev.data_ptr()), self.original_width, self.original_height, C.c_void_p(out.data_ptr())))
         return out
 
     def output_mesh(self, destination_path: str, source_path: str, vertex_mode: VertexMode = VertexMode.Texture,

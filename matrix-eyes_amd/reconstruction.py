@@ -1,6 +1,7 @@
 """Host-side mirror of reference src/reconstruction.rs: image front end and the
-top-level `extract_depth`.  File decoding, EXIF and Lanczos resampling are Pillow's (the reference
-uses the `image` and `kamadak-exif` crates); at the native 1536x1536 size the resize is the identity.
+top-level `extract_depth`.  File decoding and EXIF are Pillow's (the reference uses the `image` and
+`kamadak-exif` crates); the Lanczos resampling is Pillow's too by default, or the library's
+(resampler="device": the `image` crate's bytes); at the native 1536x1536 size the resize is the identity.
 The u8 -> float normalisation and HWC -> CHW (reconstruction.rs:114-124) run on the GPU
 (`me_extract_depth_u8`)."""
 import math
@@ -11,7 +12,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from .depth_pro import IMG_SIZE, DepthProModelLoader
+from .depth_pro import IMG_SIZE, DepthProModelLoader, resolve_resampler
 from .output import DepthMap, ImageOutputFormat, VertexMode
 
 _EXIF_IFD = 0x8769
@@ -29,9 +30,13 @@ class SourceImage:                          # reconstruction.rs:74-81
     focal_length_35mm: Optional[float]
 
     @staticmethod
-    def load(path: str, focal_length_35mm: Optional[float] = None, size: int = IMG_SIZE) -> "SourceImage":
-        """reconstruction.rs:87-131: decode, EXIF focal length, orientation, Lanczos3 to size x size"""
+    def load(path: str, focal_length_35mm: Optional[float] = None, size: int = IMG_SIZE, resampler=None,
+             ctx=None) -> "SourceImage":
+        """reconstruction.rs:87-131: decode, EXIF focal length, orientation, Lanczos3 to size x size.
+        resampler: depth_pro.resolve_resampler; "device" resizes on `ctx` (a Context, or a callable that returns one
+        and is only called once the file has been decoded)."""
         from PIL import Image, ImageOps
+        resampler = resolve_resampler(resampler)
         try:
             img = Image.open(path)
             img.load()
@@ -42,7 +47,13 @@ class SourceImage:                          # reconstruction.rs:74-81
         img = ImageOps.exif_transpose(img)  # decoder.orientation() + apply_orientation (:103-105)
         original_size = img.size
         img = img.convert("RGB")
-        if img.size != (size, size):        # resize_exact(.., Lanczos3) (:107-113)
+        if img.size != (size, size) and resampler == "device":   # resize_exact(.., Lanczos3) (:107-113)
+            if ctx is None:
+                raise ReconstructionError("Failed to load source image: the device resampler needs a context")
+            ctx = ctx() if callable(ctx) else ctx
+            return SourceImage(ctx.resize_lanczos3(np.asarray(img, dtype=np.uint8), (size, size)), original_size,
+                               focal_length_35mm)
+        if img.size != (size, size):
             img = img.resize((size, size), Image.LANCZOS)
         return SourceImage(np.ascontiguousarray(np.asarray(img, dtype=np.uint8)), original_size,
                            focal_length_35mm)
@@ -68,16 +79,19 @@ class SourceImage:                          # reconstruction.rs:74-81
 
 def extract_depth(device: int, model_loader: DepthProModelLoader, source_path: str, destination_path: str,
                   focal_length_35mm: Optional[float], image_format: ImageOutputFormat,
-                  vertex_mode: VertexMode, progress=None, noise=None) -> None:
-    """reconstruction.rs:155-205"""
+                  vertex_mode: VertexMode, progress=None, noise=None, resampler=None) -> None:
+    """reconstruction.rs:155-205.  resampler: depth_pro.resolve_resampler, passed down to every resize"""
+    resampler = resolve_resampler(resampler)
+    dtype = os.environ.get("MATRIX_EYES_DTYPE", "f16")   # f16 | bf16 | fp8, as the C++ twin
     try:
-        img = SourceImage.load(source_path, focal_length_35mm, model_loader.cfg.img_size)
+        img = SourceImage.load(source_path, focal_length_35mm, model_loader.cfg.img_size, resampler=resampler,
+                               ctx=lambda: model_loader.context(device, dtype))
     except ReconstructionError as err:
         print(err, file=sys.stderr)
         raise
     f_px = img.focal_length_px()
     f_norm = None if f_px is None else float(np.float32(f_px / float(img.original_size[0])))   # :174-176
-    ctx = model_loader.context(device, os.environ.get("MATRIX_EYES_DTYPE", "f16"))   # f16 | bf16 | fp8, as the C++ twin
+    ctx = model_loader.context(device, dtype)
     ctx.set_progress(progress)
     try:
         inverse_depth = ctx.extract_depth(img.rgb8[None], f_norm)[0]
@@ -88,7 +102,8 @@ def extract_depth(device: int, model_loader: DepthProModelLoader, source_path: s
         ctx.set_progress(None)
     depth_map = DepthMap(ctx, inverse_depth, img.original_size)
     try:
-        depth_map.output_image(destination_path, source_path, image_format, vertex_mode, noise=noise)
+        depth_map.output_image(destination_path, source_path, image_format, vertex_mode, noise=noise,
+                               resampler=resampler)
     except Exception as err:
         print(f"Failed to output result: {err}", file=sys.stderr)
         raise
