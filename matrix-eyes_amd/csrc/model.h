@@ -80,7 +80,7 @@ struct ModelW {
     // derived (weights.hip compose_head): head.1 (ConvTranspose 2x2 s2) and head.2 (conv 3x3) as ONE 3x3 convolution on the
     // half-resolution map with 4 x 32 output channels (output phase (dy, dx) x channel), [128][9][Cmid] 16-bit; head_fused_b:
     // f32 [32] bias of interior pixels, then [9][32] the share of each 3x3 tap in it (taken out again where the tap falls
-    // outside the full-resolution image).  Null when the composition does not apply (SPLIT_HEAD).
+    // outside the full-resolution image), then [32] head.4.weight padded with zeros beyond head_dims[0].  Null when the composition does not apply (SPLIT_HEAD).
     const void* head_fused_w = nullptr;
     const float* head_fused_b = nullptr;
     // derived (weights.hip compose_features): fusions[0].out_conv and head.0 as ONE 3x3 convolution of out_conv's input,

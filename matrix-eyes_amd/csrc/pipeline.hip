@@ -218,8 +218,10 @@ void tap_fn(void* user, int index, const float* tokens) {
     TapCtx* t = (TapCtx*)user;
     me_ctx* ctx = t->ctx;
     // encoder.rs:266-280: reshape_feature + merge of the first 25 windows, padding 3 (= g/8)
-    void* dst = index == ctx->cfg.tap_blocks[0] ? t->lat0
-                                                : (index == ctx->cfg.tap_blocks[1] ? t->lat1 : nullptr);
+    // vit.rs:311-316 pushes a tapped block's output when the loop REACHES it (`blocks_to_take.contains(&i)`), so output[0] --
+    // latent0 -- is the earlier of the two blocks whatever the order they are listed in
+    const int t0 = ctx->cfg.tap_blocks[0], t1 = ctx->cfg.tap_blocks[1];
+    void* dst = index == (t0 < t1 ? t0 : t1) ? t->lat0 : (index == (t0 < t1 ? t1 : t0) ? t->lat1 : nullptr);
     if (dst)
         merge_launch(tokens, nullptr, dst, t->B, 35, 0, 5, ctx->g() / 8, ctx->g(), ctx->C(),
                      ctx->dtype, t->s, ctx->split(SPLIT_UPSAMPLE) ? 1 : 0);
@@ -954,7 +956,8 @@ void stage_head(me_ctx* ctx, int B, const float* f_norm_dev, bool clamp, float* 
         p.A = h0b, p.in_Hp = Hh + 2, p.in_Wp = Hh + 2, p.Cin = dec / 2, p.out_H = Hh, p.out_W = Hh;
         p.KH = 3, p.KW = 3, p.stride = 1, p.W = ctx->w.head_fused_w, p.bias = ctx->w.head_fused_b;
         p.tap_bias = ctx->w.head_fused_b + 32;
-        p.w2 = ctx->w.head4_w, p.b2 = ctx->w.head4_b, p.f_norm = f_norm_dev;
+        // head.4.weight as the 32 floats the epilogue reads (compose_head pads the head_dims[0] of the checkpoint with zeros)
+        p.w2 = ctx->w.head_fused_b + 32 + 9 * 32, p.b2 = ctx->w.head4_b, p.f_norm = f_norm_dev;
         p.pixels_per_image = S * S, p.out32 = depth_dev;
         p.clamp_lo = clamp ? 1e-4f : -INFINITY, p.clamp_hi = clamp ? 1e4f : INFINITY;
         head_composed_launch(p, ctx->dtype, s);

@@ -238,11 +238,12 @@ void build_weight_table(me_ctx* ctx) {
             ctx->fused_off[i] = ctx->arena_bytes;
             ctx->arena_bytes = align_up(ctx->arena_bytes + (size_t)(4 * dec) * (3 * dec) * 2, 256);
         }
-    // derived: head.1 o head.2 as one 3x3 convolution with 4 x 32 output channels (compose_head), + its f32 bias tables
+    // derived: head.1 o head.2 as one 3x3 convolution with 4 x 32 output channels (compose_head), + its f32 tables: [32] bias,
+    // [9][32] per-tap bias shares, [32] head.4.weight padded with zeros (the epilogue reads 32 channels whatever head_dims[0] is)
     ctx->head_fused_off = 0;
     if (!ctx->split(SPLIT_HEAD)) {
         ctx->head_fused_off = ctx->arena_bytes;
-        ctx->arena_bytes = align_up(ctx->arena_bytes + (size_t)128 * 9 * (dec / 2) * 2 + (size_t)(32 + 9 * 32) * 4, 256);
+        ctx->arena_bytes = align_up(ctx->arena_bytes + (size_t)128 * 9 * (dec / 2) * 2 + (size_t)(32 + 9 * 32 + 32) * 4, 256);
     }
     // derived: fusions.0.out_conv o head.0 as one 3x3 convolution (compose_features), + its f32 bias tables [dec / 2] + [9][dec / 2]
     ctx->feat_fused_off = 0;
@@ -334,7 +335,8 @@ void load_weight(me_ctx* ctx, const char* name, const void* data, int32_t weight
         keep.resize((size_t)n);
         for (int64_t i = 0; i < n; ++i) keep[i] = src.get(i);
     }
-    if (ctx->head_fused_off && (s.name == "head.1.weight" || s.name == "head.1.bias" || s.name == "head.2.weight" || s.name == "head.2.bias")) {
+    if (ctx->head_fused_off && (s.name == "head.1.weight" || s.name == "head.1.bias" || s.name == "head.2.weight" || s.name == "head.2.bias" ||
+                                s.name == "head.4.weight")) {
         std::vector<float>& keep = ctx->factor_keep[s.name];  // composed at finalize (compose_head)
         keep.resize((size_t)n);
         for (int64_t i = 0; i < n; ++i) keep[i] = src.get(i);
@@ -540,13 +542,15 @@ static void compose_fusion_out(me_ctx* ctx) {
 // ConvTranspose's launch and FLOPs go.  Bias: b'[co] = b3[co] + sum_{ky, kx} Cb[ky][kx][co], Cb = sum_c bT[c] W3[co][c][ky][kx];
 // where tap (ky, kx) of the 3 x 3 convolution falls outside the full-resolution image (its zero padding) the epilogue takes
 // that tap's share out again (X is zero-bordered, so the X part vanishes by itself).  Composed in f64 from the checkpoint's
-// values, rounded once to the operand type; rows of output channels beyond head_dims[0] are zero.
+// values, rounded once to the operand type; rows of output channels beyond head_dims[0] are zero, and so are their entries in
+// the tables -- the 32-float copy of head.4.weight among them: the checkpoint's slot holds head_dims[0] floats only, and the
+// epilogue multiplies all 32 channels (a zero row times whatever lies behind a short slot is NaN when that is not finite).
 static void compose_head(me_ctx* ctx) {
     if (!ctx->head_fused_off) return;
     const int64_t Cm = ctx->cfg.dec_dim / 2, Co = ctx->cfg.head_dims[0];
     const bool to_bf16 = ctx->dtype == ME_DTYPE_BF16;
     auto to16 = [&](float f) { return to_bf16 ? float_to_bf16(f) : float_to_half(f); };
-    const char* names[4] = {"head.1.weight", "head.1.bias", "head.2.weight", "head.2.bias"};
+    const char* names[5] = {"head.1.weight", "head.1.bias", "head.2.weight", "head.2.bias", "head.4.weight"};
     bool any = false;
     for (const char* nm : names) any = any || ctx->factor_keep.count(nm);
     if (!any) return;  // nothing (re)loaded on this context: the arena's own composition (me_weights_adopt / broadcast)
@@ -556,6 +560,7 @@ static void compose_head(me_ctx* ctx) {
     const std::vector<float>& bT = fetch_factor(ctx, "head.1.bias");    // [c]
     const std::vector<float>& W3 = fetch_factor(ctx, "head.2.weight");  // [co][c][ky][kx]
     const std::vector<float>& b3 = fetch_factor(ctx, "head.2.bias");    // [co]
+    const std::vector<float>& w4 = fetch_factor(ctx, "head.4.weight");  // [co]
     std::vector<double> Wp((size_t)128 * 9 * Cm, 0.0);      // [(phase * 32 + co)][tap][ci]
     std::vector<double> w3row((size_t)Cm);
     for (int dy = 0; dy < 2; ++dy)
@@ -579,7 +584,7 @@ static void compose_head(me_ctx* ctx) {
                 }
     std::vector<uint16_t> packed((size_t)128 * 9 * Cm);
     for (size_t i = 0; i < packed.size(); ++i) packed[i] = to16((float)Wp[i]);
-    std::vector<float> tab((size_t)32 + 9 * 32, 0.f);  // [32] interior bias, [9][32] per-tap shares
+    std::vector<float> tab((size_t)32 + 9 * 32 + 32, 0.f);  // [32] interior bias, [9][32] per-tap shares, [32] head.4.weight
     for (int64_t co = 0; co < Co; ++co) {
         double bsum = (double)b3[co];
         for (int t = 0; t < 9; ++t) {
@@ -589,6 +594,7 @@ static void compose_head(me_ctx* ctx) {
             bsum += a;
         }
         tab[co] = (float)bsum;
+        tab[32 + 9 * 32 + co] = w4[co];
     }
     ME_HIP(hipMemcpy(ctx->arena + ctx->head_fused_off, packed.data(), packed.size() * 2, hipMemcpyHostToDevice));
     ME_HIP(hipMemcpy(ctx->arena + ctx->head_fused_off + packed.size() * 2, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));

@@ -38,6 +38,9 @@ class OracleConfig:
     ln_eps: float = 1e-5
     align_corners: bool = True
     dtype: torch.dtype = torch.float32
+    # Sensitivity probe, NOT a model of the HIP path: when set, both operands of every F.linear / F.conv2d /
+    # F.conv_transpose2d are rounded to this type and back before the call; nothing else is rounded
+    operand_dtype: Optional[torch.dtype] = None
 
     @property
     def window(self):
@@ -46,6 +49,29 @@ class OracleConfig:
 
 def _w(weights: Dict[str, torch.Tensor], name: str, cfg: OracleConfig) -> torch.Tensor:
     return weights[name].to(cfg.dtype)
+
+
+def _ops(cfg: OracleConfig, x, w):
+    """The two operands of a linear / convolution call: as they are, or (cfg.operand_dtype) each rounded to that
+    type and back.  With None the very same tensors go through, so the default oracle is unchanged bit for bit."""
+    if cfg.operand_dtype is None:
+        return x, w
+    return x.to(cfg.operand_dtype).to(x.dtype), w.to(cfg.operand_dtype).to(w.dtype)
+
+
+def _linear(cfg, x, w, b=None):
+    x, w = _ops(cfg, x, w)
+    return F.linear(x, w, b)
+
+
+def _conv2d(cfg, x, w, b=None, **kw):
+    x, w = _ops(cfg, x, w)
+    return F.conv2d(x, w, b, **kw)
+
+
+def _conv_transpose2d(cfg, x, w, b=None, **kw):
+    x, w = _ops(cfg, x, w)
+    return F.conv_transpose2d(x, w, b, **kw)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -67,14 +93,14 @@ def attention_forward(xs, weights, p, cfg):
     """vit.rs:58-75 Attention::forward"""
     b, n, c = xs.shape
     h = cfg.num_heads
-    qkv = F.linear(xs, _w(weights, p + "qkv.weight", cfg), _w(weights, p + "qkv.bias", cfg))
+    qkv = _linear(cfg, xs, _w(weights, p + "qkv.weight", cfg), _w(weights, p + "qkv.bias", cfg))
     qkv = qkv.reshape(b, n, 3, h, c // h).permute(2, 0, 3, 1, 4)       # :63-64
     q, k, v = qkv[0], qkv[1], qkv[2]
     scale = 1.0 / math.sqrt(c // h)                                      # :47
     q = q * scale                                                        # :69
     attn = torch.softmax(q @ k.transpose(3, 2), dim=3)                   # :72
     out = (attn @ v).transpose(1, 2).reshape(b, n, c)                    # :73
-    return F.linear(out, _w(weights, p + "proj.weight", cfg), _w(weights, p + "proj.bias", cfg))
+    return _linear(cfg, out, _w(weights, p + "proj.weight", cfg), _w(weights, p + "proj.bias", cfg))
 
 
 def block_forward(xs, weights, p, cfg):
@@ -85,9 +111,9 @@ def block_forward(xs, weights, p, cfg):
     xs = y + residual
     residual = xs
     y = layer_norm(xs, _w(weights, p + "norm2.weight", cfg), _w(weights, p + "norm2.bias", cfg), cfg.ln_eps)
-    y = F.linear(y, _w(weights, p + "mlp.fc1.weight", cfg), _w(weights, p + "mlp.fc1.bias", cfg))
+    y = _linear(cfg, y, _w(weights, p + "mlp.fc1.weight", cfg), _w(weights, p + "mlp.fc1.bias", cfg))
     y = gelu(y)
-    y = F.linear(y, _w(weights, p + "mlp.fc2.weight", cfg), _w(weights, p + "mlp.fc2.bias", cfg))
+    y = _linear(cfg, y, _w(weights, p + "mlp.fc2.weight", cfg), _w(weights, p + "mlp.fc2.bias", cfg))
     y = y * _w(weights, p + "ls2.gamma", cfg)
     return y + residual
 
@@ -97,7 +123,7 @@ def patch_embed_forward(xs, weights, p, cfg):
     _, _, h, w = xs.shape
     if h % 16 or w % 16:   # :213-218
         raise ValueError(f"image {h}x{w} is not a multiple of the patch size 16")
-    y = F.conv2d(xs, _w(weights, p + "proj.weight", cfg), _w(weights, p + "proj.bias", cfg), stride=16)
+    y = _conv2d(cfg, xs, _w(weights, p + "proj.weight", cfg), _w(weights, p + "proj.bias", cfg), stride=16)
     b, c, hh, ww = y.shape
     return y.reshape(b, c, hh * ww).transpose(1, 2)
 
@@ -213,9 +239,9 @@ def reshape_feature(emb, width, height, cls_token_offset):
 def _upsample_block(x, weights, p, n_convt, cfg):
     """encoder.rs:210-216 forward_seq over init_project_upsample_block (:85-118): 1x1 conv (no
     bias) then n ConvTranspose2d(2,2,stride 2, no bias)."""
-    y = F.conv2d(x, _w(weights, p + "0.weight", cfg))
+    y = _conv2d(cfg, x, _w(weights, p + "0.weight", cfg))
     for i in range(n_convt):
-        y = F.conv_transpose2d(y, _w(weights, f"{p}{i + 1}.weight", cfg), stride=2)
+        y = _conv_transpose2d(cfg, y, _w(weights, f"{p}{i + 1}.weight", cfg), stride=2)
     return y
 
 
@@ -246,9 +272,9 @@ def encoder_forward_encodings(x, weights, cfg) -> List[torch.Tensor]:
     x0_feat = _upsample_block(x0_feat, weights, "encoder.upsample0.", 1, cfg)    # :312
     x1_feat = _upsample_block(x1_feat, weights, "encoder.upsample1.", 1, cfg)    # :314
     x2_feat = _upsample_block(x2_feat, weights, "encoder.upsample2.", 1, cfg)    # :316
-    glob = F.conv_transpose2d(glob, _w(weights, "encoder.upsample_lowres.weight", cfg),
+    glob = _conv_transpose2d(cfg, glob, _w(weights, "encoder.upsample_lowres.weight", cfg),
                               _w(weights, "encoder.upsample_lowres.bias", cfg), stride=2)   # :320
-    glob = F.conv2d(torch.cat([x2_feat, glob], dim=1), _w(weights, "encoder.fuse_lowres.weight", cfg),
+    glob = _conv2d(cfg, torch.cat([x2_feat, glob], dim=1), _w(weights, "encoder.fuse_lowres.weight", cfg),
                     _w(weights, "encoder.fuse_lowres.bias", cfg))         # :323-325
     return [lat0, lat1, x0_feat, x1_feat, glob]                           # :328-334
 
@@ -261,7 +287,7 @@ def _rcu(x, weights, p, cfg):
     out = x
     for idx in ("1", "3"):
         out = F.relu(out)
-        out = F.conv2d(out, _w(weights, f"{p}residual.{idx}.weight", cfg),
+        out = _conv2d(cfg, out, _w(weights, f"{p}residual.{idx}.weight", cfg),
                        _w(weights, f"{p}residual.{idx}.bias", cfg), padding=1)
     return x + out
 
@@ -273,21 +299,21 @@ def _fusion(x0, x1, weights, p, has_deconv, cfg):
         out = x0 + _rcu(x1, weights, p + "resnet1.", cfg)
     out = _rcu(out, weights, p + "resnet2.", cfg)
     if has_deconv:
-        out = F.conv_transpose2d(out, _w(weights, p + "deconv.weight", cfg), stride=2)
-    return F.conv2d(out, _w(weights, p + "out_conv.weight", cfg), _w(weights, p + "out_conv.bias", cfg))
+        out = _conv_transpose2d(cfg, out, _w(weights, p + "deconv.weight", cfg), stride=2)
+    return _conv2d(cfg, out, _w(weights, p + "out_conv.weight", cfg), _w(weights, p + "out_conv.bias", cfg))
 
 
 def decoder_forward(encodings: List[torch.Tensor], weights, cfg):
     """decoder.rs:153-208 MultiresConvDecoder::forward -> (features, lowres_features)"""
     if len(encodings) != 5:   # :161-165
         raise ValueError(f"got encoder output levels {len(encodings)}, expected levels 5")
-    feats = F.conv2d(encodings[4], _w(weights, "decoder.convs.4.weight", cfg), padding=1)   # :171-176
+    feats = _conv2d(cfg, encodings[4], _w(weights, "decoder.convs.4.weight", cfg), padding=1)   # :171-176
     lowres = feats.clone()                                                                 # :178
     feats = _fusion(feats, None, weights, "decoder.fusions.4.", True, cfg)                 # :179-183
     for i in (3, 2, 1, 0):                                                                 # :188-205
         enc = encodings[i]
         if i >= 1:
-            enc = F.conv2d(enc, _w(weights, f"decoder.convs.{i}.weight", cfg), padding=1)
+            enc = _conv2d(cfg, enc, _w(weights, f"decoder.convs.{i}.weight", cfg), padding=1)
         feats = _fusion(feats, enc, weights, f"decoder.fusions.{i}.", i != 0, cfg)
     return feats, lowres
 
@@ -297,11 +323,11 @@ def decoder_forward(encodings: List[torch.Tensor], weights, cfg):
 # ---------------------------------------------------------------------------------------------
 def head_forward(features, weights, cfg):
     """mod.rs:323-338 -> canonical inverse depth [B, S, S] (the reference squeezes batch 1)"""
-    y = F.conv2d(features, _w(weights, "head.0.weight", cfg), _w(weights, "head.0.bias", cfg), padding=1)
-    y = F.conv_transpose2d(y, _w(weights, "head.1.weight", cfg), _w(weights, "head.1.bias", cfg), stride=2)
-    y = F.conv2d(y, _w(weights, "head.2.weight", cfg), _w(weights, "head.2.bias", cfg), padding=1)
+    y = _conv2d(cfg, features, _w(weights, "head.0.weight", cfg), _w(weights, "head.0.bias", cfg), padding=1)
+    y = _conv_transpose2d(cfg, y, _w(weights, "head.1.weight", cfg), _w(weights, "head.1.bias", cfg), stride=2)
+    y = _conv2d(cfg, y, _w(weights, "head.2.weight", cfg), _w(weights, "head.2.bias", cfg), padding=1)
     y = F.relu(y)
-    y = F.conv2d(y, _w(weights, "head.4.weight", cfg), _w(weights, "head.4.bias", cfg))
+    y = _conv2d(cfg, y, _w(weights, "head.4.weight", cfg), _w(weights, "head.4.bias", cfg))
     y = F.relu(y)
     return y[:, 0]
 
@@ -311,17 +337,17 @@ def fov_forward(x, lowres_feature, weights, cfg):
     _, _, h, w = x.shape
     x = interpolate_bilinear(x, w // 4, h // 4, cfg.align_corners)                          # :53
     y, _ = vit_forward_features(x, weights, "fov.encoder.0.", cfg, [])                      # :57-61
-    y = F.linear(y, _w(weights, "fov.encoder.1.weight", cfg), _w(weights, "fov.encoder.1.bias", cfg))  # :63
+    y = _linear(cfg, y, _w(weights, "fov.encoder.1.weight", cfg), _w(weights, "fov.encoder.1.bias", cfg))  # :63
     y = y[:, 1:, :].permute(0, 2, 1)                                                        # :66-67
-    low = F.conv2d(lowres_feature, _w(weights, "fov.downsample.0.weight", cfg),
+    low = _conv2d(cfg, lowres_feature, _w(weights, "fov.downsample.0.weight", cfg),
                    _w(weights, "fov.downsample.0.bias", cfg), stride=2, padding=1)          # :70
     low = F.relu(low)                                                                       # :72
     y = y.reshape(low.shape) + low                                                          # :74
-    y = F.relu(F.conv2d(y, _w(weights, "fov.head.0.weight", cfg), _w(weights, "fov.head.0.bias", cfg),
+    y = F.relu(_conv2d(cfg, y, _w(weights, "fov.head.0.weight", cfg), _w(weights, "fov.head.0.bias", cfg),
                         stride=2, padding=1))                                               # :77-79
-    y = F.relu(F.conv2d(y, _w(weights, "fov.head.2.weight", cfg), _w(weights, "fov.head.2.bias", cfg),
+    y = F.relu(_conv2d(cfg, y, _w(weights, "fov.head.2.weight", cfg), _w(weights, "fov.head.2.bias", cfg),
                         stride=2, padding=1))                                               # :81-83
-    y = F.conv2d(y, _w(weights, "fov.head.4.weight", cfg), _w(weights, "fov.head.4.bias", cfg))   # :85
+    y = _conv2d(cfg, y, _w(weights, "fov.head.4.weight", cfg), _w(weights, "fov.head.4.bias", cfg))   # :85
     return y.reshape(-1)                                                                    # :87
 
 

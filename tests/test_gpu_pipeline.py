@@ -626,7 +626,9 @@ sys.path.insert(0, sys.argv[1])
 import matrix_eyes_amd as m
 from matrix_eyes_amd.synthetic import synthetic_checkpoint, synthetic_images
 cfg = m.ModelConfig.tiny()
-w = dict(synthetic_checkpoint(cfg))
+if len(sys.argv) > 3:
+    cfg.head_dims = (int(sys.argv[3]), 1)
+w = dict(synthetic_checkpoint(cfg, seed=int(sys.argv[4]) if len(sys.argv) > 4 else 2024))
 # a ConvTranspose bias large enough that a wrong border term would show: the composed form takes the share of every 3x3 tap
 # that falls into the zero padding of the full-resolution map out of its bias
 import torch
@@ -648,6 +650,19 @@ def test_composed_head_equals_the_three_layers(tmp_path):
     bias: the maps agree to the 16-bit rounding the composed form SKIPS (the ConvTranspose output is no longer rounded to an
     operand), on the one-pixel frame -- where taps of the 3x3 convolution fall into its zero padding and the composed bias
     changes -- as well as inside.  (test_extract_depth_tiny / the full-size pairs hold the composed form to the fp32 oracle.)"""
+    _composed_head_against_the_three_layers(tmp_path, [])
+
+
+def test_composed_head_equals_the_three_layers_head_dim_16(tmp_path):
+    """The same with head_dims[0] = 16: the composed form stays on for a head narrower than the 32 channels its epilogue multiplies
+    (rows 16..31 of the composed weights, of both bias tables and of its copy of head.4.weight are zero: weights.hip compose_head).
+    Checkpoint seed 7, chosen from the fp32 oracle alone: with seed 2024 and 16 channels the closing ReLU zeroes 64 % of this map
+    (19 % in the 32-channel test above), which inflates every relative figure -- the oracle against itself with f16 operands
+    (OracleConfig.operand_dtype) moves by 1.26e-3 there, by 7.5e-4 in the test above and by 6.5e-4 with seed 7 (9 % zeroed)."""
+    _composed_head_against_the_three_layers(tmp_path, ["16", "7"])
+
+
+def _composed_head_against_the_three_layers(tmp_path, child_args):
     import os
     import subprocess
     import sys
@@ -655,7 +670,7 @@ def test_composed_head_equals_the_three_layers(tmp_path):
     outs = {}
     for name, extra in (("composed", {}), ("layers", {"ME_HEAD_COMPOSED": "0"})):
         path = str(tmp_path / (name + ".npy"))
-        r = subprocess.run([sys.executable, "-c", _HEAD_CHILD, root, path], env=dict(os.environ, **extra),
+        r = subprocess.run([sys.executable, "-c", _HEAD_CHILD, root, path] + child_args, env=dict(os.environ, **extra),
                            capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         outs[name] = np.load(path)
