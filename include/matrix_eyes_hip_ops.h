@@ -61,6 +61,71 @@ int32_t me_op_head_final(me_ctx* ctx, const void* in16b, int32_t B, int32_t H, i
 int32_t me_op_conv_transpose2x2(me_ctx* ctx, const void* in16, int32_t B, int32_t H, int32_t W,
                                 int32_t Cin, const void* w16, int32_t Cout, const float* bias,
                                 float* out32, void* out16, int32_t border16, int32_t tile_cfg);
+/* The 16-bit output forms of the split-operand stages (model.h SplitStage; pipeline.hip conv / linear / convt), which
+   me_op_conv2d, me_op_linear and me_op_conv_transpose2x2 cannot ask for.  A split value is the pair hi = T(v),
+   lo = T(v - hi) (0 where hi overflowed).  The INPUT side of a split stage needs no entry point: the kernel only sees K
+   (or Cin) doubled or tripled against weights stored with every run of K (or Cin) values followed by a copy of itself
+   (weights.hip), and the caller builds those operands.
+   me_op_conv2d_forms: me_op_conv2d with out16_parts = 1: out16 pixels of Cout (plain), 2: [hi | lo] of 2 Cout,
+   3: [hi | lo | hi] of 3 Cout; each zero-bordered when border16.  Cin is the operand's channel count as stored.
+   me_op_linear_split: me_op_linear with out16 rows of [hi | lo], 2 N wide.
+   me_op_conv_transpose2x2_forms: me_op_conv_transpose2x2 with act16 on the 16-bit copy, out16 pixels pixel_stride
+   channels apart (0: Cout, or 2 Cout when out_split: a channel slice of a wider map otherwise) and, when out_split,
+   the lo part lo_off channels behind the hi part (0: Cout).  Cin is the operand row's length as stored. */
+int32_t me_op_conv2d_forms(me_ctx* ctx, const void* in16b, int32_t B, int32_t H, int32_t W, int32_t Cin,
+                           const void* w16, int32_t Cout, int32_t k, int32_t stride, const float* bias,
+                           const float* res32, const float* res32b, float* out32, void* out16,
+                           int32_t border16, int32_t out16_parts, int32_t act, int32_t act_both, int32_t tile_cfg);
+int32_t me_op_linear_split(me_ctx* ctx, int32_t M, int32_t N, int32_t K, const void* A16, const void* W16,
+                           const float* bias, void* out16, float* out32, int32_t act, int32_t tile_cfg);
+int32_t me_op_conv_transpose2x2_forms(me_ctx* ctx, const void* in16, int32_t B, int32_t H, int32_t W,
+                                      int32_t Cin, const void* w16, int32_t Cout, const float* bias,
+                                      float* out32, void* out16, int32_t border16, int32_t act16,
+                                      int32_t out_split, int32_t pixel_stride, int32_t lo_off, int32_t tile_cfg);
+/* Patch embed + pos (vit.rs:287-295; gemm_core.h EPI_PATCH_EMBED): patches16 [windows * P][768] . W16 [C][768]^T + bias
+   + pos[1 + p] -> rows 1 .. P of each window of tokens32 [windows][P + 1][C]; the cls rows are not written
+   (me_op_cls_rows writes them). */
+int32_t me_op_patch_embed(me_ctx* ctx, const void* patches16, int32_t windows, int32_t P, int32_t C, const void* W16,
+                          const float* bias, const float* pos, float* tokens32, int32_t tile_cfg);
+/* The layout and element-wise kernels between the GEMMs (csrc/elementwise.hip), one entry point each; arguments as the
+   forward pass gives them (pipeline.hip).  grid: a multiple of 8 up to 64 (what me_ctx_create admits).
+   me_op_bilinear: src32 [planes][in][in] -> dst16 [planes][out][out] (encoder.rs:125-140).
+   me_op_patchify: the 25 + 9 + 1 windows of x0 [B][3][64 g]^2, x1 [B][3][32 g]^2, x2 [B][3][16 g]^2 (16-bit) as im2col
+   rows patches [(b * 35 + win) * g * g + py * g + px][c * 256 + iy * 16 + ix]; me_op_patchify_windows: the same for a
+   stack of whole windows xs16 [windows][3][16 g]^2.
+   me_op_cls_rows: tokens [windows][tpw][dim] row 0 = cls + pos[0 .. dim).
+   me_op_merge: reshape_feature + merge (encoder.rs:158-208) as one row gather from tokens [batch * wpi][g * g + 1][dim]
+   (ONE of src32 / src16) of windows win0 .. win0 + steps^2 - 1 of each image -> dst16 NHWC [batch][side][side][dim],
+   side = g (steps 1) or 2 (g - padding) + (steps - 2)(g - 2 padding); split (src32 only): pixels of [hi | lo], 2 dim.
+   me_op_nchw32_to_nhwc: src [B][C][H][W] f32 -> dst32 [B][H][W][C] and/or dst16 (zero-bordered [B][H+2][W+2] when
+   border; ReLU when relu16; pixels of [hi | lo] when split).  me_op_nhwc16_to_nchw32 / me_op_nhwc32_to_nchw32: back
+   (split: value = hi + lo).  me_op_nhwc32_to_16b: f32 NHWC -> the interior of a bordered 16-bit map, C % 4 == 0.
+   me_op_concat_channels: a [pixels][Ca] and b [pixels][Cb] (16-bit, multiples of 8) -> dst [pixels][Ca + Cb].
+   me_op_fov_add: dst16b [B][g+2][g+2][C] interior = T(lin[b][1 + p][c] + low[b][p][c]) (fov.rs:66-74), lin [B][tpw][C].
+   me_op_fov_final: fov_deg[b] (may be NULL) = x16[b][0 .. k*k*C) . w + bias[0], f_norm[b] = tan(fov_deg/2 in rad)/0.5. */
+int32_t me_op_bilinear(me_ctx* ctx, const float* src32, void* dst16, int32_t planes, int32_t in_size, int32_t out_size,
+                       int32_t align_corners);
+int32_t me_op_patchify(me_ctx* ctx, const void* x0, const void* x1, const void* x2, void* patches, int32_t batch,
+                       int32_t grid);
+int32_t me_op_patchify_windows(me_ctx* ctx, const void* xs16, void* patches, int32_t windows, int32_t grid);
+int32_t me_op_cls_rows(me_ctx* ctx, float* tokens, const float* cls, const float* pos, int32_t windows, int32_t tpw,
+                       int32_t dim);
+int32_t me_op_merge(me_ctx* ctx, const float* src32, const void* src16, void* dst16, int32_t batch, int32_t wpi,
+                    int32_t win0, int32_t steps, int32_t padding, int32_t grid, int32_t dim, int32_t split);
+int32_t me_op_nchw32_to_nhwc(me_ctx* ctx, const float* src, float* dst32, void* dst16, int32_t batch, int32_t H,
+                             int32_t W, int32_t C, int32_t border, int32_t relu16, int32_t split);
+int32_t me_op_nhwc16_to_nchw32(me_ctx* ctx, const void* src16, float* dst, int32_t batch, int32_t H, int32_t W,
+                               int32_t C, int32_t border, int32_t split);
+int32_t me_op_nhwc32_to_nchw32(me_ctx* ctx, const float* src, float* dst, int32_t batch, int32_t H, int32_t W,
+                               int32_t C);
+int32_t me_op_nhwc32_to_16b(me_ctx* ctx, const float* src, void* dst16b, int32_t batch, int32_t H, int32_t W,
+                            int32_t C, int32_t relu);
+int32_t me_op_concat_channels(me_ctx* ctx, const void* a16, const void* b16, void* dst16, int64_t pixels, int32_t Ca,
+                              int32_t Cb);
+int32_t me_op_fov_add(me_ctx* ctx, const float* lin, const float* low, void* dst16b, int32_t batch, int32_t grid,
+                      int32_t C, int32_t tpw);
+int32_t me_op_fov_final(me_ctx* ctx, const void* x16, const float* w, const float* bias, float* fov_deg, float* f_norm,
+                        int32_t batch, int32_t k, int32_t C);
 /* MX block-scaled fp8 (ME_DTYPE_FP8, BASELINE configs[3]; csrc/gemm_fp8.hip, mx_fp8.h).
    me_op_quantize_fp8: f16 [rows][K] -> e4m3 bytes dst8 [rows][K] + one e8m0 scale per 32 K elements into
    `scales`, in the weight operand's layout (weight_layout = 1: rows a multiple of 64, rows*K/32 bytes) or the

@@ -99,6 +99,24 @@ SIGNATURES = {
     "me_op_head_final": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _i32]),
     "me_op_conv_transpose2x2": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp,
                                        _i32, _i32]),
+    "me_op_conv2d_forms": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp,
+                                  _vp, _vp, _i32, _i32, _i32, _i32, _i32]),
+    "me_op_linear_split": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32]),
+    "me_op_conv_transpose2x2_forms": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp,
+                                             _i32, _i32, _i32, _i32, _i32, _i32]),
+    "me_op_patch_embed": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32]),
+    "me_op_bilinear": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32]),
+    "me_op_patchify": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32]),
+    "me_op_patchify_windows": (_i32, [_vp, _vp, _vp, _i32, _i32]),
+    "me_op_cls_rows": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32]),
+    "me_op_merge": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "me_op_nchw32_to_nhwc": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "me_op_nhwc16_to_nchw32": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "me_op_nhwc32_to_nchw32": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32]),
+    "me_op_nhwc32_to_16b": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32]),
+    "me_op_concat_channels": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32]),
+    "me_op_fov_add": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32]),
+    "me_op_fov_final": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32]),
     "me_op_quantize_fp8": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "me_op_attention_fp8": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32]),
     "me_op_scale_index": (_i64, [_i64, _i32, _i64, _i32]),

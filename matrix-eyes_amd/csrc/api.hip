@@ -1182,6 +1182,220 @@ int32_t me_op_conv_transpose2x2(me_ctx* ctx, const void* in16, int32_t B, int32_
     ME_API_END(ctx)
 }
 
+// ---- the split-operand output forms, GemmParams filled as pipeline.hip's conv / linear / convt helpers fill them ----
+int32_t me_op_conv2d_forms(me_ctx* ctx, const void* in16b, int32_t B, int32_t H, int32_t W, int32_t Cin,
+                           const void* w16, int32_t Cout, int32_t k, int32_t stride, const float* bias,
+                           const float* res32, const float* res32b, float* out32, void* out16,
+                           int32_t border16, int32_t out16_parts, int32_t act, int32_t act_both, int32_t tile_cfg) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(in16b && w16 && (out32 || out16), ME_ERR_BAD_ARG, "me_op_conv2d_forms: null pointer");
+    ME_CHECK((k == 1 || k == 3) && (stride == 1 || stride == 2) && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 &&
+                 H % stride == 0 && W % stride == 0,
+             ME_ERR_BAD_SHAPE, "me_op_conv2d_forms: %d x %d x %d, %d -> %d, k=%d stride=%d", B, H, W, Cin, Cout, k, stride);
+    ME_CHECK(out16_parts >= 1 && out16_parts <= 3 && (out16_parts == 1 || out16), ME_ERR_BAD_ARG,
+             "me_op_conv2d_forms: out16_parts=%d", out16_parts);
+    ME_CHECK(act == ME_ACT_NONE || act == ME_ACT_RELU, ME_ERR_BAD_ARG, "me_op_conv2d_forms: act=%d", act);
+    GemmParams p = GemmParams();
+    p.clamp_lo = -INFINITY, p.clamp_hi = INFINITY;
+    const int Ho = H / stride, Wo = W / stride;
+    p.M = B * Ho * Wo, p.N = Cout, p.K = k * k * Cin, p.A = in16b;
+    p.in_Hp = H + 2, p.in_Wp = W + 2, p.Cin = Cin, p.out_H = Ho, p.out_W = Wo;
+    p.KH = k, p.KW = k, p.stride = stride, p.W = w16, p.bias = bias;
+    p.res32 = res32, p.res32b = res32b, p.out32 = out32, p.out16 = out16, p.ldc = Cout;
+    p.out16_border = border16 ? 1 : 0, p.act = act, p.act16_only = act_both ? 0 : 1;
+    if (out16_parts >= 2) p.ldc16 = 2 * (int64_t)Cout, p.lo_off16 = Cout;          // pipeline.hip set_out16_split
+    if (out16_parts == 3) p.ldc16 = 3 * (int64_t)Cout, p.hi2_off16 = 2 * Cout;     // ... ConvOut::triple16
+    gemm_launch(p, A_CONV, EPI_STORE, ctx->dtype, ctx->stream, tile_cfg);
+    ME_API_END(ctx)
+}
+
+int32_t me_op_linear_split(me_ctx* ctx, int32_t M, int32_t N, int32_t K, const void* A16, const void* W16,
+                           const float* bias, void* out16, float* out32, int32_t act, int32_t tile_cfg) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(A16 && W16 && out16, ME_ERR_BAD_ARG, "me_op_linear_split: null pointer");
+    GemmParams p = GemmParams();
+    p.clamp_lo = -INFINITY, p.clamp_hi = INFINITY;
+    p.M = M, p.N = N, p.K = K, p.A = A16, p.lda = K, p.W = W16, p.bias = bias;
+    p.out16 = out16, p.out32 = out32, p.ldc = N, p.act = act;
+    p.ldc16 = 2 * (int64_t)N, p.lo_off16 = N;
+    gemm_launch(p, A_PLAIN, EPI_STORE, ctx->dtype, ctx->stream, tile_cfg);
+    ME_API_END(ctx)
+}
+
+int32_t me_op_conv_transpose2x2_forms(me_ctx* ctx, const void* in16, int32_t B, int32_t H, int32_t W,
+                                      int32_t Cin, const void* w16, int32_t Cout, const float* bias,
+                                      float* out32, void* out16, int32_t border16, int32_t act16,
+                                      int32_t out_split, int32_t pixel_stride, int32_t lo_off, int32_t tile_cfg) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(in16 && w16 && (out32 || out16), ME_ERR_BAD_ARG, "me_op_conv_transpose2x2_forms: null pointer");
+    ME_CHECK(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cout % 8 == 0, ME_ERR_BAD_SHAPE,
+             "me_op_conv_transpose2x2_forms: %d x %d x %d, %d -> %d", B, H, W, Cin, Cout);
+    ME_CHECK(act16 == ME_ACT_NONE || act16 == ME_ACT_RELU, ME_ERR_BAD_ARG, "me_op_conv_transpose2x2_forms: act16=%d", act16);
+    ME_CHECK((!out_split && !pixel_stride && !lo_off) || out16, ME_ERR_BAD_ARG,
+             "me_op_conv_transpose2x2_forms: a 16-bit layout without a 16-bit output");
+    ME_CHECK(out_split || !lo_off, ME_ERR_BAD_ARG, "me_op_conv_transpose2x2_forms: lo_off without out_split");
+    const int lo = out_split ? (lo_off ? lo_off : Cout) : 0;
+    ME_CHECK(pixel_stride >= 0 && pixel_stride % 8 == 0 && lo % 8 == 0 && (!out_split || lo >= Cout) &&
+                 (!pixel_stride || pixel_stride >= lo + Cout),
+             ME_ERR_BAD_SHAPE, "me_op_conv_transpose2x2_forms: pixel_stride=%d lo_off=%d for %d channels", pixel_stride, lo_off, Cout);
+    GemmParams p = GemmParams();
+    p.clamp_lo = -INFINITY, p.clamp_hi = INFINITY;
+    p.M = B * H * W, p.N = 4 * Cout, p.K = Cin, p.A = in16, p.lda = Cin, p.W = w16, p.bias = bias;
+    p.out_H = H, p.out_W = W, p.Cout = Cout, p.out32 = out32, p.out16 = out16;
+    p.out16_border = border16 ? 1 : 0, p.ldc = Cout, p.act = act16;
+    if (out_split) {
+        p.lo_off16 = lo;
+        p.ldc16 = pixel_stride ? pixel_stride : 2 * Cout;
+    } else if (pixel_stride) {
+        p.ldc16 = pixel_stride;
+    }
+    gemm_launch(p, A_PLAIN, EPI_CONVT, ctx->dtype, ctx->stream, tile_cfg);
+    ME_API_END(ctx)
+}
+
+int32_t me_op_patch_embed(me_ctx* ctx, const void* patches16, int32_t windows, int32_t P, int32_t C, const void* W16,
+                          const float* bias, const float* pos, float* tokens32, int32_t tile_cfg) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(patches16 && W16 && bias && pos && tokens32, ME_ERR_BAD_ARG, "me_op_patch_embed: null pointer");
+    ME_CHECK(windows > 0 && P > 0 && C > 0 && (int64_t)windows * P < (1 << 30), ME_ERR_BAD_SHAPE,
+             "me_op_patch_embed: %d windows of %d patches, dim %d", windows, P, C);
+    GemmParams p = GemmParams();
+    p.clamp_lo = -INFINITY, p.clamp_hi = INFINITY;
+    p.M = windows * P, p.N = C, p.K = 768, p.A = patches16, p.lda = 768, p.W = W16;
+    p.bias = bias, p.pos = pos, p.out32 = tokens32, p.ldc = C, p.tokens_per_window = P;
+    gemm_launch(p, A_PLAIN, EPI_PATCH_EMBED, ctx->dtype, ctx->stream, tile_cfg);
+    ME_API_END(ctx)
+}
+
+// ---- the layout / element-wise kernels (elementwise.hip), arguments checked here: the launch helpers trust the pipeline ----
+namespace {
+void check_grid(const char* who, int32_t grid) {
+    ME_CHECK(grid >= 8 && grid <= 64 && grid % 8 == 0, ME_ERR_BAD_SHAPE, "%s: grid %d is not a multiple of 8 in [8, 64]", who, grid);
+}
+void check_map(const char* who, int32_t batch, int32_t H, int32_t W, int32_t C) {
+    ME_CHECK(batch > 0 && batch <= 65535 && H > 0 && W > 0 && C > 0 && (int64_t)H * W < (1ll << 31) && (int64_t)C <= 65535 * 32ll,
+             ME_ERR_BAD_SHAPE, "%s: %d x %d x %d x %d", who, batch, H, W, C);
+}
+}  // namespace
+
+int32_t me_op_bilinear(me_ctx* ctx, const float* src32, void* dst16, int32_t planes, int32_t in_size, int32_t out_size,
+                       int32_t align_corners) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(src32 && dst16, ME_ERR_BAD_ARG, "me_op_bilinear: null pointer");
+    ME_CHECK(planes > 0 && in_size > 0 && out_size > 0 && in_size <= 32768 && out_size <= 32768, ME_ERR_BAD_SHAPE,
+             "me_op_bilinear: %d planes, %d -> %d", planes, in_size, out_size);
+    bilinear_launch(src32, dst16, planes, in_size, out_size, align_corners ? 1 : 0, ctx->dtype, ctx->stream);
+    ME_API_END(ctx)
+}
+
+int32_t me_op_patchify(me_ctx* ctx, const void* x0, const void* x1, const void* x2, void* patches, int32_t batch,
+                       int32_t grid) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(x0 && x1 && x2 && patches, ME_ERR_BAD_ARG, "me_op_patchify: null pointer");
+    check_grid("me_op_patchify", grid);
+    ME_CHECK(batch > 0 && batch <= 1024, ME_ERR_BAD_SHAPE, "me_op_patchify: batch %d", batch);
+    patchify_launch(x0, x1, x2, patches, batch, grid, ctx->dtype, ctx->stream);
+    ME_API_END(ctx)
+}
+
+int32_t me_op_patchify_windows(me_ctx* ctx, const void* xs16, void* patches, int32_t windows, int32_t grid) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(xs16 && patches, ME_ERR_BAD_ARG, "me_op_patchify_windows: null pointer");
+    check_grid("me_op_patchify_windows", grid);
+    ME_CHECK(windows > 0 && windows <= 35 * 1024, ME_ERR_BAD_SHAPE, "me_op_patchify_windows: %d windows", windows);
+    patchify_windows_launch(xs16, patches, windows, grid, ctx->dtype, ctx->stream);
+    ME_API_END(ctx)
+}
+
+int32_t me_op_cls_rows(me_ctx* ctx, float* tokens, const float* cls, const float* pos, int32_t windows, int32_t tpw,
+                       int32_t dim) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(tokens && cls && pos, ME_ERR_BAD_ARG, "me_op_cls_rows: null pointer");
+    ME_CHECK(windows > 0 && tpw > 0 && dim > 0, ME_ERR_BAD_SHAPE, "me_op_cls_rows: %d windows of %d tokens, dim %d", windows, tpw, dim);
+    cls_rows_launch(tokens, cls, pos, windows, tpw, dim, ctx->stream);
+    ME_API_END(ctx)
+}
+
+int32_t me_op_merge(me_ctx* ctx, const float* src32, const void* src16, void* dst16, int32_t batch, int32_t wpi,
+                    int32_t win0, int32_t steps, int32_t padding, int32_t grid, int32_t dim, int32_t split) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(dst16, ME_ERR_BAD_ARG, "me_op_merge: null pointer");
+    check_grid("me_op_merge", grid);
+    ME_CHECK(batch > 0 && dim > 0 && steps >= 1 && steps <= 5 && padding >= 0 && 2 * padding < grid && (steps > 1 || padding == 0) &&
+                 win0 >= 0 && wpi > 0 && win0 + steps * steps <= wpi,
+             ME_ERR_BAD_SHAPE, "me_op_merge: batch %d, windows %d + %d x %d of %d, padding %d, dim %d", batch, win0, steps, steps, wpi,
+             padding, dim);
+    merge_launch(src32, src16, dst16, batch, wpi, win0, steps, padding, grid, dim, ctx->dtype, ctx->stream, split ? 1 : 0);
+    ME_API_END(ctx)
+}
+
+int32_t me_op_nchw32_to_nhwc(me_ctx* ctx, const float* src, float* dst32, void* dst16, int32_t batch, int32_t H,
+                             int32_t W, int32_t C, int32_t border, int32_t relu16, int32_t split) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(src && (dst32 || dst16) && (dst16 || (!border && !relu16 && !split)), ME_ERR_BAD_ARG, "me_op_nchw32_to_nhwc: null pointer");
+    check_map("me_op_nchw32_to_nhwc", batch, H, W, C);
+    nchw32_to_nhwc_launch(src, dst32, dst16, batch, H, W, C, border ? 1 : 0, relu16 ? 1 : 0, ctx->dtype, ctx->stream, split ? 1 : 0);
+    ME_API_END(ctx)
+}
+
+int32_t me_op_nhwc16_to_nchw32(me_ctx* ctx, const void* src16, float* dst, int32_t batch, int32_t H, int32_t W,
+                               int32_t C, int32_t border, int32_t split) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(src16 && dst, ME_ERR_BAD_ARG, "me_op_nhwc16_to_nchw32: null pointer");
+    check_map("me_op_nhwc16_to_nchw32", batch, H, W, C);
+    nhwc16_to_nchw32_launch(src16, dst, batch, H, W, C, border ? 1 : 0, ctx->dtype, ctx->stream, split ? 1 : 0);
+    ME_API_END(ctx)
+}
+
+int32_t me_op_nhwc32_to_nchw32(me_ctx* ctx, const float* src, float* dst, int32_t batch, int32_t H, int32_t W,
+                               int32_t C) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(src && dst, ME_ERR_BAD_ARG, "me_op_nhwc32_to_nchw32: null pointer");
+    check_map("me_op_nhwc32_to_nchw32", batch, H, W, C);
+    nhwc32_to_nchw32_launch(src, dst, batch, H, W, C, ctx->stream);
+    ME_API_END(ctx)
+}
+
+int32_t me_op_nhwc32_to_16b(me_ctx* ctx, const float* src, void* dst16b, int32_t batch, int32_t H, int32_t W,
+                            int32_t C, int32_t relu) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(src && dst16b, ME_ERR_BAD_ARG, "me_op_nhwc32_to_16b: null pointer");
+    check_map("me_op_nhwc32_to_16b", batch, H, W, C);
+    nhwc32_to_16b_launch(src, dst16b, batch, H, W, C, relu ? 1 : 0, ctx->dtype, ctx->stream);
+    ME_API_END(ctx)
+}
+
+int32_t me_op_concat_channels(me_ctx* ctx, const void* a16, const void* b16, void* dst16, int64_t pixels, int32_t Ca,
+                              int32_t Cb) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(a16 && b16 && dst16, ME_ERR_BAD_ARG, "me_op_concat_channels: null pointer");
+    ME_CHECK(pixels > 0 && Ca > 0 && Cb > 0, ME_ERR_BAD_SHAPE, "me_op_concat_channels: %lld pixels of %d + %d channels",
+             (long long)pixels, Ca, Cb);
+    concat_channels_launch(a16, b16, dst16, pixels, Ca, Cb, ctx->stream);
+    ME_API_END(ctx)
+}
+
+int32_t me_op_fov_add(me_ctx* ctx, const float* lin, const float* low, void* dst16b, int32_t batch, int32_t grid,
+                      int32_t C, int32_t tpw) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(lin && low && dst16b, ME_ERR_BAD_ARG, "me_op_fov_add: null pointer");
+    check_grid("me_op_fov_add", grid);
+    ME_CHECK(batch > 0 && C > 0 && tpw >= grid * grid + 1, ME_ERR_BAD_SHAPE, "me_op_fov_add: batch %d, %d channels, %d tokens per window",
+             batch, C, tpw);
+    fov_add_relu_launch(lin, low, dst16b, batch, grid, C, tpw, ctx->dtype, ctx->stream);
+    ME_API_END(ctx)
+}
+
+int32_t me_op_fov_final(me_ctx* ctx, const void* x16, const float* w, const float* bias, float* fov_deg, float* f_norm,
+                        int32_t batch, int32_t k, int32_t C) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(x16 && w && bias && f_norm, ME_ERR_BAD_ARG, "me_op_fov_final: null pointer");
+    ME_CHECK(batch > 0 && k > 0 && C > 0 && (int64_t)k * k * C < (1ll << 31), ME_ERR_BAD_SHAPE, "me_op_fov_final: batch %d, %d x %d x %d",
+             batch, k, k, C);
+    fov_final_launch(x16, w, bias, fov_deg, f_norm, batch, k, C, ctx->dtype, ctx->stream);
+    ME_API_END(ctx)
+}
+
 int32_t me_op_quantize_fp8(me_ctx* ctx, const void* src16, int64_t rows, int32_t K, int32_t weight_layout,
                            uint8_t* dst8, uint8_t* scales) {
     ME_API_BEGIN(ctx)

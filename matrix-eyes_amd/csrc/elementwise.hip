@@ -174,7 +174,8 @@ __global__ void cast_to32_kernel(const T* __restrict__ src, float* __restrict__ 
 // ---------------------------------------------------------------------------------------
 template <typename T>
 __global__ void bilinear_kernel(const float* __restrict__ src, T* __restrict__ dst, int planes,
-                                int in_size, int out_size, int align_corners) {
+                                int in_size, int out_size, int align_corners, unsigned* __restrict__ status) {
+    float amax16 = 0.f;  // overflow guard of the 16-bit copy (common.h)
     const int64_t total = (int64_t)planes * out_size * out_size;
     const float ratio = align_corners
                             ? (float)((double)(in_size - 1) / (double)(out_size > 1 ? out_size - 1 : 1))
@@ -205,7 +206,9 @@ __global__ void bilinear_kernel(const float* __restrict__ src, T* __restrict__ d
         const float v = a * (1.f - wx) * (1.f - wy) + b * wx * (1.f - wy) + c * (1.f - wx) * wy +
                         d * wx * wy;
         dst[i] = (T)v;
+        amax16 = fmaxf(amax16, fabsf(v));
     }
+    raise_overflow16<T>(status, amax16);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -474,7 +477,9 @@ __global__ void concat_channels_kernel(const uint4* __restrict__ a, const uint4*
 // `low` already holds the relu'd conv output, NHWC f32 [B][g*g][C].
 template <typename T>
 __global__ void fov_add_kernel(const float* __restrict__ lin, const float* __restrict__ low,
-                               T* __restrict__ dst16, int batch, int grid, int C, int tpw) {
+                               T* __restrict__ dst16, int batch, int grid, int C, int tpw,
+                               unsigned* __restrict__ status) {
+    float amax16 = 0.f;  // both addends are f32 nothing has rounded yet: the sum may leave the f16 range
     const int P = grid * grid;
     const int64_t total = (int64_t)batch * P * C;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
@@ -485,7 +490,9 @@ __global__ void fov_add_kernel(const float* __restrict__ lin, const float* __res
         const float v = lin[((int64_t)b * tpw + 1 + p) * C + c] + low[i];
         const int y = p / grid, x = p - y * grid;
         dst16[(((int64_t)b * (grid + 2) + y + 1) * (grid + 2) + x + 1) * C + c] = (T)v;
+        amax16 = fmaxf(amax16, fabsf(v));
     }
+    raise_overflow16<T>(status, amax16);
 }
 
 // fov.rs:85 head[2] (k x k valid conv to one value) + mod.rs:358 f_norm.  One workgroup per image.
@@ -577,10 +584,11 @@ void bilinear_launch(const float* src32, void* dst16, int32_t planes, int32_t in
     const int64_t total = (int64_t)planes * out_size * out_size;
     ME_BY_DTYPE(dtype,
                 hipLaunchKernelGGL(bilinear_kernel<f16>, dim3(grid_for(total)), dim3(256), 0, stream,
-                                   src32, (f16*)dst16, planes, in_size, out_size, align_corners),
+                                   src32, (f16*)dst16, planes, in_size, out_size, align_corners,
+                                   current_status_word()),
                 hipLaunchKernelGGL(bilinear_kernel<bf16>, dim3(grid_for(total)), dim3(256), 0,
                                    stream, src32, (bf16*)dst16, planes, in_size, out_size,
-                                   align_corners));
+                                   align_corners, current_status_word()));
 }
 
 void patchify_launch(const void* x0, const void* x1, const void* x2, void* patches, int32_t batch,
@@ -680,9 +688,11 @@ void fov_add_relu_launch(const float* lin, const float* low, void* dst16, int32_
     const int64_t total = (int64_t)batch * grid * grid * C;
     ME_BY_DTYPE(dtype,
                 hipLaunchKernelGGL(fov_add_kernel<f16>, dim3(grid_for(total)), dim3(256), 0, stream,
-                                   lin, low, (f16*)dst16, batch, grid, C, tokens_per_window),
+                                   lin, low, (f16*)dst16, batch, grid, C, tokens_per_window,
+                                   current_status_word()),
                 hipLaunchKernelGGL(fov_add_kernel<bf16>, dim3(grid_for(total)), dim3(256), 0, stream,
-                                   lin, low, (bf16*)dst16, batch, grid, C, tokens_per_window));
+                                   lin, low, (bf16*)dst16, batch, grid, C, tokens_per_window,
+                                   current_status_word()));
 }
 
 void fov_final_launch(const void* x16, const float* w, const float* bias, float* fov_deg,

@@ -677,8 +677,9 @@ def test_conv2d(dtype, case, cfg):
 def test_conv3x3_halo_tile(dtype, case):
     """Tile config 9 (gemm_core.h conv_halo_kernel): 16 x 16 pixel tiles whose 18 x 18 halo is staged once per 64 input
     channels and read at shifted rows by the nine taps -- against torch.nn.functional.conv2d on the same 16-bit operands,
-    with the f32 residual inputs, the fused ReLU, the zero-bordered 16-bit output and the split [hi | lo] output form;
-    maps larger than one round of tiles; the zero border stays zero.  The automatic choice picks it for such shapes."""
+    with the f32 residual inputs, the fused ReLU and the zero-bordered 16-bit output; maps larger than one round of
+    tiles; the zero border stays zero.  The automatic choice picks it for such shapes.  (The split [hi | lo] and
+    [hi | lo | hi] output forms on these tiles: test_gpu_split_forms.py test_halo_tiles_with_doubled_cin.)"""
     ctx = ctx_for("tiny", dtype)
     B, H, W, Cin, Cout = (case[n] for n in ("B", "H", "W", "Cin", "Cout"))
     g = torch.Generator().manual_seed(H * W + Cin + Cout)
