@@ -305,6 +305,30 @@ int32_t me_depthmap_rgb_resized(me_ctx* ctx, const float* depth, int32_t data_wi
                                 float min_depth, float max_depth, const float* minmax_dev,
                                 int32_t out_w, int32_t out_h, uint8_t* rgb);
 
+/* ---- PNG encoding on the device (RgbImage::save to ".png") ---------------------------------------------------------- */
+
+/* RgbImage::save to ".png" (output.rs:138, :192): rgb [h,w,3] -> a complete PNG file (colour type 2, bit depth 8, no
+   interlace; adaptive row filters, one dynamic-Huffman or stored deflate chunk per 64 KiB of filtered rows, one IDAT per
+   chunk) in DEVICE memory owned by the context (valid until its next PNG call); host or device rgb; enqueued on the
+   context's stream, synchronised because it returns a size.  Any decoder reads the file back to exactly the input
+   pixels; its bytes are this encoder's own (a pure function of the pixels), not the `png` crate's.  Needs a context, not
+   finalised weights.  A null pointer is ME_ERR_BAD_ARG; a non-positive size or one above ME_RESIZE_MAX_DIM is
+   ME_ERR_BAD_SHAPE.  Scratch belongs to the context and grows to the high-water mark. */
+int32_t me_png_encode_rgb8(me_ctx* ctx, const uint8_t* rgb, int32_t w, int32_t h,
+                           const uint8_t** png_dev, int64_t* nbytes);
+/* The same, copied to the host once and written to destination_path (an unwritable path is ME_ERR_IO). */
+int32_t me_output_png(me_ctx* ctx, const uint8_t* rgb, int32_t w, int32_t h, const char* destination_path);
+/* output.rs:123-139 output_depth_map, whole: me_depthmap_rgb_resized into context-owned device memory, then
+   me_output_png.  Arguments and errors as me_depthmap_rgb_resized. */
+int32_t me_output_depth_map_png(me_ctx* ctx, const float* depth, int32_t data_width, int32_t data_height,
+                                float min_depth, float max_depth, const float* minmax_dev,
+                                int32_t out_w, int32_t out_h, const char* destination_path);
+/* output.rs:141-193 output_stereogram, whole: me_stereogram into context-owned device memory, then me_output_png.
+   Arguments and errors as me_stereogram. */
+int32_t me_output_stereogram_png(me_ctx* ctx, const float* depth, int32_t rows, int32_t cols, float min_depth,
+                                 float max_depth, int32_t out_w, int32_t out_h, float amplitude,
+                                 const uint8_t* noise, const char* destination_path);
+
 /* output.rs:264-363 IndexedMesh::new + for_each_face + remap_face.
    depth [height,width] (DepthMap.data, stride `width`).  vertex_index [height*width]: the
    first-use vertex id or -1.  faces [nfaces,3] remapped vertex ids in the reference's

@@ -48,6 +48,13 @@ impl HipDevice {
         self.check(unsafe { ffi::me_output_flush(self.ctx) })
     }
 
+    /// RgbImage::save to ".png" for any 8-bit RGB picture (host bytes): encoded on the GPU, written to `destination_path`
+    pub fn save_png(&self, rgb: &[u8], w: u32, h: u32, destination_path: &str) -> Result<(), HipError> {
+        assert_eq!(rgb.len(), w as usize * h as usize * 3);
+        let dst = CString::new(destination_path).unwrap();
+        self.check(unsafe { ffi::me_output_png(self.ctx, rgb.as_ptr(), w as i32, h as i32, dst.as_ptr()) })
+    }
+
     /// DynamicImage::resize_exact(nw, nh, FilterType::Lanczos3) for an RGB8 buffer (reconstruction.rs:107-113,
     /// output.rs:206-218) on the GPU: the bytes `image` 0.25.10 writes.  `rgb` is `[h, w, 3]`, the result `[nh, nw, 3]`.
     pub fn resize_exact_lanczos3(&self, rgb: &[u8], w: u32, h: u32, nw: u32, nh: u32) -> Result<Vec<u8>, HipError> {
@@ -163,6 +170,27 @@ impl<'d> DepthMap<'d> {
                                self.range.1, out_w as i32, out_h as i32, amplitude, noise.as_ptr(), out.as_mut_ptr())
         })?;
         Ok(out)
+    }
+
+    /// output.rs:123-139 output_depth_map to a ".png" destination, whole: colour map, resize, row filters and deflate on
+    /// the GPU; only the file's bytes come back
+    pub fn output_depth_map_png(&self, destination_path: &str) -> Result<(), HipError> {
+        let (ow, oh) = self.original_size;
+        let dst = CString::new(destination_path).unwrap();
+        self.device.check(unsafe {
+            ffi::me_output_depth_map_png(self.device.ctx, self.data.as_ptr(), self.data_width as i32, self.data_height as i32, self.range.0,
+                                         self.range.1, null(), ow as i32, oh as i32, dst.as_ptr())
+        })
+    }
+
+    /// output.rs:141-193 output_stereogram to a ".png" destination, whole (`noise` as for `stereogram`)
+    pub fn output_stereogram_png(&self, out_w: u32, out_h: u32, amplitude: f32, noise: &[u8], destination_path: &str) -> Result<(), HipError> {
+        assert_eq!(noise.len(), out_w as usize * out_h as usize * 3);
+        let dst = CString::new(destination_path).unwrap();
+        self.device.check(unsafe {
+            ffi::me_output_stereogram_png(self.device.ctx, self.data.as_ptr(), self.data_width as i32, self.data_height as i32, self.range.0,
+                                          self.range.1, out_w as i32, out_h as i32, amplitude, noise.as_ptr(), dst.as_ptr())
+        })
     }
 
     /// output.rs:195-261 output_mesh with ObjWriter / PlyWriter (:385-630); vertex_mode = ME_VERTEX_*

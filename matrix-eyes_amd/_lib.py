@@ -80,6 +80,10 @@ SIGNATURES = {
     "me_depthmap_rgb": (_i32, [_vp, _vp, _i64, _f32, _f32, _vp]),
     "me_resize_lanczos3_rgb8": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _i32]),
     "me_depthmap_rgb_resized": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _vp, _i32, _i32, _vp]),
+    "me_png_encode_rgb8": (_i32, [_vp, _vp, _i32, _i32, C.POINTER(_vp), C.POINTER(_i64)]),
+    "me_output_png": (_i32, [_vp, _vp, _i32, _i32, C.c_char_p]),
+    "me_output_depth_map_png": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _vp, _i32, _i32, C.c_char_p]),
+    "me_output_stereogram_png": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _i32, _i32, _f32, _vp, C.c_char_p]),
     "me_mesh_index": (_i32, [_vp, _vp, _i32, _i32, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "me_mesh_vertices": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _u32, _u32, _vp, _vp]),
     "me_output_mesh": (_i32, [_vp, _vp, _i32, _i32, _u32, _u32, C.c_char_p, C.c_char_p, _i32, _vp]),

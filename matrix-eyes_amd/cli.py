@@ -116,14 +116,23 @@ def main(argv: Optional[List[str]] = None) -> int:
     except UsageExit as e:
         return int(e.code)
     from ._lib import MatrixEyesError
-    from .depth_pro import DepthProModelLoader, resolve_resampler
+    from .depth_pro import DepthProModelLoader, resolve_png_encoder, resolve_resampler
     from .reconstruction import extract_depth
     try:
         resolve_resampler()                  # MATRIX_EYES_RESAMPLER = pillow | device
     except MatrixEyesError as err:
         print(f"MATRIX_EYES_RESAMPLER: {err.message}", file=sys.stderr)
         return 2
-    loader = DepthProModelLoader(args.checkpoint_path, args.convert_checkpoints)
+    try:
+        resolve_png_encoder()                # MATRIX_EYES_PNG_ENCODER = pillow | device
+    except MatrixEyesError as err:
+        print(f"MATRIX_EYES_PNG_ENCODER: {err.message}", file=sys.stderr)
+        return 2
+    import os
+    from .config import ModelConfig
+    # MATRIX_EYES_MODEL=tiny: the test geometry of the parity suite, as the compiled CLI takes it
+    cfg = ModelConfig.tiny() if os.environ.get("MATRIX_EYES_MODEL") == "tiny" else None
+    loader = DepthProModelLoader(args.checkpoint_path, args.convert_checkpoints, cfg)
     try:
         extract_depth(0, loader, args.img_src, args.img_out, args.focal_length, args.output_format,
                       args.vertex_mode)

@@ -59,6 +59,20 @@ def resolve_resampler(resampler=None) -> str:
     return value
 
 
+PNG_ENCODERS = ("pillow", "device")
+
+
+def resolve_png_encoder(png_encoder=None) -> str:
+    """Who writes a ".png" destination (RgbImage::save, output.rs:138 and :192): "pillow" (the default) or "device"
+    (me_output_png and the two whole-method calls: row filters, deflate and CRCs on the GPU, only the file's bytes come
+    back).  The files decode to the same pixels.  None reads MATRIX_EYES_PNG_ENCODER; anything but the two names is an
+    argument error."""
+    value = os.environ.get("MATRIX_EYES_PNG_ENCODER", "pillow") if png_encoder is None else png_encoder
+    if value not in PNG_ENCODERS:
+        raise L.MatrixEyesError(1, f"png encoder {value!r}: expected one of {', '.join(PNG_ENCODERS)}")
+    return value
+
+
 class Context:
     """One GPU: stream, packed weights, workspaces (`me_ctx`)."""
 
@@ -280,6 +294,35 @@ class Context:
         po, out = _out(out, (nh, nw, 3), np.uint8)
         self._check(self.lib.me_resize_lanczos3_rgb8(self._h, p, w, h, po, nw, nh))
         return out
+
+    @staticmethod
+    def _rgb_shape(rgb, who):
+        if len(rgb.shape) != 3 or rgb.shape[2] != 3:
+            raise L.MatrixEyesError(2, f"{who}: uint8 [h, w, 3] expected, got {tuple(rgb.shape)}")
+        return int(rgb.shape[0]), int(rgb.shape[1])
+
+    def png_encode(self, rgb):
+        """RgbImage::save to ".png" without the file (me_png_encode_rgb8): uint8 [h, w, 3] -> the complete PNG file,
+        encoded on the GPU.  numpy in -> `bytes`; a CUDA torch tensor in -> a CUDA uint8 tensor (a copy of the
+        context-owned buffer)."""
+        h, w = self._rgb_shape(rgb, "png_encode")
+        p, keep = _in_ptr(rgb, np.uint8)
+        ptr, n = C.c_void_p(), C.c_int64()
+        self._check(self.lib.me_png_encode_rgb8(self._h, p, w, h, C.byref(ptr), C.byref(n)))
+        import torch
+
+        class _DevMem:
+            def __init__(self, ptr, nbytes):
+                self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
+        on_device = _is_torch(rgb) and rgb.is_cuda
+        file = torch.as_tensor(_DevMem(int(ptr.value), int(n.value)), device=rgb.device if on_device else "cuda")
+        return file.clone() if on_device else file.cpu().numpy().tobytes()
+
+    def output_png(self, rgb, destination_path: str):
+        """png_encode, copied to the host once and written to destination_path (me_output_png)"""
+        h, w = self._rgb_shape(rgb, "output_png")
+        p, keep = _in_ptr(rgb, np.uint8)
+        self._check(self.lib.me_output_png(self._h, p, w, h, str(destination_path).encode()))
 
     def vit_forward_features(self, which: int, xs, intermediate_blocks: Sequence[int] = ()):
         """vit.rs:328-346 -> (final [W,T,C], [intermediate ...])"""

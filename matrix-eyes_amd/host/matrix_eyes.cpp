@@ -56,6 +56,12 @@ Device::Device() {
         else if (std::strcmp(rs, "device") != 0)
             throw ModelError(ME_ERR_BAD_ARG, std::string("MATRIX_EYES_RESAMPLER=") + rs + ": expected host or device");
     }
+    if (const char* pe = std::getenv("MATRIX_EYES_PNG_ENCODER")) {
+        if (std::strcmp(pe, "device") == 0)
+            device_png_encoder_ = true;
+        else if (std::strcmp(pe, "host") != 0)
+            throw ModelError(ME_ERR_BAD_ARG, std::string("MATRIX_EYES_PNG_ENCODER=") + pe + ": expected host or device");
+    }
     me_model_config cfg;
     me_default_config(&cfg);
     if (model && std::strcmp(model, "tiny") == 0) {
@@ -145,6 +151,13 @@ void DepthMap::output_image(const std::string& destination_path, const std::stri
 }
 
 void DepthMap::output_depth_map(const std::string& destination_path) const {
+    if (device_.device_resampler() && device_.device_png_encoder() && ends_with_ci(destination_path, ".png")) {
+        // ... and the save: filtered and compressed on the GPU, only the file's bytes come back
+        check_output(device_.ctx(), me_output_depth_map_png(device_.ctx(), data_.data(), (int32_t)data_width_, (int32_t)data_height_,
+                                                            min_, max_, nullptr, (int32_t)original_width_, (int32_t)original_height_,
+                                                            destination_path.c_str()));
+        return;
+    }
     if (device_.device_resampler()) {  // the colour map and the resize chained on the GPU
         RgbImage resized(original_width_, original_height_);
         check_output(device_.ctx(), me_depthmap_rgb_resized(device_.ctx(), data_.data(), (int32_t)data_width_, (int32_t)data_height_, min_,
@@ -181,6 +194,12 @@ void DepthMap::output_stereogram(const std::string& destination_path, std::optio
     for (size_t i = 0; i < noise.data.size(); i += 4) {
         const uint32_t v = rng();
         for (size_t k = 0; k < 4 && i + k < noise.data.size(); ++k) noise.data[i + k] = (uint8_t)(v >> (8 * k));
+    }
+    if (device_.device_png_encoder() && ends_with_ci(destination_path, ".png")) {
+        check_output(device_.ctx(), me_output_stereogram_png(device_.ctx(), data_.data(), (int32_t)data_width_, (int32_t)data_height_,
+                                                             min_, max_, (int32_t)w, (int32_t)h, amplitude, noise.data.data(),
+                                                             destination_path.c_str()));
+        return;
     }
     check_output(device_.ctx(), me_stereogram(device_.ctx(), data_.data(), (int32_t)data_width_, (int32_t)data_height_, min_, max_,
                                               (int32_t)w, (int32_t)h, amplitude, noise.data.data(), out.data.data()));

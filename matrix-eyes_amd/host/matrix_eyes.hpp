@@ -59,11 +59,17 @@ public:
     // core.  Both write the `image` crate's bytes; any other value of the variable fails the constructor.
     bool device_resampler() const { return device_resampler_; }
     RgbImage resize_exact_lanczos3(const RgbImage& img, uint32_t width, uint32_t height) const;
+    // RgbImage::save to ".png" (output.rs:138, :192): with MATRIX_EYES_PNG_ENCODER=device output_depth_map and
+    // output_stereogram make, filter and compress the picture on the GPU in one call (me_output_depth_map_png,
+    // me_output_stereogram_png) and only the file's bytes come back; "host" (the default) is image_io's encode_png.  Any
+    // other value fails the constructor.  The files differ in their bytes, not in their pixels.
+    bool device_png_encoder() const { return device_png_encoder_; }
 
 private:
     me_ctx* ctx_ = nullptr;
     int image_size_ = IMG_SIZE;
     bool device_resampler_ = true;
+    bool device_png_encoder_ = false;
     mutable bool weights_loaded_ = false;
     friend class DepthProModelLoader;
 };

@@ -9,7 +9,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib as L
-from .depth_pro import Context, _in_ptr, resolve_resampler
+from .depth_pro import Context, _in_ptr, resolve_png_encoder, resolve_resampler
 
 
 class VertexMode(enum.IntEnum):   # output.rs:33-38
@@ -44,6 +44,14 @@ def _f32_round(x: float) -> int:
     if t <= 0:
         return 0
     return int(min(float(t), 4294967295.0))
+
+
+def _noise_rng():
+    """The stand-in for the reference's rand::rng(): seeded from the OS, or -- as the compiled CLI does -- from
+    MATRIX_EYES_SEED, which makes a run repeatable (the reference is not)."""
+    import os
+    seed = os.environ.get("MATRIX_EYES_SEED")
+    return np.random.default_rng(int(seed) if seed else None)
 
 
 class DepthMap:
@@ -86,7 +94,7 @@ class DepthMap:
         numpy when omitted."""
         w, h = self.stereogram_size(resize_scale)
         if noise is None:
-            noise = np.random.default_rng().integers(0, 256, size=(h, w, 3), dtype=np.uint8)
+            noise = _noise_rng().integers(0, 256, size=(h, w, 3), dtype=np.uint8)
         pn, keep = _in_ptr(noise, np.uint8)
         if tuple(noise.shape) != (h, w, 3):
             raise L.MatrixEyesError(2, f"noise must be [{h},{w},3]")
@@ -130,14 +138,44 @@ class DepthMap:
             self.original_width, self.original_height, C.c_void_p(out.ctypes.data)))
         return out
 
+    def output_depth_map_png(self, destination_path: str):
+        """output.rs:123-139 whole, on the GPU (me_output_depth_map_png): colour map, Lanczos3 resize, PNG file"""
+        mn, mx = self._range
+        self.ctx._check(self.ctx.lib.me_output_depth_map_png(
+            self.ctx.handle, C.c_void_p(self.data.ctypes.data), self.data_width, self.data_height, mn, mx, None,
+            self.original_width, self.original_height, str(destination_path).encode()))
+
+    def output_stereogram_png(self, destination_path: str, resize_scale: Optional[float], amplitude: float, noise=None):
+        """output.rs:141-193 whole, on the GPU (me_output_stereogram_png); noise as for `stereogram`"""
+        w, h = self.stereogram_size(resize_scale)
+        if noise is None:
+            noise = _noise_rng().integers(0, 256, size=(h, w, 3), dtype=np.uint8)
+        pn, keep = _in_ptr(noise, np.uint8)
+        if tuple(noise.shape) != (h, w, 3):
+            raise L.MatrixEyesError(2, f"noise must be [{h},{w},3]")
+        mn, mx = self._range
+        self.ctx._check(self.ctx.lib.me_output_stereogram_png(
+            self.ctx.handle, C.c_void_p(self.data.ctypes.data), self.data_width, self.data_height, mn, mx,
+            w, h, amplitude, pn, str(destination_path).encode()))
+
     def output_image(self, destination_path: str, source_path: str, image_format: ImageOutputFormat,
-                     vertex_mode: VertexMode, noise=None, resampler=None):
-        """output.rs:100-121: dispatch on the destination suffix.  resampler: depth_pro.resolve_resampler."""
+                     vertex_mode: VertexMode, noise=None, resampler=None, png_encoder=None):
+        """output.rs:100-121: dispatch on the destination suffix.  resampler: depth_pro.resolve_resampler;
+        png_encoder: depth_pro.resolve_png_encoder."""
         resampler = resolve_resampler(resampler)
+        png_encoder = resolve_png_encoder(png_encoder)
         low = destination_path.lower()
         if low.endswith(".ply") or low.endswith(".obj"):
             return self.output_mesh(destination_path, source_path, vertex_mode, resampler=resampler)
         from PIL import Image
+        if png_encoder == "device" and low.endswith(".png"):
+            native = self.original_width == self.original_height == self.data_width == self.data_height
+            if image_format.kind != "depthmap":
+                return self.output_stereogram_png(destination_path, image_format.resize_scale, image_format.amplitude, noise)
+            if resampler == "device" or native:   # (the resize is the identity at the native size)
+                return self.output_depth_map_png(destination_path)
+            img = Image.fromarray(self.depth_map_rgb()).resize((self.original_width, self.original_height), Image.LANCZOS)
+            return self.ctx.output_png(np.asarray(img, dtype=np.uint8), destination_path)
         if image_format.kind == "depthmap" and resampler == "device":
             Image.fromarray(self.depth_map_rgb_resized()).save(destination_path)
         elif image_format.kind == "depthmap":

@@ -11,3 +11,7 @@ _spec = importlib.util.spec_from_file_location(
 _mod = importlib.util.module_from_spec(_spec)
 sys.modules["matrix_eyes_amd"] = _mod
 _spec.loader.exec_module(_mod)
+
+if __name__ == "__main__":   # python -m matrix_eyes_amd: the command line (matrix-eyes_amd/cli.py)
+    from matrix_eyes_amd.cli import main
+    sys.exit(main())
