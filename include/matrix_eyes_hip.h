@@ -329,6 +329,35 @@ int32_t me_output_stereogram_png(me_ctx* ctx, const float* depth, int32_t rows, 
                                  float max_depth, int32_t out_w, int32_t out_h, float amplitude,
                                  const uint8_t* noise, const char* destination_path);
 
+/* ---- JPEG decoding on the device (reconstruction.rs:95-113: ImageReader::open(..).decode(), apply_orientation) --------- */
+
+/* Frame size and EXIF span of a JPEG file in memory: width / height as coded (before any orientation), and the offset and
+   length inside `file` of the TIFF-structured EXIF block (behind "Exif\0\0" of the first APP1 segment that has one; 0, 0:
+   none), which the caller parses with what it has.  Needs neither a GPU nor a context (ctx-less errors: me_last_error(NULL)).
+   A null pointer is ME_ERR_BAD_ARG, and so is a file the decoder refuses, with the decoder's message. */
+int32_t me_jpeg_info(const uint8_t* file, int64_t nbytes, int32_t* width, int32_t* height,
+                     int64_t* exif_offset, int64_t* exif_nbytes);
+/* The picture of a JPEG file (baseline, extended sequential or progressive Huffman; 8 bits; grey or three components with
+   integer sampling ratios; restart intervals), byte for byte what the C++ host layer's decoder writes (host/jpeg_decoder.cpp
+   decode_jpeg) followed by apply_orientation(orientation): the entropy-coded segments are decoded on the host into
+   pinned memory, and dequantisation, IDCT, level shift, chroma upsampling, colour conversion and the orientation run on the
+   GPU.  rgb [h,w,3] is the ORIENTED size (w and h swap for orientations 5..8), a host or device pointer; enqueued on the
+   context's stream: a device rgb is not synchronised, a host rgb is (the convention of me_resize_lanczos3_rgb8).  A null
+   pointer or an orientation outside 1..8 is ME_ERR_BAD_ARG; a size that does not match the file ME_ERR_BAD_SHAPE; a file
+   the decoder refuses ME_ERR_BAD_ARG with the decoder's own message ("<jpeg>: ..." in place of a path).  Needs a
+   context, not finalised weights.  Scratch belongs to the context and grows to the high-water mark. */
+int32_t me_jpeg_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t orientation,
+                            uint8_t* rgb, int32_t w, int32_t h);
+/* reconstruction.rs:95-113 in one call: me_jpeg_decode_rgb8 into context-owned device memory, then
+   me_resize_lanczos3_rgb8 to dst [nh,nw,3] (host or device): only the resized picture can cross to the host.  Errors as
+   the two calls; the oriented picture's sides are bound by ME_RESIZE_MAX_DIM. */
+int32_t me_jpeg_decode_resized_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t orientation,
+                                    uint8_t* dst, int32_t nw, int32_t nh);
+/* Legs of the context's last JPEG decode in milliseconds: [0] entropy decoding on the host (wall clock), [1] upload of the
+   coefficients, [2] jpeg_idct_kernel, [3] jpeg_finish_kernel, [4] download to a host rgb (0 for a device one); [1]..[4]
+   are HIP event times.  Synchronises the context's stream. */
+int32_t me_last_jpeg_timing(me_ctx* ctx, double ms_out[5]);
+
 /* output.rs:264-363 IndexedMesh::new + for_each_face + remap_face.
    depth [height,width] (DepthMap.data, stride `width`).  vertex_index [height*width]: the
    first-use vertex id or -1.  faces [nfaces,3] remapped vertex ids in the reference's

@@ -211,6 +211,10 @@ int32_t me_profile_report(me_ctx* ctx, char* json, int64_t capacity);
    with libm's sinf, whatever the device): it can be tested on a machine without a GPU. */
 int64_t me_op_lanczos3_table(int32_t len_in, int32_t len_out, int32_t* left, int32_t* count,
                              float* weights, int64_t weights_cap);
+/* The C++ host layer's JPEG decoder (host/jpeg_decoder.cpp decode_jpeg, no orientation) from inside the library: the
+   yardstick me_jpeg_decode_rgb8 is measured against in the same process (tools/bench_jpeg.py).  HOST arrays only, no
+   context, no GPU; rgb [h,w,3].  0, or < 0 on a null pointer, a size that does not match or a file the decoder refuses. */
+int32_t me_op_jpeg_decode_host(const uint8_t* file, int64_t nbytes, uint8_t* rgb, int32_t w, int32_t h);
 /* Names of the GEMM tile configurations (for reports). */
 int32_t me_op_gemm_config_count(void);
 const char* me_op_gemm_config_name(int32_t cfg);

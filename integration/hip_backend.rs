@@ -64,6 +64,28 @@ impl HipDevice {
         Ok(out)
     }
 
+    /// reconstruction.rs:95-113 for a JPEG photo in one call, in place of `ImageReader::open(..).decode()`,
+    /// `apply_orientation` and `resize_exact(IMG_SIZE, IMG_SIZE, Lanczos3)`: `file` is the file's bytes, `orientation` the
+    /// EXIF value (1..8) the caller read from the block `jpeg_info` points at.  Entropy decoding runs on the host, the
+    /// reconstruction, the orientation and the resize on the GPU; only the `[nh, nw, 3]` picture comes back.  The pixels are
+    /// the C++ host layer's decoder's, which agrees with `image`'s (zune-jpeg) to within JPEG's usual unit or two.
+    pub fn decode_jpeg_resized(&self, file: &[u8], orientation: i32, nw: u32, nh: u32) -> Result<Vec<u8>, HipError> {
+        let mut out = vec![0u8; nw as usize * nh as usize * 3];
+        self.check(unsafe { ffi::me_jpeg_decode_resized_rgb8(self.ctx, file.as_ptr(), file.len() as i64, orientation, out.as_mut_ptr(), nw as i32, nh as i32) })?;
+        Ok(out)
+    }
+
+    /// (width, height, exif_offset, exif_len) of a JPEG file: the size as coded and where its TIFF-structured EXIF block
+    /// lies in `file` (0, 0: none) -- hand that slice to `exif::Reader::read_raw`.  No GPU work.
+    pub fn jpeg_info(file: &[u8]) -> Result<(u32, u32, usize, usize), HipError> {
+        let (mut w, mut h, mut off, mut n) = (0i32, 0i32, 0i64, 0i64);
+        let rc = unsafe { ffi::me_jpeg_info(file.as_ptr(), file.len() as i64, &mut w, &mut h, &mut off, &mut n) };
+        if rc != ffi::ME_OK {
+            return Err(last_error(std::ptr::null(), rc));
+        }
+        Ok((w as u32, h as u32, off as usize, n as usize))
+    }
+
     fn check(&self, rc: i32) -> Result<(), HipError> {
         if rc == ffi::ME_OK {
             Ok(())

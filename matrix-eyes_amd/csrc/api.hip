@@ -7,6 +7,7 @@
 #include <exception>
 
 #include "../../include/matrix_eyes_hip_ops.h"
+#include "../host/image_io.hpp"
 #include "model.h"
 #include "mx_fp8.h"
 
@@ -321,6 +322,7 @@ void me_ctx_destroy(me_ctx* ctx) {
     for (auto& kv : ctx->bufs)
         if (kv.second.p) (void)hipFree(kv.second.p);
     me::free_resample_tables(ctx);
+    me::free_jpeg_scratch(ctx);
     if (ctx->arena) (void)hipFree(ctx->arena);
     if (ctx->arena8) (void)hipFree(ctx->arena8);
     if (ctx->status_dev) (void)hipFree(ctx->status_dev);
@@ -982,6 +984,98 @@ int32_t me_resize_lanczos3_rgb8(me_ctx* ctx, const uint8_t* src, int32_t w, int3
     OutBuf o = out_buf(ctx, dst, nout, "resample.dst");
     resize_lanczos3_rgb8(ctx, s, w, h, (uint8_t*)o.dev, nw, nh);
     finish(ctx, o);
+    ME_API_END(ctx)
+}
+
+// ---- JPEG decoding (jpeg_decode.hip) -------------------------------------------------------------------------------
+int32_t me_jpeg_info(const uint8_t* file, int64_t nbytes, int32_t* width, int32_t* height, int64_t* exif_offset,
+                     int64_t* exif_nbytes) {
+    if (!file || nbytes < 0 || !width || !height || !exif_offset || !exif_nbytes) {
+        g_create_error = "me_jpeg_info: null pointer";
+        return ME_ERR_BAD_ARG;
+    }
+    try {
+        const std::vector<uint8_t> bytes(file, file + nbytes);
+        const matrix_eyes::JpegCoefficients head = matrix_eyes::parse_jpeg_header(bytes, "<jpeg>");
+        *width = head.width, *height = head.height;
+        *exif_offset = (int64_t)head.exif_offset, *exif_nbytes = (int64_t)head.exif_nbytes;
+    } catch (const std::exception& e) {
+        g_create_error = e.what();
+        return ME_ERR_BAD_ARG;
+    }
+    return ME_OK;
+}
+
+int32_t me_op_jpeg_decode_host(const uint8_t* file, int64_t nbytes, uint8_t* rgb, int32_t w, int32_t h) {
+    if (!file || nbytes < 0 || !rgb) return -1;
+    try {
+        const std::vector<uint8_t> bytes(file, file + nbytes);
+        const matrix_eyes::RgbImage img = matrix_eyes::decode_jpeg(bytes, "<jpeg>", nullptr);
+        if ((int64_t)img.width != w || (int64_t)img.height != h) return -2;
+        std::memcpy(rgb, img.data.data(), img.data.size());
+    } catch (const std::exception&) {
+        return -3;
+    }
+    return 0;
+}
+
+namespace {
+void check_jpeg_args(const char* who, const uint8_t* file, int64_t nbytes, int32_t orientation, const void* dst) {
+    ME_CHECK(file && dst && nbytes >= 0, ME_ERR_BAD_ARG, "%s: null pointer", who);
+    ME_CHECK(orientation >= 1 && orientation <= 8, ME_ERR_BAD_ARG, "%s: orientation %d outside 1..8", who, orientation);
+    ME_CHECK(!is_device_ptr(file), ME_ERR_BAD_ARG, "%s: the file's bytes must be in host memory (they are parsed there)", who);
+}
+}  // namespace
+
+int32_t me_jpeg_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t orientation, uint8_t* rgb, int32_t w,
+                            int32_t h) {
+    ME_API_BEGIN(ctx)
+    check_jpeg_args("me_jpeg_decode_rgb8", file, nbytes, orientation, rgb);
+    ME_CHECK(w > 0 && h > 0, ME_ERR_BAD_SHAPE, "me_jpeg_decode_rgb8: %dx%d", w, h);
+    const size_t nout = (size_t)w * h * 3;
+    const bool dev = is_device_ptr(rgb);
+    int32_t ow = 0, oh = 0;
+    uint8_t* d = jpeg_decode_rgb8(ctx, file, nbytes, orientation, dev ? rgb : nullptr, w, h, &ow, &oh);
+    if (!dev) {
+        ME_HIP(hipMemcpyAsync(rgb, d, nout, hipMemcpyDeviceToHost, ctx->stream));
+        ME_HIP(hipEventRecord(ctx->jpeg_ev[4], ctx->stream));
+        ctx->jpeg_timed_download = true;
+        ME_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    ME_API_END(ctx)
+}
+
+int32_t me_jpeg_decode_resized_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t orientation, uint8_t* dst,
+                                    int32_t nw, int32_t nh) {
+    ME_API_BEGIN(ctx)
+    check_jpeg_args("me_jpeg_decode_resized_rgb8", file, nbytes, orientation, dst);
+    ME_CHECK(nw > 0 && nh > 0 && nw <= ME_RESIZE_MAX_DIM && nh <= ME_RESIZE_MAX_DIM, ME_ERR_BAD_SHAPE,
+             "me_jpeg_decode_resized_rgb8: -> %dx%d", nw, nh);
+    {
+        int32_t fw = 0, fh = 0;  // the file's size before anything is decoded: the resampler's bound
+        int64_t eo = 0, en = 0;
+        if (me_jpeg_info(file, nbytes, &fw, &fh, &eo, &en) != ME_OK) fail(ME_ERR_BAD_ARG, "%s", g_create_error.c_str());
+        check_resize_shape("me_jpeg_decode_resized_rgb8", fw, fh, nw, nh);
+    }
+    int32_t ow = 0, oh = 0;
+    const uint8_t* full = jpeg_decode_rgb8(ctx, file, nbytes, orientation, nullptr, 0, 0, &ow, &oh);
+    OutBuf o = out_buf(ctx, dst, (size_t)nw * nh * 3, "jpeg.resized");
+    resize_lanczos3_rgb8(ctx, full, ow, oh, (uint8_t*)o.dev, nw, nh);
+    finish(ctx, o);
+    ME_API_END(ctx)
+}
+
+int32_t me_last_jpeg_timing(me_ctx* ctx, double ms_out[5]) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(ms_out, ME_ERR_BAD_ARG, "me_last_jpeg_timing: null pointer");
+    ME_CHECK(ctx->jpeg_timed, ME_ERR_NOT_READY, "me_last_jpeg_timing: no JPEG decode has completed on this context");
+    ME_HIP(hipStreamSynchronize(ctx->stream));
+    ms_out[0] = ctx->jpeg_entropy_ms;
+    for (int i = 0; i < 4; ++i) {
+        float ms = 0.f;
+        if (i < 3 || ctx->jpeg_timed_download) ME_HIP(hipEventElapsedTime(&ms, ctx->jpeg_ev[i], ctx->jpeg_ev[i + 1]));
+        ms_out[1 + i] = ms;
+    }
     ME_API_END(ctx)
 }
 

@@ -237,6 +237,18 @@ struct me_ctx {
     std::vector<me::ResampleTable> rs_tables;
     uint64_t rs_stamp = 0;
 
+    // JPEG decoding (jpeg_decode.hip): the pinned host buffer the entropy decoder fills and the upload reads, grown to the
+    // high-water mark; `jpeg_uploaded` is recorded behind every upload, and the next decode waits for it on the host
+    // before it writes the buffer again (calls may be queued without a synchronise between them).  jpeg_ev: the marks
+    // around the legs of the last decode (me_last_jpeg_timing).
+    int16_t* jpeg_pinned = nullptr;
+    size_t jpeg_pinned_count = 0;
+    hipEvent_t jpeg_uploaded = nullptr;
+    bool jpeg_upload_pending = false;
+    hipEvent_t jpeg_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool jpeg_timed = false, jpeg_timed_download = false;
+    double jpeg_entropy_ms = 0.0;
+
     // The whole extract_depth step as one hipGraph (shapes are static per batch size).  A call whose pointers
     // all live on the device and that needs no host callback is enqueued eagerly the first time it is seen,
     // captured the second time and replayed with one hipGraphLaunch from then on; anything that changes what the
@@ -360,6 +372,14 @@ struct OutputScope {
 // resample.hip: DynamicImage::resize_exact(nw, nh, Lanczos3) for 8-bit RGB, device pointers, on ctx->stream
 void resize_lanczos3_rgb8(me_ctx* ctx, const uint8_t* src_dev, int32_t w, int32_t h, uint8_t* dst_dev, int32_t nw, int32_t nh);
 void free_resample_tables(me_ctx* ctx);
+
+// jpeg_decode.hip: a JPEG file in host memory -> its oriented RGB picture [oh][ow][3] in device memory, on ctx->stream.
+// Throws me::Error (ME_ERR_BAD_ARG with the host decoder's message for a file it refuses, ME_ERR_BAD_SHAPE for a size that
+// does not match).  dst_dev == nullptr: into the context's own "jpeg.rgb" buffer; returns where the picture is.  want_w /
+// want_h <= 0: any size; *ow / *oh receive the oriented size.
+uint8_t* jpeg_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t orientation, uint8_t* dst_dev,
+                          int32_t want_w, int32_t want_h, int32_t* ow, int32_t* oh);
+void free_jpeg_scratch(me_ctx* ctx);
 
 // calibrate.hip: the two fixed loops of bench.py's calibration leg (out[6])
 void calibrate(me_ctx* ctx, double* out);

@@ -73,6 +73,20 @@ def resolve_png_encoder(png_encoder=None) -> str:
     return value
 
 
+JPEG_DECODERS = ("pillow", "host", "device")
+
+
+def resolve_jpeg_decoder(jpeg_decoder=None) -> str:
+    """Who decodes a ".jpg" / ".jpeg" source (reconstruction.rs:95-106): "pillow" (the default; "host", the compiled
+    CLI's name for its own decoder, means the same here) or "device" (me_jpeg_decode_rgb8 / me_jpeg_decode_resized_rgb8:
+    entropy decoding on the host, reconstruction and orientation on the GPU, the C++ host decoder's bytes).  None reads
+    MATRIX_EYES_JPEG_DECODER; anything but these names is an argument error."""
+    value = os.environ.get("MATRIX_EYES_JPEG_DECODER", "pillow") if jpeg_decoder is None else jpeg_decoder
+    if value not in JPEG_DECODERS:
+        raise L.MatrixEyesError(1, f"jpeg decoder {value!r}: expected one of {', '.join(JPEG_DECODERS)}")
+    return "pillow" if value == "host" else value
+
+
 class Context:
     """One GPU: stream, packed weights, workspaces (`me_ctx`)."""
 
@@ -294,6 +308,49 @@ class Context:
         po, out = _out(out, (nh, nw, 3), np.uint8)
         self._check(self.lib.me_resize_lanczos3_rgb8(self._h, p, w, h, po, nw, nh))
         return out
+
+    @staticmethod
+    def jpeg_info(data: bytes):
+        """(width, height, exif_offset, exif_nbytes) of a JPEG file in memory (me_jpeg_info): the size as coded, before
+        any orientation, and the span of the TIFF-structured EXIF block inside `data` (0, 0: none).  No GPU."""
+        lib = L.load_library()
+        data = bytes(data)
+        w, h, off, n = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+        rc = lib.me_jpeg_info(data, len(data), C.byref(w), C.byref(h), C.byref(off), C.byref(n))
+        if rc != L.ME_OK:
+            msg = lib.me_last_error(None)
+            raise L.MatrixEyesError(rc, msg.decode("utf-8", "replace") if msg else "")
+        return w.value, h.value, off.value, n.value
+
+    def decode_jpeg(self, data: bytes, orientation: int = 1, out=None):
+        """The picture of a JPEG file, oriented (me_jpeg_decode_rgb8): uint8 [h, w, 3], the C++ host decoder's bytes.
+        out: a numpy array or a CUDA torch tensor of the oriented shape (a CUDA one is only queued on the context's
+        stream); None: a new numpy array."""
+        data = bytes(data)
+        w, h, _, _ = self.jpeg_info(data)
+        if 5 <= int(orientation) <= 8:
+            w, h = h, w
+        po, out = _out(out, (h, w, 3), np.uint8)
+        self._check(self.lib.me_jpeg_decode_rgb8(self._h, data, len(data), int(orientation), po, w, h))
+        return out
+
+    def decode_jpeg_resized(self, data: bytes, size, orientation: int = 1, out=None):
+        """decode_jpeg into context-owned device memory, then resize_lanczos3 to size = (nw, nh)
+        (me_jpeg_decode_resized_rgb8, reconstruction.rs:95-113 in one call): only the resized picture leaves the device,
+        or, with a CUDA `out`, nothing does."""
+        data = bytes(data)
+        nw, nh = int(size[0]), int(size[1])
+        if nw <= 0 or nh <= 0:
+            raise L.MatrixEyesError(2, f"decode_jpeg_resized: target size {nw}x{nh}")
+        po, out = _out(out, (nh, nw, 3), np.uint8)
+        self._check(self.lib.me_jpeg_decode_resized_rgb8(self._h, data, len(data), int(orientation), po, nw, nh))
+        return out
+
+    def last_jpeg_timing(self):
+        """[entropy decode (host), upload, IDCT kernel, finish kernel, download] of the last decode, in ms"""
+        ms = (C.c_double * 5)()
+        self._check(self.lib.me_last_jpeg_timing(self._h, ms))
+        return list(ms)
 
     @staticmethod
     def _rgb_shape(rgb, who):

@@ -45,7 +45,7 @@ struct Component {
     int width = 0, height = 0;     // samples: ceil(W * h / hmax)
     int blocks_w = 0, blocks_h = 0;  // allocated blocks (whole MCUs)
     int pred = 0;
-    std::vector<int16_t> coef;     // blocks_w * blocks_h * 64, natural (de-zigzagged) order
+    int16_t* coef = nullptr;       // blocks_w * blocks_h * 64, natural (de-zigzagged) order (in Decoder::coef_store or the caller's)
     std::vector<uint8_t> plane;    // blocks_w * 8 x blocks_h * 8 samples after the IDCT
 };
 
@@ -116,11 +116,16 @@ struct Decoder {
     bool progressive = false, have_frame = false;
     int restart_interval = 0;
     int adobe_transform = -1;
-    uint16_t qt[4][64];
+    uint16_t qt[4][64] = {};
     bool qt_present[4] = {false, false, false, false};
     HuffTable dc[4], ac[4];
     std::vector<Component> comps;
-    std::vector<uint8_t> exif;
+    size_t exif_offset = 0, exif_nbytes = 0;  // the block behind "Exif\0\0" of the first APP1 that has one
+    bool header_only = false;                 // stop at the first scan (parse_jpeg_header)
+    JpegCoefAlloc alloc = nullptr;            // where the coefficients live when the caller provides the memory
+    void* alloc_user = nullptr;
+    std::vector<int16_t> coef_store;
+    size_t total_coefs = 0;
 
     Decoder(const std::vector<uint8_t>& f, const std::string& p) : file(f), path(p) {}
 
@@ -179,10 +184,25 @@ struct Decoder {
         }
         if (n == 1) comps[0].h = comps[0].v = hmax = vmax = 1;  // a single component is never interleaved
         const int mcus_x = (width + 8 * hmax - 1) / (8 * hmax), mcus_y = (height + 8 * vmax - 1) / (8 * vmax);
+        total_coefs = 0;
         for (Component& c : comps) {
             c.width = (width * c.h + hmax - 1) / hmax, c.height = (height * c.v + vmax - 1) / vmax;
             c.blocks_w = mcus_x * c.h, c.blocks_h = mcus_y * c.v;
-            c.coef.assign((size_t)c.blocks_w * c.blocks_h * 64, 0);
+            total_coefs += (size_t)c.blocks_w * c.blocks_h * 64;
+        }
+        if (!header_only) {
+            int16_t* base;
+            if (alloc) {
+                base = alloc(alloc_user, total_coefs);
+                std::memset(base, 0, total_coefs * sizeof(int16_t));
+            } else {
+                coef_store.assign(total_coefs, 0);
+                base = coef_store.data();
+            }
+            for (Component& c : comps) {
+                c.coef = base;
+                base += (size_t)c.blocks_w * c.blocks_h * 64;
+            }
         }
         progressive = prog, have_frame = true;
     }
@@ -369,9 +389,7 @@ struct Decoder {
     void idct_all() {
         // exact separable IDCT in double precision (T.81 A.3.3), level shift, clamp
         double basis[8][8];
-        for (int x = 0; x < 8; ++x)
-            for (int u = 0; u < 8; ++u)
-                basis[x][u] = (u == 0 ? std::sqrt(0.125) : 0.5) * std::cos((2 * x + 1) * u * 3.14159265358979323846 / 16.0);
+        jpeg_idct_basis(&basis[0][0]);
         for (Component& c : comps) {
             if (!qt_present[c.tq]) fail("component uses an undefined quantisation table");
             const uint16_t* q = qt[c.tq];
@@ -407,8 +425,6 @@ struct Decoder {
                             out[(size_t)y * pw + x] = (uint8_t)std::min(255, std::max(0, px));
                         }
                 }
-            c.coef.clear();
-            c.coef.shrink_to_fit();
         }
     }
 
@@ -504,7 +520,8 @@ struct Decoder {
         return img;
     }
 
-    RgbImage run() {
+    // everything up to and including the entropy-coded segments
+    void parse() {
         if (file.size() < 4 || file[0] != 0xff || file[1] != 0xd8) fail("not a JPEG file");
         size_t pos = 2;
         bool done = false;
@@ -531,12 +548,16 @@ struct Decoder {
                     restart_interval = be16(body);
                     break;
                 case 0xe1:
-                    if (exif.empty() && len >= 8 && !std::memcmp(&file[body], "Exif\0\0", 6)) exif.assign(file.data() + body + 6, file.data() + end);
+                    if (exif_nbytes == 0 && len >= 8 && !std::memcmp(&file[body], "Exif\0\0", 6)) exif_offset = body + 6, exif_nbytes = end - (body + 6);
                     break;
                 case 0xee:
                     if (len >= 14 && !std::memcmp(&file[body], "Adobe", 5)) adobe_transform = file[body + 11];
                     break;
                 case 0xda:
+                    if (header_only) {
+                        if (!have_frame) fail("SOS before SOF");
+                        return;
+                    }
                     pos = parse_sos(body, end);
                     continue;
                 default: break;  // APPn, COM, ...
@@ -544,7 +565,25 @@ struct Decoder {
             pos = end;
         }
         if (!have_frame) fail("JPEG without a frame header");
-        return finish();
+    }
+
+    JpegCoefficients coefficients() {
+        JpegCoefficients out;
+        out.width = width, out.height = height, out.hmax = hmax, out.vmax = vmax;
+        for (const Component& c : comps) {
+            JpegComponent o;
+            o.id = c.id, o.h = c.h, o.v = c.v, o.tq = c.tq;
+            o.width = c.width, o.height = c.height, o.blocks_w = c.blocks_w, o.blocks_h = c.blocks_h;
+            o.coef = c.coef;
+            out.comps.push_back(o);
+        }
+        std::memcpy(out.qt, qt, sizeof(qt));
+        std::memcpy(out.qt_present, qt_present, sizeof(qt_present));
+        out.adobe_transform = adobe_transform;
+        out.exif_offset = exif_offset, out.exif_nbytes = exif_nbytes;
+        out.total_coefs = total_coefs;
+        out.storage = std::move(coef_store);  // (a vector's buffer keeps its address when moved)
+        return out;
     }
 };
 
@@ -552,9 +591,33 @@ struct Decoder {
 
 RgbImage decode_jpeg(const std::vector<uint8_t>& file, const std::string& path, std::vector<uint8_t>* exif) {
     Decoder d(file, path);
-    RgbImage img = d.run();
-    if (exif) *exif = std::move(d.exif);
+    d.parse();
+    RgbImage img = d.finish();
+    if (exif) exif->assign(file.data() + d.exif_offset, file.data() + d.exif_offset + d.exif_nbytes);
     return img;
+}
+
+JpegCoefficients decode_jpeg_coefficients(const std::vector<uint8_t>& file, const std::string& path, JpegCoefAlloc alloc,
+                                          void* alloc_user) {
+    Decoder d(file, path);
+    d.alloc = alloc, d.alloc_user = alloc_user;
+    d.parse();
+    return d.coefficients();
+}
+
+JpegCoefficients parse_jpeg_header(const std::vector<uint8_t>& file, const std::string& path) {
+    Decoder d(file, path);
+    d.header_only = true;
+    d.parse();
+    return d.coefficients();
+}
+
+// what Decoder::finish refuses, in its order: idct_all per component, then upsample per component
+void check_jpeg_reconstructible(const JpegCoefficients& c, const std::string& path) {
+    for (const JpegComponent& k : c.comps)
+        if (!c.qt_present[k.tq]) throw ImageError(path + ": component uses an undefined quantisation table");
+    for (const JpegComponent& k : c.comps)
+        if (c.hmax % k.h || c.vmax % k.v) throw ImageError(path + ": fractional JPEG sampling ratios are not supported");
 }
 
 }  // namespace matrix_eyes

@@ -4,6 +4,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
+#include <iterator>
 #include <random>
 
 #include "matrix_eyes_hip.h"
@@ -62,6 +64,12 @@ Device::Device() {
         else if (std::strcmp(pe, "host") != 0)
             throw ModelError(ME_ERR_BAD_ARG, std::string("MATRIX_EYES_PNG_ENCODER=") + pe + ": expected host or device");
     }
+    if (const char* jd = std::getenv("MATRIX_EYES_JPEG_DECODER")) {
+        if (std::strcmp(jd, "device") == 0)
+            device_jpeg_decoder_ = true;
+        else if (std::strcmp(jd, "host") != 0)
+            throw ModelError(ME_ERR_BAD_ARG, std::string("MATRIX_EYES_JPEG_DECODER=") + jd + ": expected host or device");
+    }
     me_model_config cfg;
     me_default_config(&cfg);
     if (model && std::strcmp(model, "tiny") == 0) {
@@ -100,6 +108,42 @@ RgbImage Device::resize_exact_lanczos3(const RgbImage& img, uint32_t width, uint
                                                (int32_t)width, (int32_t)height);
     if (rc != ME_OK) throw ImageError(std::string("cannot resize: ") + me_last_error(ctx_));
     return out;
+}
+
+bool Device::load_jpeg_resized(const std::string& path, bool with_orientation, uint32_t width, uint32_t height, RgbImage* out,
+                               ImageMetadata* metadata, uint32_t* original_width, uint32_t* original_height) const {
+    if (!device_jpeg_decoder_ || !(ends_with_ci(path, ".jpg") || ends_with_ci(path, ".jpeg"))) return false;
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw ImageError("cannot open " + path);
+    const std::vector<uint8_t> file((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    if (!(file.size() >= 3 && file[0] == 0xff && file[1] == 0xd8 && file[2] == 0xff)) return false;  // load_image goes by the signature
+    // the library says "<jpeg>: ..." where the host decoder says "<path>: ..."
+    auto refuse = [&](const char* message) {
+        const std::string m = message ? message : "";
+        throw ImageError(m.rfind("<jpeg>", 0) == 0 ? path + m.substr(6) : m);
+    };
+    int32_t w = 0, h = 0;
+    int64_t exif_offset = 0, exif_nbytes = 0;
+    if (me_jpeg_info(file.data(), (int64_t)file.size(), &w, &h, &exif_offset, &exif_nbytes) != ME_OK) refuse(me_last_error(nullptr));
+    const ImageMetadata meta = parse_exif(std::vector<uint8_t>(file.begin() + exif_offset, file.begin() + exif_offset + exif_nbytes));
+    if (metadata) *metadata = meta;
+    // apply_orientation leaves the picture alone for a value outside 2..8
+    const int orientation = with_orientation && meta.orientation >= 2 && meta.orientation <= 8 ? meta.orientation : 1;
+    const uint32_t ow = orientation >= 5 ? (uint32_t)h : (uint32_t)w, oh = orientation >= 5 ? (uint32_t)w : (uint32_t)h;
+    if (original_width) *original_width = ow;
+    if (original_height) *original_height = oh;
+    if (device_resampler_) {  // decode, orientation and resize chained on the GPU: only the resized picture comes back
+        *out = RgbImage(width, height);
+        const int32_t rc = me_jpeg_decode_resized_rgb8(ctx_, file.data(), (int64_t)file.size(), orientation, out->data.data(),
+                                                       (int32_t)width, (int32_t)height);
+        if (rc != ME_OK) refuse(me_last_error(ctx_));
+        return true;
+    }
+    RgbImage full(ow, oh);
+    const int32_t rc = me_jpeg_decode_rgb8(ctx_, file.data(), (int64_t)file.size(), orientation, full.data.data(), (int32_t)ow, (int32_t)oh);
+    if (rc != ME_OK) refuse(me_last_error(ctx_));
+    *out = matrix_eyes::resize_exact_lanczos3(full, width, height);
+    return true;
 }
 
 // ---- DepthProModelLoader -----------------------------------------------------------------------------
@@ -214,7 +258,11 @@ void DepthMap::output_mesh(const std::string& destination_path, const std::strin
     std::vector<uint8_t> colors;
     if (mode == VertexMode::Color) {  // output.rs:206-218
         try {
-            colors = device_.resize_exact_lanczos3(load_image(source_path), (uint32_t)data_width_, (uint32_t)data_height_).data;
+            RgbImage resized;  // the source as decoded (no orientation), resized to the depth map
+            if (!device_.load_jpeg_resized(source_path, false, (uint32_t)data_width_, (uint32_t)data_height_, &resized, nullptr, nullptr,
+                                           nullptr))
+                resized = device_.resize_exact_lanczos3(load_image(source_path), (uint32_t)data_width_, (uint32_t)data_height_);
+            colors = std::move(resized.data);
         } catch (const ImageError& err) {
             throw OutputError(err.what());
         }
@@ -259,6 +307,14 @@ SourceImage SourceImage::load_with(const Device* device, const std::string& path
     RgbImage img;
     ImageMetadata meta;
     try {
+        // a JPEG photo with MATRIX_EYES_JPEG_DECODER=device: reconstruction, orientation (:104-106) and the resize (:107-113) on the GPU
+        uint32_t ow = 0, oh = 0;
+        if (device && device->load_jpeg_resized(path, true, (uint32_t)size, (uint32_t)size, &s.img, &meta, &ow, &oh)) {
+            s.focal_length_35mm = focal_length_35mm;
+            if (!s.focal_length_35mm && meta.focal_length_35mm) s.focal_length_35mm = (float)*meta.focal_length_35mm;
+            s.original_width = ow, s.original_height = oh;
+            return s;
+        }
         img = load_image(path, &meta);
     } catch (const ImageError& err) {
         throw ReconstructionError(std::string("Image error: ") + err.what());

@@ -64,12 +64,24 @@ public:
     // me_output_stereogram_png) and only the file's bytes come back; "host" (the default) is image_io's encode_png.  Any
     // other value fails the constructor.  The files differ in their bytes, not in their pixels.
     bool device_png_encoder() const { return device_png_encoder_; }
+    // ImageReader::open(..).decode() of a JPEG photo (reconstruction.rs:95-106): with MATRIX_EYES_JPEG_DECODER=device the
+    // entropy-coded segments are decoded on the host and the picture is reconstructed and oriented on the GPU
+    // (me_jpeg_decode_rgb8), chained there with the resize when the device resampler is on (me_jpeg_decode_resized_rgb8:
+    // the full-size picture never exists on the host); "host" (the default) is jpeg_decoder.cpp.  Both write the same
+    // bytes; any other value fails the constructor.
+    bool device_jpeg_decoder() const { return device_jpeg_decoder_; }
+    // load_image + (with_orientation: apply_orientation with the file's EXIF value) + resize_exact_lanczos3(width, height)
+    // of a ".jpg" / ".jpeg" file through the device decoder.  False (nothing done) when the decoder is "host" or the file
+    // is not a JPEG by name and signature: the caller takes the host path.  original_*: the oriented size before the resize.
+    bool load_jpeg_resized(const std::string& path, bool with_orientation, uint32_t width, uint32_t height, RgbImage* out,
+                           ImageMetadata* metadata, uint32_t* original_width, uint32_t* original_height) const;
 
 private:
     me_ctx* ctx_ = nullptr;
     int image_size_ = IMG_SIZE;
     bool device_resampler_ = true;
     bool device_png_encoder_ = false;
+    bool device_jpeg_decoder_ = false;
     mutable bool weights_loaded_ = false;
     friend class DepthProModelLoader;
 };

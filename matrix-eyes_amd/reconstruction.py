@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from .depth_pro import IMG_SIZE, DepthProModelLoader, resolve_resampler
+from .depth_pro import IMG_SIZE, DepthProModelLoader, resolve_jpeg_decoder, resolve_resampler
 from .output import DepthMap, ImageOutputFormat, VertexMode
 
 _EXIF_IFD = 0x8769
@@ -31,12 +31,16 @@ class SourceImage:                          # reconstruction.rs:74-81
 
     @staticmethod
     def load(path: str, focal_length_35mm: Optional[float] = None, size: int = IMG_SIZE, resampler=None,
-             ctx=None) -> "SourceImage":
+             ctx=None, jpeg_decoder=None) -> "SourceImage":
         """reconstruction.rs:87-131: decode, EXIF focal length, orientation, Lanczos3 to size x size.
         resampler: depth_pro.resolve_resampler; "device" resizes on `ctx` (a Context, or a callable that returns one
-        and is only called once the file has been decoded)."""
+        and is only called once the file has been decoded).  jpeg_decoder: depth_pro.resolve_jpeg_decoder; "device"
+        decodes a .jpg / .jpeg source on `ctx` (Pillow still reads the EXIF block), chained with the resize when the
+        resampler is "device" too."""
         from PIL import Image, ImageOps
         resampler = resolve_resampler(resampler)
+        if resolve_jpeg_decoder(jpeg_decoder) == "device" and path.lower().endswith((".jpg", ".jpeg")):
+            return SourceImage._load_jpeg_on_device(path, focal_length_35mm, size, resampler, ctx)
         try:
             img = Image.open(path)
             img.load()
@@ -59,6 +63,41 @@ class SourceImage:                          # reconstruction.rs:74-81
                            focal_length_35mm)
 
     @staticmethod
+    def _load_jpeg_on_device(path, focal_length_35mm, size, resampler, ctx) -> "SourceImage":
+        import io
+        from PIL import Image
+        if ctx is None:
+            raise ReconstructionError("Failed to load source image: the device JPEG decoder needs a context")
+        try:
+            with open(path, "rb") as f:
+                data = f.read()
+            ctx = ctx() if callable(ctx) else ctx
+            width, height, _, _ = ctx.jpeg_info(data)
+            orientation = 1
+            try:                                  # header only: Pillow parses the EXIF block, not the scans
+                head = Image.open(io.BytesIO(data))
+                if focal_length_35mm is None:
+                    focal_length_35mm = SourceImage.get_focal_length_35mm(head)
+                orientation = int(head.getexif().get(0x0112, 1))
+            except Exception:
+                pass
+            if not 1 <= orientation <= 8:
+                orientation = 1
+            original_size = (height, width) if orientation >= 5 else (width, height)
+            if resampler == "device":
+                rgb = ctx.decode_jpeg_resized(data, (size, size), orientation)      # :95-113 in one call
+            else:
+                img = Image.fromarray(ctx.decode_jpeg(data, orientation))
+                if img.size != (size, size):
+                    img = img.resize((size, size), Image.LANCZOS)
+                rgb = np.ascontiguousarray(np.asarray(img, dtype=np.uint8))
+        except ReconstructionError:
+            raise
+        except Exception as err:
+            raise ReconstructionError(f"Failed to load source image: {err}") from err
+        return SourceImage(rgb, original_size, focal_length_35mm)
+
+    @staticmethod
     def get_focal_length_35mm(img) -> Optional[float]:
         """reconstruction.rs:133-143"""
         try:
@@ -79,13 +118,15 @@ class SourceImage:                          # reconstruction.rs:74-81
 
 def extract_depth(device: int, model_loader: DepthProModelLoader, source_path: str, destination_path: str,
                   focal_length_35mm: Optional[float], image_format: ImageOutputFormat,
-                  vertex_mode: VertexMode, progress=None, noise=None, resampler=None) -> None:
-    """reconstruction.rs:155-205.  resampler: depth_pro.resolve_resampler, passed down to every resize"""
+                  vertex_mode: VertexMode, progress=None, noise=None, resampler=None, jpeg_decoder=None) -> None:
+    """reconstruction.rs:155-205.  resampler: depth_pro.resolve_resampler, passed down to every resize; jpeg_decoder:
+    depth_pro.resolve_jpeg_decoder, for the source photo"""
     resampler = resolve_resampler(resampler)
+    jpeg_decoder = resolve_jpeg_decoder(jpeg_decoder)
     dtype = os.environ.get("MATRIX_EYES_DTYPE", "f16")   # f16 | bf16 | fp8, as the C++ twin
     try:
         img = SourceImage.load(source_path, focal_length_35mm, model_loader.cfg.img_size, resampler=resampler,
-                               ctx=lambda: model_loader.context(device, dtype))
+                               ctx=lambda: model_loader.context(device, dtype), jpeg_decoder=jpeg_decoder)
     except ReconstructionError as err:
         print(err, file=sys.stderr)
         raise
