@@ -357,6 +357,23 @@ int32_t me_jpeg_decode_resized_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nb
    coefficients, [2] jpeg_idct_kernel, [3] jpeg_finish_kernel, [4] download to a host rgb (0 for a device one); [1]..[4]
    are HIP event times.  Synchronises the context's stream. */
 int32_t me_last_jpeg_timing(me_ctx* ctx, double ms_out[5]);
+/* Where me_jpeg_decode_rgb8 / me_jpeg_decode_resized_rgb8 decode the entropy-coded data: 0 (the default) on the host, as
+   described above; 1 on the device (csrc/jpeg_entropy.hip): the scan's bytes go up instead of the coefficients and are
+   Huffman-decoded by one thread per subsequence of bits, with the host decoder's coefficients integer for integer, so the
+   picture's bytes do not change.  The device decoder takes sequential files (SOF0 / SOF1) with ONE scan that holds all
+   components, prefix-code Huffman tables, DC categories up to 15, no marker but RSTn inside the scan and all the RSTn the
+   restart interval needs; progressive and multi-scan files, and a file whose true chain meets an invalid code, a run past
+   coefficient 63, a segment that ends early or no synchronisation within 65536 bits, are DECLINED: the host decoder then
+   runs whole, so the picture or the refusal is the host's either way.  Any other mode is ME_ERR_BAD_ARG. */
+int32_t me_ctx_set_jpeg_entropy(me_ctx* ctx, int32_t mode);
+/* The entropy leg of the context's last JPEG decode.  report: [0] where the coefficients were made (0 host, 1 device),
+   [1] why the device declined (0: it did not, or was not asked; 1 progressive, 2 scans, 3 Huffman table not a prefix code,
+   4 DC value above 15, 5 marker inside the scan, 6 too few RSTn, 7 MCU / scan too large, 8 the planner refused the file,
+   10 invalid code, 11 run past 63, 12 no synchronisation, 13 segment ends early), [2] segments (restart intervals),
+   [3] subsequences, [4] bits per subsequence, [5] synchronisation rounds, the confirming one included, [6] bytes uploaded,
+   [7] workgroups of each entropy kernel.  ms: [0] marker scan and destuffing on the host (wall clock), [1] upload,
+   [2] entropy kernels with the looks at their changed counts (HIP events). */
+int32_t me_last_jpeg_entropy(me_ctx* ctx, int64_t report[8], double ms[3]);
 
 /* output.rs:264-363 IndexedMesh::new + for_each_face + remap_face.
    depth [height,width] (DepthMap.data, stride `width`).  vertex_index [height*width]: the

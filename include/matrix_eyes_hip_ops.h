@@ -215,6 +215,18 @@ int64_t me_op_lanczos3_table(int32_t len_in, int32_t len_out, int32_t* left, int
    yardstick me_jpeg_decode_rgb8 is measured against in the same process (tools/bench_jpeg.py).  HOST arrays only, no
    context, no GPU; rgb [h,w,3].  0, or < 0 on a null pointer, a size that does not match or a file the decoder refuses. */
 int32_t me_op_jpeg_decode_host(const uint8_t* file, int64_t nbytes, uint8_t* rgb, int32_t w, int32_t h);
+/* The quantised DCT coefficients of a JPEG file as the host decoder makes them (decode_jpeg_coefficients): all components
+   one after the other, natural order, `count` int16_t in all (the layout jpeg_idct_kernel reads).  HOST arrays only, no
+   context, no GPU.  0, or < 0 on a null pointer (-1), a count that does not match (-2) or a file the decoder refuses (-3). */
+int32_t me_op_jpeg_coefficients_host(const uint8_t* file, int64_t nbytes, int16_t* coef, int64_t count);
+/* The same coefficients from the device entropy decoder (csrc/jpeg_entropy.hip) on its own, whatever
+   me_ctx_set_jpeg_entropy says; coef a host or device pointer.  subseq_bits: bits per subsequence, a multiple of 32 in
+   [64, 65536], 0 for the default (1024): small values make small pictures span many subsequences and workgroups.  A file
+   the device decoder declines returns ME_OP_JPEG_ENTROPY_DECLINED (me_last_jpeg_entropy says why) and writes nothing:
+   there is no fallback inside this call. */
+#define ME_OP_JPEG_ENTROPY_DECLINED 100
+int32_t me_op_jpeg_entropy(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t subseq_bits, int16_t* coef,
+                           int64_t count);
 /* Names of the GEMM tile configurations (for reports). */
 int32_t me_op_gemm_config_count(void);
 const char* me_op_gemm_config_name(int32_t cfg);

@@ -75,6 +75,12 @@ impl HipDevice {
         Ok(out)
     }
 
+    /// Where `decode_jpeg_resized` runs the Huffman decoding: `false` (the default) on the host, `true` on the GPU
+    /// (`me_ctx_set_jpeg_entropy`; sequential single-scan files -- anything else falls back to the host loop).  The same pixels.
+    pub fn set_jpeg_entropy_on_device(&self, on: bool) -> Result<(), HipError> {
+        self.check(unsafe { ffi::me_ctx_set_jpeg_entropy(self.ctx, on as i32) })
+    }
+
     /// (width, height, exif_offset, exif_len) of a JPEG file: the size as coded and where its TIFF-structured EXIF block
     /// lies in `file` (0, 0: none) -- hand that slice to `exif::Reader::read_raw`.  No GPU work.
     pub fn jpeg_info(file: &[u8]) -> Result<(u32, u32, usize, usize), HipError> {

@@ -84,6 +84,8 @@ SIGNATURES = {
     "me_jpeg_decode_rgb8": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32]),
     "me_jpeg_decode_resized_rgb8": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32]),
     "me_last_jpeg_timing": (_i32, [_vp, C.POINTER(C.c_double)]),
+    "me_ctx_set_jpeg_entropy": (_i32, [_vp, _i32]),
+    "me_last_jpeg_entropy": (_i32, [_vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
     "me_png_encode_rgb8": (_i32, [_vp, _vp, _i32, _i32, C.POINTER(_vp), C.POINTER(_i64)]),
     "me_output_png": (_i32, [_vp, _vp, _i32, _i32, C.c_char_p]),
     "me_output_depth_map_png": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _vp, _i32, _i32, C.c_char_p]),
@@ -148,6 +150,8 @@ SIGNATURES = {
     "me_profile_report": (_i32, [_vp, C.c_char_p, _i64]),
     "me_op_lanczos3_table": (_i64, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32), _i64]),
     "me_op_jpeg_decode_host": (_i32, [_vp, _i64, _vp, _i32, _i32]),
+    "me_op_jpeg_coefficients_host": (_i32, [_vp, _i64, _vp, _i64]),
+    "me_op_jpeg_entropy": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64]),
     "me_op_gemm_config_count": (_i32, []),
     "me_op_gemm_config_name": (C.c_char_p, [_i32]),
 }

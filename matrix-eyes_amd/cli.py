@@ -116,7 +116,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     except UsageExit as e:
         return int(e.code)
     from ._lib import MatrixEyesError
-    from .depth_pro import DepthProModelLoader, resolve_jpeg_decoder, resolve_png_encoder, resolve_resampler
+    from .depth_pro import (DepthProModelLoader, resolve_jpeg_decoder, resolve_jpeg_entropy, resolve_png_encoder,
+                            resolve_resampler)
     from .reconstruction import extract_depth
     try:
         resolve_resampler()                  # MATRIX_EYES_RESAMPLER = pillow | device
@@ -132,6 +133,11 @@ def main(argv: Optional[List[str]] = None) -> int:
         resolve_jpeg_decoder()               # MATRIX_EYES_JPEG_DECODER = pillow | host | device
     except MatrixEyesError as err:
         print(f"MATRIX_EYES_JPEG_DECODER: {err.message}", file=sys.stderr)
+        return 2
+    try:
+        resolve_jpeg_entropy()               # MATRIX_EYES_JPEG_ENTROPY = host | device
+    except MatrixEyesError as err:
+        print(f"MATRIX_EYES_JPEG_ENTROPY: {err.message}", file=sys.stderr)
         return 2
     import os
     from .config import ModelConfig

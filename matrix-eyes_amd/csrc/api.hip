@@ -1079,6 +1079,57 @@ int32_t me_last_jpeg_timing(me_ctx* ctx, double ms_out[5]) {
     ME_API_END(ctx)
 }
 
+int32_t me_ctx_set_jpeg_entropy(me_ctx* ctx, int32_t mode) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(mode == 0 || mode == 1, ME_ERR_BAD_ARG, "me_ctx_set_jpeg_entropy: mode %d (0 host, 1 device)", mode);
+    ctx->jpeg_entropy_mode = mode;
+    ME_API_END(ctx)
+}
+
+int32_t me_last_jpeg_entropy(me_ctx* ctx, int64_t report[8], double ms[3]) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(report && ms, ME_ERR_BAD_ARG, "me_last_jpeg_entropy: null pointer");
+    ME_CHECK(ctx->jpeg_timed || ctx->jpeg_entropy_reported, ME_ERR_NOT_READY,
+             "me_last_jpeg_entropy: no JPEG decode has completed on this context");
+    // a decode that never tried the device (mode 0) reports the host, with nothing else to say
+    const JpegEntropyReport r = ctx->jpeg_entropy_reported ? ctx->jpeg_entropy_report : JpegEntropyReport();
+    report[0] = r.where, report[1] = r.reason, report[2] = r.segments, report[3] = r.subseqs, report[4] = r.subseq_bits;
+    report[5] = r.rounds, report[6] = r.upload_bytes, report[7] = r.workgroups;
+    for (int i = 0; i < 3; ++i) ms[i] = r.ms[i];
+    ME_API_END(ctx)
+}
+
+int32_t me_op_jpeg_entropy(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t subseq_bits, int16_t* coef,
+                           int64_t count) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(file && coef && nbytes >= 0, ME_ERR_BAD_ARG, "me_op_jpeg_entropy: null pointer");
+    ME_CHECK(!is_device_ptr(file), ME_ERR_BAD_ARG, "me_op_jpeg_entropy: the file's bytes must be in host memory");
+    const std::vector<uint8_t> bytes(file, file + nbytes);
+    matrix_eyes::JpegEntropyPlan plan;
+    if (!jpeg_entropy_decode(ctx, bytes, subseq_bits, plan)) {
+        ctx->last_error = "me_op_jpeg_entropy: declined, reason " + std::to_string(ctx->jpeg_entropy_report.reason) +
+                          (plan.why.empty() ? "" : " (" + plan.why + ")");
+        return ME_OP_JPEG_ENTROPY_DECLINED;
+    }
+    ME_CHECK(count == (int64_t)plan.frame.total_coefs, ME_ERR_BAD_SHAPE, "me_op_jpeg_entropy: the file has %zu coefficients, not %lld",
+             plan.frame.total_coefs, (long long)count);
+    from_device(ctx, coef, site_buf(ctx, "jpeg.coef", (size_t)count * sizeof(int16_t)), (size_t)count * sizeof(int16_t));
+    ME_API_END(ctx)
+}
+
+int32_t me_op_jpeg_coefficients_host(const uint8_t* file, int64_t nbytes, int16_t* coef, int64_t count) {
+    if (!file || nbytes < 0 || !coef) return -1;
+    try {
+        const std::vector<uint8_t> bytes(file, file + nbytes);
+        const matrix_eyes::JpegCoefficients c = matrix_eyes::decode_jpeg_coefficients(bytes, "<jpeg>");
+        if ((int64_t)c.total_coefs != count) return -2;
+        std::memcpy(coef, c.comps[0].coef, (size_t)count * sizeof(int16_t));
+    } catch (const std::exception&) {
+        return -3;
+    }
+    return 0;
+}
+
 int32_t me_depthmap_rgb_resized(me_ctx* ctx, const float* depth, int32_t data_width, int32_t data_height,
                                 float min_depth, float max_depth, const float* minmax_dev, int32_t out_w,
                                 int32_t out_h, uint8_t* rgb) {

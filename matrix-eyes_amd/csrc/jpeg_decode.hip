@@ -7,6 +7,8 @@
 //                       the DC-only vote, row pass, column pass through LDS, level shift, clamp)
 //   jpeg_finish_kernel  planes -> oriented RGB: chroma upsampling, colour conversion and the orientation as a remap of the
 //                       store address, one pass over the output pixels
+// With me_ctx_set_jpeg_entropy(ctx, 1) the scan's bytes go up instead and the coefficients are made on the device
+// (jpeg_entropy.hip); a file that decoder declines takes the host path above, whole.
 // The arithmetic is jpeg_recon.h's, shared with the host driver of the CPU tests; this unit is compiled with contraction off
 // (pragma below and the Makefile rule) as resample.hip is: a fused multiply-add in the IDCT changes bytes.  The IDCT basis
 // comes from the one host function both decoders use (jpeg_basis.cpp) -- no device cos.  HBM-side kernels, no MFMA.
@@ -116,6 +118,10 @@ __global__ __launch_bounds__(256) void jpeg_finish_kernel(const Frame f, const u
 // pinned memory for the entropy decoder (JpegCoefAlloc): the upload of the call before may still be reading the buffer
 int16_t* pinned_coefficients(void* user, size_t count) {
     me_ctx* ctx = (me_ctx*)user;
+    if (!ctx->jpeg_uploaded) {
+        ME_HIP(hipEventCreateWithFlags(&ctx->jpeg_uploaded, hipEventDisableTiming));
+        for (hipEvent_t& e : ctx->jpeg_ev) ME_HIP(hipEventCreate(&e));
+    }
     if (ctx->jpeg_upload_pending) {
         ME_HIP(hipEventSynchronize(ctx->jpeg_uploaded));
         ctx->jpeg_upload_pending = false;
@@ -161,7 +167,10 @@ void plan(const matrix_eyes::JpegCoefficients& c, int32_t orientation, Frame& f,
 
 }  // namespace
 
+int16_t* jpeg_pinned_buffer(me_ctx* ctx, size_t count) { return pinned_coefficients(ctx, count); }
+
 void free_jpeg_scratch(me_ctx* ctx) {
+    free_jpeg_entropy_scratch(ctx);
     if (ctx->jpeg_pinned) (void)hipHostFree(ctx->jpeg_pinned);
     ctx->jpeg_pinned = nullptr, ctx->jpeg_pinned_count = 0;
     if (ctx->jpeg_uploaded) (void)hipEventDestroy(ctx->jpeg_uploaded);
@@ -177,12 +186,9 @@ uint8_t* jpeg_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int3
     const std::string name = "<jpeg>";
     const std::vector<uint8_t> bytes(file, file + nbytes);
     hipStream_t s = ctx->stream;
-    if (!ctx->jpeg_uploaded) {
-        ME_HIP(hipEventCreateWithFlags(&ctx->jpeg_uploaded, hipEventDisableTiming));
-        for (hipEvent_t& e : ctx->jpeg_ev) ME_HIP(hipEventCreate(&e));
-    }
     ctx->jpeg_timed = false;
     matrix_eyes::JpegCoefficients c;
+    bool on_device = false;  // the coefficients are in "jpeg.coef" already (jpeg_entropy.hip)
     try {
         // the size first: a caller's buffer of another size is refused before any decoding
         const matrix_eyes::JpegCoefficients head = matrix_eyes::parse_jpeg_header(bytes, name);
@@ -192,7 +198,14 @@ uint8_t* jpeg_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int3
                  "JPEG decode: the picture is %dx%d (orientation %d), the destination %dx%d", *ow, *oh, orientation, want_w,
                  want_h);
         const auto t0 = std::chrono::steady_clock::now();
-        c = matrix_eyes::decode_jpeg_coefficients(bytes, name, pinned_coefficients, ctx);
+        ctx->jpeg_entropy_reported = false;
+        if (ctx->jpeg_entropy_mode == 1) {
+            // a decline judges nothing: the host decoder below runs whole, and its pixels or its words stand
+            matrix_eyes::JpegEntropyPlan entropy;
+            on_device = jpeg_entropy_decode(ctx, bytes, 0, entropy);
+            if (on_device) c = std::move(entropy.frame);
+        }
+        if (!on_device) c = matrix_eyes::decode_jpeg_coefficients(bytes, name, pinned_coefficients, ctx);
         ctx->jpeg_entropy_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         matrix_eyes::check_jpeg_reconstructible(c, name);
     } catch (const matrix_eyes::ImageError& err) {
@@ -208,9 +221,11 @@ uint8_t* jpeg_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int3
     if (!dst_dev) dst_dev = (uint8_t*)site_buf(ctx, "jpeg.rgb", (size_t)f.width * f.height * 3);
 
     ME_HIP(hipEventRecord(ctx->jpeg_ev[0], s));
-    ME_HIP(hipMemcpyAsync(coef, c.comps[0].coef, c.total_coefs * sizeof(int16_t), hipMemcpyHostToDevice, s));
-    ME_HIP(hipEventRecord(ctx->jpeg_uploaded, s));
-    ctx->jpeg_upload_pending = true;
+    if (!on_device) {
+        ME_HIP(hipMemcpyAsync(coef, c.comps[0].coef, c.total_coefs * sizeof(int16_t), hipMemcpyHostToDevice, s));
+        ME_HIP(hipEventRecord(ctx->jpeg_uploaded, s));
+        ctx->jpeg_upload_pending = true;
+    }
     ME_HIP(hipEventRecord(ctx->jpeg_ev[1], s));
 
     const int nchunks = (int)cdiv(f.total_blocks, kIdctChunk);

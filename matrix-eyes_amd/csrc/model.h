@@ -5,6 +5,7 @@
 #include <thread>
 #include <vector>
 
+#include "../host/image_io.hpp"
 #include "common.h"
 
 namespace me {
@@ -124,6 +125,17 @@ struct ResampleTable {
 }  // namespace me
 
 // The opaque C handle.
+// me_last_jpeg_entropy: the last attempt at decoding a JPEG scan on the device (jpeg_entropy.hip)
+struct JpegEntropyReport {
+    int64_t where = 0;          // 0: the host decoder made the coefficients, 1: the device
+    int64_t reason = 0;         // matrix_eyes::JpegEntropyDecline when where == 0 after an attempt
+    int64_t segments = 0, subseqs = 0, subseq_bits = 0;
+    int64_t rounds = 0;         // sync rounds, the confirming one included
+    int64_t upload_bytes = 0;
+    int64_t workgroups = 0;     // of each entropy kernel
+    double ms[3] = {0, 0, 0};   // host marker scan and destuffing (wall clock), upload, entropy kernels (HIP events)
+};
+
 struct me_ctx {
     int device = 0;
     int32_t dtype = ME_DTYPE_F16;
@@ -248,6 +260,13 @@ struct me_ctx {
     hipEvent_t jpeg_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool jpeg_timed = false, jpeg_timed_download = false;
     double jpeg_entropy_ms = 0.0;
+    // The entropy leg on the device (jpeg_entropy.hip; me_ctx_set_jpeg_entropy): 0 host, 1 device.  The report of the last
+    // attempt (me_last_jpeg_entropy), the marks around its upload and kernels, and the pinned words its status comes back in.
+    int32_t jpeg_entropy_mode = 0;
+    JpegEntropyReport jpeg_entropy_report;
+    bool jpeg_entropy_reported = false;
+    hipEvent_t jpeg_entropy_ev[3] = {nullptr, nullptr, nullptr};
+    int32_t* jpeg_entropy_status = nullptr;
 
     // The whole extract_depth step as one hipGraph (shapes are static per batch size).  A call whose pointers
     // all live on the device and that needs no host callback is enqueued eagerly the first time it is seen,
@@ -380,6 +399,13 @@ void free_resample_tables(me_ctx* ctx);
 uint8_t* jpeg_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t orientation, uint8_t* dst_dev,
                           int32_t want_w, int32_t want_h, int32_t* ow, int32_t* oh);
 void free_jpeg_scratch(me_ctx* ctx);
+// the context's pinned staging buffer of `count` int16_t, once the upload of the call before has left it
+int16_t* jpeg_pinned_buffer(me_ctx* ctx, size_t count);
+// jpeg_entropy.hip: the scan's coefficients made on the device, into the "jpeg.coef" buffer.  subseq_bits 0: the default.
+// False: declined (ctx->jpeg_entropy_report.reason), the host decoder is to run.
+bool jpeg_entropy_decode(me_ctx* ctx, const std::vector<uint8_t>& file, int32_t subseq_bits,
+                         matrix_eyes::JpegEntropyPlan& plan);
+void free_jpeg_entropy_scratch(me_ctx* ctx);
 
 // calibrate.hip: the two fixed loops of bench.py's calibration leg (out[6])
 void calibrate(me_ctx* ctx, double* out);

@@ -87,6 +87,21 @@ def resolve_jpeg_decoder(jpeg_decoder=None) -> str:
     return "pillow" if value == "host" else value
 
 
+JPEG_ENTROPIES = ("host", "device")
+
+
+def resolve_jpeg_entropy(jpeg_entropy=None) -> str:
+    """Where the device JPEG decoder decodes the entropy-coded data: "host" (the default: the host decoder's loop on one
+    core, the coefficients uploaded) or "device" (me_ctx_set_jpeg_entropy(ctx, 1): the scan's bytes uploaded and
+    Huffman-decoded on the GPU; a file that decoder declines -- progressive, several scans, damaged -- takes the host loop).
+    The same bytes either way.  Acts only with jpeg_decoder "device".  None reads MATRIX_EYES_JPEG_ENTROPY; anything but
+    the two names is an argument error."""
+    value = os.environ.get("MATRIX_EYES_JPEG_ENTROPY", "host") if jpeg_entropy is None else jpeg_entropy
+    if value not in JPEG_ENTROPIES:
+        raise L.MatrixEyesError(1, f"jpeg entropy decoder {value!r}: expected one of {', '.join(JPEG_ENTROPIES)}")
+    return value
+
+
 class Context:
     """One GPU: stream, packed weights, workspaces (`me_ctx`)."""
 
@@ -345,6 +360,20 @@ class Context:
         po, out = _out(out, (nh, nw, 3), np.uint8)
         self._check(self.lib.me_jpeg_decode_resized_rgb8(self._h, data, len(data), int(orientation), po, nw, nh))
         return out
+
+    def set_jpeg_entropy(self, where: str) -> None:
+        """resolve_jpeg_entropy's "host" / "device" for this context's JPEG decodes (me_ctx_set_jpeg_entropy)"""
+        self._check(self.lib.me_ctx_set_jpeg_entropy(self._h, 1 if resolve_jpeg_entropy(where) == "device" else 0))
+
+    def last_jpeg_entropy(self):
+        """(report, ms) of me_last_jpeg_entropy: report a dict of where ("host" / "device"), reason, segments, subseqs,
+        subseq_bits, rounds, upload_bytes, workgroups; ms (marker scan, upload, entropy kernels)"""
+        rep, ms = (C.c_int64 * 8)(), (C.c_double * 3)()
+        self._check(self.lib.me_last_jpeg_entropy(self._h, rep, ms))
+        names = ("where", "reason", "segments", "subseqs", "subseq_bits", "rounds", "upload_bytes", "workgroups")
+        out = dict(zip(names, (int(v) for v in rep)))
+        out["where"] = "device" if out["where"] == 1 else "host"
+        return out, tuple(float(v) for v in ms)
 
     def last_jpeg_timing(self):
         """[entropy decode (host), upload, IDCT kernel, finish kernel, download] of the last decode, in ms"""

@@ -67,6 +67,52 @@ JpegCoefficients decode_jpeg_coefficients(const std::vector<uint8_t>& file, cons
                                           JpegCoefAlloc alloc = nullptr, void* alloc_user = nullptr);
 // frame header and EXIF span only (no entropy decoding); comps carry no coefficients
 JpegCoefficients parse_jpeg_header(const std::vector<uint8_t>& file, const std::string& path);
+// What the device entropy decoder (csrc/jpeg_entropy.h) needs of a file, and whether it may take it: parse() with the
+// entropy loops skipped.  `frame` is parse_jpeg_header's struct with the FINAL quantisation tables (a DQT behind the scan
+// counts, as in the host decoder, whose reconstruction runs after the whole file is parsed).  A file is eligible when the
+// frame is SOF0 / SOF1, its one scan holds all frame components, every Huffman table the scan uses is a prefix code
+// (Kraft sum <= 1) whose DC values are at most 15, no marker but RSTn stands inside the scan and there are as many RSTn
+// as the restart interval needs; everything else (progressive files, several scans, ...) declines with a reason and is
+// decoded by decode_jpeg_coefficients.  Throws ImageError where parse() does outside the entropy-coded data.
+enum JpegEntropyDecline : int {
+    kJpegEntropyOk = 0,
+    kJpegDeclineProgressive = 1,   // SOF2
+    kJpegDeclineScans = 2,         // no scan, several scans, or a scan without all frame components
+    kJpegDeclineHuffman = 3,       // a table of the scan is not a prefix code (Kraft sum > 1)
+    kJpegDeclineDcValue = 4,       // a DC table of the scan holds a value above 15
+    kJpegDeclineMarker = 5,        // a marker other than RSTn (or a fill byte) inside the scan
+    kJpegDeclineRestarts = 6,      // fewer RSTn than the restart interval needs
+    kJpegDeclineLayout = 7,        // more than 10 blocks per MCU, or a scan of 2^28 bytes and more
+    kJpegDeclineHostError = 8,     // the planner itself refused the file: the host decoder says why
+    // at run time, through the device decoder's status word (csrc/jpeg_entropy.h)
+    kJpegDeclineBadCode = 10,      // the true chain met an invalid Huffman code
+    kJpegDeclineBadRun = 11,       // ... or an AC run past coefficient 63
+    kJpegDeclineNoSync = 12,       // no synchronisation within the give-up distance
+    kJpegDeclineShort = 13         // a segment ends before its MCUs do (the host decoder reads zeros there)
+};
+struct JpegHuffmanSpec {
+    bool present = false;
+    uint8_t counts[16] = {};       // codes of length 1..16
+    uint8_t values[256] = {};
+    int nvalues = 0;
+};
+struct JpegEntropyPlan {
+    JpegCoefficients frame;        // geometry, final tables, EXIF span; comps carry no coefficients
+    bool eligible = false;
+    int reason = kJpegEntropyOk;   // JpegEntropyDecline
+    std::string why;               // the reason in words ("progressive", ...)
+    int restart_interval = 0;      // MCUs (0: none), as in force at the scan
+    int mcus_x = 0, mcus_y = 0;
+    int scan_comps = 0;            // components of the scan, in its order:
+    int scan_comp[3] = {0, 0, 0};  //   index into frame.comps
+    int scan_td[3] = {0, 0, 0}, scan_ta[3] = {0, 0, 0};
+    JpegHuffmanSpec dc[4], ac[4];  // as in force at the scan
+    size_t scan_begin = 0, scan_end = 0;   // the entropy-coded data: file[scan_begin, scan_end), stuffing and RSTn included
+    // segment j: file[seg_begin[j], seg_end[j]) -- from behind the j-th RSTn (the scan's start for j = 0) to the first
+    // marker, whatever the RSTn's numbers; only the segments the MCU count needs
+    std::vector<size_t> seg_begin, seg_end;
+};
+JpegEntropyPlan plan_jpeg_entropy(const std::vector<uint8_t>& file, const std::string& path);
 // the refusals of the reconstruction, in its order and with its words: an undefined quantisation table, fractional
 // sampling ratios.  Throws ImageError.
 void check_jpeg_reconstructible(const JpegCoefficients& c, const std::string& path);

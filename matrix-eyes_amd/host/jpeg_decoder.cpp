@@ -22,9 +22,13 @@ const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18,
 struct HuffTable {
     bool present = false;
     uint8_t values[256];
+    uint8_t counts[16];
+    int nvalues = 0;
     int mincode[17], maxcode[18], valptr[17];
-    void build(const uint8_t counts[16], const uint8_t* vals, int nvals) {
+    void build(const uint8_t cnt[16], const uint8_t* vals, int nvals) {
         std::memcpy(values, vals, (size_t)nvals);
+        std::memcpy(counts, cnt, 16);
+        nvalues = nvals;
         int code = 0, k = 0;
         for (int len = 1; len <= 16; ++len) {
             valptr[len] = k;
@@ -126,6 +130,8 @@ struct Decoder {
     void* alloc_user = nullptr;
     std::vector<int16_t> coef_store;
     size_t total_coefs = 0;
+    JpegEntropyPlan* plan = nullptr;          // plan_jpeg_entropy: the scans are walked for their markers, not decoded
+    int scans_seen = 0;
 
     Decoder(const std::vector<uint8_t>& f, const std::string& p) : file(f), path(p) {}
 
@@ -190,7 +196,7 @@ struct Decoder {
             c.blocks_w = mcus_x * c.h, c.blocks_h = mcus_y * c.v;
             total_coefs += (size_t)c.blocks_w * c.blocks_h * 64;
         }
-        if (!header_only) {
+        if (!header_only && !plan) {
             int16_t* base;
             if (alloc) {
                 base = alloc(alloc_user, total_coefs);
@@ -382,7 +388,89 @@ struct Decoder {
             const bool need_dc = !progressive || (sc.ss == 0 && sc.ah == 0), need_ac = !progressive || sc.ss > 0;
             if ((need_dc && !dc[c.td].present) || (need_ac && !ac[c.ta].present)) fail("scan uses an undefined Huffman table");
         }
-        return decode_scan(end, sc);
+        return plan ? plan_scan(end, sc) : decode_scan(end, sc);
+    }
+
+    // plan_jpeg_entropy's stand-in for decode_scan: one pass over the scan's bytes for 0xFF.  Segment j runs from behind
+    // the j-th RSTn to the first marker (BitReader::fill reads zeros from there on, and restart() walks on to the next
+    // RSTn, whatever its number); the scan ends where decode_scan says it does, at the first marker that is neither.
+    size_t plan_scan(size_t pos, const Scan& sc) {
+        const bool first = scans_seen++ == 0;
+        const uint8_t* base = file.data();
+        const size_t n = file.size();
+        std::vector<size_t> begin{pos}, stop;
+        bool open = true, fill_bytes = false;
+        size_t p = pos;
+        while (p < n) {
+            const void* q = std::memchr(base + p, 0xff, n - p);
+            if (!q) {
+                p = n;
+                break;
+            }
+            p = (size_t)((const uint8_t*)q - base);
+            const int m = p + 1 < n ? base[p + 1] : -1;
+            if (m == 0x00) {
+                p += 2;
+                continue;
+            }
+            if (open) stop.push_back(p), open = false;  // any other 0xFF ends the segment's data
+            if (m >= 0xd0 && m <= 0xd7) {
+                p += 2;
+                begin.push_back(p), open = true;
+                continue;
+            }
+            if (m == 0xff) {
+                fill_bytes = true, ++p;
+                continue;
+            }
+            if (m < 0) p = n;
+            break;
+        }
+        if (open) stop.push_back(std::min(p, n));
+        if (first) {
+            JpegEntropyPlan& o = *plan;
+            o.restart_interval = restart_interval;
+            o.mcus_x = (width + 8 * hmax - 1) / (8 * hmax), o.mcus_y = (height + 8 * vmax - 1) / (8 * vmax);
+            o.scan_comps = (int)sc.comp.size();
+            int blocks = 0;
+            for (size_t i = 0; i < sc.comp.size() && i < 3; ++i) {
+                const Component& c = comps[(size_t)sc.comp[i]];
+                o.scan_comp[i] = sc.comp[i], o.scan_td[i] = c.td, o.scan_ta[i] = c.ta;
+                blocks += c.h * c.v;
+            }
+            auto spec = [](const HuffTable& t, JpegHuffmanSpec& s) {
+                s.present = t.present;
+                if (!t.present) return;
+                std::memcpy(s.counts, t.counts, 16);
+                s.nvalues = t.nvalues;
+                std::memcpy(s.values, t.values, (size_t)t.nvalues);
+            };
+            for (int i = 0; i < 4; ++i) spec(dc[i], o.dc[i]), spec(ac[i], o.ac[i]);
+            o.scan_begin = pos, o.scan_end = p;
+            const int64_t mcus = (int64_t)o.mcus_x * o.mcus_y;
+            const size_t need = restart_interval ? (size_t)((mcus + restart_interval - 1) / restart_interval) : 1;
+            auto decline = [&](int reason, const char* why) {
+                if (o.reason == kJpegEntropyOk) o.reason = reason, o.why = why;
+            };
+            if (progressive) decline(kJpegDeclineProgressive, "progressive");
+            if (sc.comp.size() != comps.size()) decline(kJpegDeclineScans, "the scan does not hold all frame components");
+            for (size_t i = 0; i < sc.comp.size() && !progressive; ++i) {
+                const JpegHuffmanSpec* used[2] = {&o.dc[o.scan_td[i]], &o.ac[o.scan_ta[i]]};
+                for (int k = 0; k < 2; ++k) {
+                    uint32_t kraft = 0;  // in units of 2^-16
+                    for (int len = 1; len <= 16; ++len) kraft += (uint32_t)used[k]->counts[len - 1] << (16 - len);
+                    if (kraft > 65536) decline(kJpegDeclineHuffman, "a Huffman table is not a prefix code");
+                }
+                for (int v = 0; v < used[0]->nvalues; ++v)
+                    if (used[0]->values[v] > 15) decline(kJpegDeclineDcValue, "a DC table holds a value above 15");
+            }
+            if (fill_bytes) decline(kJpegDeclineMarker, "a marker other than RSTn inside the scan");
+            if (begin.size() < need) decline(kJpegDeclineRestarts, "fewer RSTn than the restart interval needs");
+            if (blocks > 10 || p - pos >= ((size_t)1 << 28)) decline(kJpegDeclineLayout, "MCU or scan too large");
+            begin.resize(std::min(begin.size(), need)), stop.resize(begin.size());
+            o.seg_begin = std::move(begin), o.seg_end = std::move(stop);
+        }
+        return p;
     }
 
     // ---- reconstruction -------------------------------------------------------------------------------
@@ -613,6 +701,18 @@ JpegCoefficients parse_jpeg_header(const std::vector<uint8_t>& file, const std::
 }
 
 // what Decoder::finish refuses, in its order: idct_all per component, then upsample per component
+JpegEntropyPlan plan_jpeg_entropy(const std::vector<uint8_t>& file, const std::string& path) {
+    JpegEntropyPlan out;
+    Decoder d(file, path);
+    d.plan = &out;
+    d.parse();
+    out.frame = d.coefficients();
+    if (d.scans_seen != 1 && out.reason == kJpegEntropyOk)
+        out.reason = kJpegDeclineScans, out.why = d.scans_seen ? "more than one scan" : "no scan";
+    out.eligible = out.reason == kJpegEntropyOk;
+    return out;
+}
+
 void check_jpeg_reconstructible(const JpegCoefficients& c, const std::string& path) {
     for (const JpegComponent& k : c.comps)
         if (!c.qt_present[k.tq]) throw ImageError(path + ": component uses an undefined quantisation table");

@@ -70,6 +70,13 @@ Device::Device() {
         else if (std::strcmp(jd, "host") != 0)
             throw ModelError(ME_ERR_BAD_ARG, std::string("MATRIX_EYES_JPEG_DECODER=") + jd + ": expected host or device");
     }
+    bool device_jpeg_entropy = false;  // acts only behind MATRIX_EYES_JPEG_DECODER=device: the host decoder has one entropy loop
+    if (const char* je = std::getenv("MATRIX_EYES_JPEG_ENTROPY")) {
+        if (std::strcmp(je, "device") == 0)
+            device_jpeg_entropy = true;
+        else if (std::strcmp(je, "host") != 0)
+            throw ModelError(ME_ERR_BAD_ARG, std::string("MATRIX_EYES_JPEG_ENTROPY=") + je + ": expected host or device");
+    }
     me_model_config cfg;
     me_default_config(&cfg);
     if (model && std::strcmp(model, "tiny") == 0) {
@@ -83,6 +90,7 @@ Device::Device() {
     const int32_t rc = me_ctx_create(dev ? std::atoi(dev) : 0, dtype,
                                      &cfg, &ctx_);
     if (rc != ME_OK) throw ModelError(rc, std::string("cannot initialise the HIP device: ") + me_last_error(nullptr));
+    if (device_jpeg_entropy && me_ctx_set_jpeg_entropy(ctx_, 1) != ME_OK) throw ModelError(ME_ERR_BAD_ARG, me_last_error(ctx_));
 }
 
 Device::~Device() {

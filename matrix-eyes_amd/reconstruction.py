@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from .depth_pro import IMG_SIZE, DepthProModelLoader, resolve_jpeg_decoder, resolve_resampler
+from .depth_pro import IMG_SIZE, DepthProModelLoader, resolve_jpeg_decoder, resolve_jpeg_entropy, resolve_resampler
 from .output import DepthMap, ImageOutputFormat, VertexMode
 
 _EXIF_IFD = 0x8769
@@ -31,16 +31,18 @@ class SourceImage:                          # reconstruction.rs:74-81
 
     @staticmethod
     def load(path: str, focal_length_35mm: Optional[float] = None, size: int = IMG_SIZE, resampler=None,
-             ctx=None, jpeg_decoder=None) -> "SourceImage":
+             ctx=None, jpeg_decoder=None, jpeg_entropy=None) -> "SourceImage":
         """reconstruction.rs:87-131: decode, EXIF focal length, orientation, Lanczos3 to size x size.
         resampler: depth_pro.resolve_resampler; "device" resizes on `ctx` (a Context, or a callable that returns one
         and is only called once the file has been decoded).  jpeg_decoder: depth_pro.resolve_jpeg_decoder; "device"
         decodes a .jpg / .jpeg source on `ctx` (Pillow still reads the EXIF block), chained with the resize when the
-        resampler is "device" too."""
+        resampler is "device" too; jpeg_entropy: depth_pro.resolve_jpeg_entropy, where that decoder runs the Huffman
+        decoding."""
         from PIL import Image, ImageOps
         resampler = resolve_resampler(resampler)
+        jpeg_entropy = resolve_jpeg_entropy(jpeg_entropy)
         if resolve_jpeg_decoder(jpeg_decoder) == "device" and path.lower().endswith((".jpg", ".jpeg")):
-            return SourceImage._load_jpeg_on_device(path, focal_length_35mm, size, resampler, ctx)
+            return SourceImage._load_jpeg_on_device(path, focal_length_35mm, size, resampler, ctx, jpeg_entropy)
         try:
             img = Image.open(path)
             img.load()
@@ -63,7 +65,7 @@ class SourceImage:                          # reconstruction.rs:74-81
                            focal_length_35mm)
 
     @staticmethod
-    def _load_jpeg_on_device(path, focal_length_35mm, size, resampler, ctx) -> "SourceImage":
+    def _load_jpeg_on_device(path, focal_length_35mm, size, resampler, ctx, jpeg_entropy="host") -> "SourceImage":
         import io
         from PIL import Image
         if ctx is None:
@@ -72,6 +74,7 @@ class SourceImage:                          # reconstruction.rs:74-81
             with open(path, "rb") as f:
                 data = f.read()
             ctx = ctx() if callable(ctx) else ctx
+            ctx.set_jpeg_entropy(jpeg_entropy)
             width, height, _, _ = ctx.jpeg_info(data)
             orientation = 1
             try:                                  # header only: Pillow parses the EXIF block, not the scans
@@ -118,15 +121,19 @@ class SourceImage:                          # reconstruction.rs:74-81
 
 def extract_depth(device: int, model_loader: DepthProModelLoader, source_path: str, destination_path: str,
                   focal_length_35mm: Optional[float], image_format: ImageOutputFormat,
-                  vertex_mode: VertexMode, progress=None, noise=None, resampler=None, jpeg_decoder=None) -> None:
+                  vertex_mode: VertexMode, progress=None, noise=None, resampler=None, jpeg_decoder=None,
+                  jpeg_entropy=None) -> None:
     """reconstruction.rs:155-205.  resampler: depth_pro.resolve_resampler, passed down to every resize; jpeg_decoder:
-    depth_pro.resolve_jpeg_decoder, for the source photo"""
+    depth_pro.resolve_jpeg_decoder, for the source photo, and jpeg_entropy: depth_pro.resolve_jpeg_entropy, for its
+    Huffman decoding"""
     resampler = resolve_resampler(resampler)
     jpeg_decoder = resolve_jpeg_decoder(jpeg_decoder)
+    jpeg_entropy = resolve_jpeg_entropy(jpeg_entropy)
     dtype = os.environ.get("MATRIX_EYES_DTYPE", "f16")   # f16 | bf16 | fp8, as the C++ twin
     try:
         img = SourceImage.load(source_path, focal_length_35mm, model_loader.cfg.img_size, resampler=resampler,
-                               ctx=lambda: model_loader.context(device, dtype), jpeg_decoder=jpeg_decoder)
+                               ctx=lambda: model_loader.context(device, dtype), jpeg_decoder=jpeg_decoder,
+                               jpeg_entropy=jpeg_entropy)
     except ReconstructionError as err:
         print(err, file=sys.stderr)
         raise
