@@ -329,6 +329,35 @@ int32_t me_output_stereogram_png(me_ctx* ctx, const float* depth, int32_t rows, 
                                  float max_depth, int32_t out_w, int32_t out_h, float amplitude,
                                  const uint8_t* noise, const char* destination_path);
 
+/* ---- JPEG encoding on the device (RgbImage::save to ".jpg" / ".jpeg") -------------------------------------------------- */
+
+/* RgbImage::save to ".jpg" (output.rs:138, :192): rgb [h,w,3] -> a complete baseline JFIF file (SOF0, 8 bits, three
+   components in one interleaved scan, the Annex K quantisation tables scaled by `quality` and the Annex K Huffman tables,
+   no restart markers) in DEVICE memory owned by the context (valid until its next JPEG-encode call); host or device rgb;
+   enqueued on the context's stream, synchronised because it returns a size.  quality is 1..100; subsampling 0 = 4:4:4,
+   1 = 4:2:2, 2 = 4:2:0.  The bytes are those libjpeg writes for the same parameters with its integer DCT and optimize off
+   (Pillow's Image.save(.., "JPEG", quality=, subsampling=, optimize=False)), and those of the C++ host layer's encode_jpeg.
+   Needs a context, not finalised weights.  A null pointer, a quality outside 1..100 or a subsampling outside 0..2 is
+   ME_ERR_BAD_ARG; a non-positive size or one above min(ME_RESIZE_MAX_DIM, 65535) is ME_ERR_BAD_SHAPE.  Scratch belongs to
+   the context and grows to the high-water mark. */
+int32_t me_jpeg_encode_rgb8(me_ctx* ctx, const uint8_t* rgb, int32_t w, int32_t h, int32_t quality, int32_t subsampling,
+                            const uint8_t** jpg_dev, int64_t* nbytes);
+/* The same, copied to the host once and written to destination_path (an unwritable path is ME_ERR_IO). */
+int32_t me_output_jpeg(me_ctx* ctx, const uint8_t* rgb, int32_t w, int32_t h, int32_t quality, int32_t subsampling,
+                       const char* destination_path);
+/* output.rs:123-139 output_depth_map to a ".jpg" destination, whole: me_depthmap_rgb_resized into context-owned device
+   memory, then me_output_jpeg.  Arguments and errors as me_depthmap_rgb_resized and me_output_jpeg. */
+int32_t me_output_depth_map_jpeg(me_ctx* ctx, const float* depth, int32_t data_width, int32_t data_height,
+                                 float min_depth, float max_depth, const float* minmax_dev,
+                                 int32_t out_w, int32_t out_h, int32_t quality, int32_t subsampling,
+                                 const char* destination_path);
+/* output.rs:141-193 output_stereogram to a ".jpg" destination, whole: me_stereogram into context-owned device memory, then
+   me_output_jpeg.  Arguments and errors as me_stereogram and me_output_jpeg. */
+int32_t me_output_stereogram_jpeg(me_ctx* ctx, const float* depth, int32_t rows, int32_t cols, float min_depth,
+                                  float max_depth, int32_t out_w, int32_t out_h, float amplitude,
+                                  const uint8_t* noise, int32_t quality, int32_t subsampling,
+                                  const char* destination_path);
+
 /* ---- JPEG decoding on the device (reconstruction.rs:95-113: ImageReader::open(..).decode(), apply_orientation) --------- */
 
 /* Frame size and EXIF span of a JPEG file in memory: width / height as coded (before any orientation), and the offset and

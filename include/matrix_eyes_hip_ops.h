@@ -227,6 +227,19 @@ int32_t me_op_jpeg_coefficients_host(const uint8_t* file, int64_t nbytes, int16_
 #define ME_OP_JPEG_ENTROPY_DECLINED 100
 int32_t me_op_jpeg_entropy(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t subseq_bits, int16_t* coef,
                            int64_t count);
+/* The C++ host layer's JPEG encoder (host/jpeg_encoder.cpp encode_jpeg) from inside the library: the yardstick
+   me_jpeg_encode_rgb8 is measured against in the same process.  HOST arrays only, no context, no GPU; rgb [h,w,3], the file
+   into jpg[0 .. capacity), its size into *nbytes.  0, or < 0 on a null pointer (-1), parameters the encoder refuses (-2) or
+   a capacity that is too small (-3: *nbytes says what is needed, nothing is written). */
+int32_t me_op_jpeg_encode_host(const uint8_t* rgb, int32_t w, int32_t h, int32_t quality, int32_t subsampling,
+                               uint8_t* jpg, int64_t capacity, int64_t* nbytes);
+/* The context's last JPEG encode.  report: [0] blocks of the scan (dummy blocks included), [1] bits of the scan before the
+   padding, [2] stuffed 00 bytes, [3] bytes of the file, workgroups of [4] jpeg_fdct_kernel, [5] jpeg_bits_kernel and
+   jpeg_pack_kernel, [6] the scan over the blocks' bit counts, [7] the two stuffing kernels, [8] the scan over their counts,
+   [9] bytes of the file buffer the encode was sized for (header + twice the packed stream + 2).  ms, HIP event times:
+   [0] upload of a host picture and the tables, [1] fdct, [2] bits and their scan, [3] pack (with the read-back of the
+   scan's bits), [4] stuffing, [5] download of the file (0 when it stayed on the device). */
+int32_t me_last_jpeg_encode(me_ctx* ctx, int64_t report[10], double ms[6]);
 /* Names of the GEMM tile configurations (for reports). */
 int32_t me_op_gemm_config_count(void);
 const char* me_op_gemm_config_name(int32_t cfg);

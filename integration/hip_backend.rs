@@ -55,6 +55,14 @@ impl HipDevice {
         self.check(unsafe { ffi::me_output_png(self.ctx, rgb.as_ptr(), w as i32, h as i32, dst.as_ptr()) })
     }
 
+    /// RgbImage::save to ".jpg" / ".jpeg" for any 8-bit RGB picture (host bytes): a baseline JPEG encoded on the GPU with
+    /// libjpeg's bytes for `quality` (1..100) and `subsampling` (0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0), written to `destination_path`
+    pub fn save_jpeg(&self, rgb: &[u8], w: u32, h: u32, quality: i32, subsampling: i32, destination_path: &str) -> Result<(), HipError> {
+        assert_eq!(rgb.len(), w as usize * h as usize * 3);
+        let dst = CString::new(destination_path).unwrap();
+        self.check(unsafe { ffi::me_output_jpeg(self.ctx, rgb.as_ptr(), w as i32, h as i32, quality, subsampling, dst.as_ptr()) })
+    }
+
     /// DynamicImage::resize_exact(nw, nh, FilterType::Lanczos3) for an RGB8 buffer (reconstruction.rs:107-113,
     /// output.rs:206-218) on the GPU: the bytes `image` 0.25.10 writes.  `rgb` is `[h, w, 3]`, the result `[nh, nw, 3]`.
     pub fn resize_exact_lanczos3(&self, rgb: &[u8], w: u32, h: u32, nw: u32, nh: u32) -> Result<Vec<u8>, HipError> {
@@ -218,6 +226,29 @@ impl<'d> DepthMap<'d> {
         self.device.check(unsafe {
             ffi::me_output_stereogram_png(self.device.ctx, self.data.as_ptr(), self.data_width as i32, self.data_height as i32, self.range.0,
                                           self.range.1, out_w as i32, out_h as i32, amplitude, noise.as_ptr(), dst.as_ptr())
+        })
+    }
+
+    /// output.rs:123-139 output_depth_map to a ".jpg" / ".jpeg" destination, whole: colour map, resize and the baseline JPEG
+    /// encoder on the GPU; only the file's bytes come back
+    pub fn output_depth_map_jpeg(&self, quality: i32, subsampling: i32, destination_path: &str) -> Result<(), HipError> {
+        let (ow, oh) = self.original_size;
+        let dst = CString::new(destination_path).unwrap();
+        self.device.check(unsafe {
+            ffi::me_output_depth_map_jpeg(self.device.ctx, self.data.as_ptr(), self.data_width as i32, self.data_height as i32, self.range.0,
+                                          self.range.1, null(), ow as i32, oh as i32, quality, subsampling, dst.as_ptr())
+        })
+    }
+
+    /// output.rs:141-193 output_stereogram to a ".jpg" / ".jpeg" destination, whole (`noise` as for `stereogram`)
+    pub fn output_stereogram_jpeg(&self, out_w: u32, out_h: u32, amplitude: f32, noise: &[u8], quality: i32, subsampling: i32,
+                                  destination_path: &str) -> Result<(), HipError> {
+        assert_eq!(noise.len(), out_w as usize * out_h as usize * 3);
+        let dst = CString::new(destination_path).unwrap();
+        self.device.check(unsafe {
+            ffi::me_output_stereogram_jpeg(self.device.ctx, self.data.as_ptr(), self.data_width as i32, self.data_height as i32, self.range.0,
+                                           self.range.1, out_w as i32, out_h as i32, amplitude, noise.as_ptr(), quality, subsampling,
+                                           dst.as_ptr())
         })
     }
 

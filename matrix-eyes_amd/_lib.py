@@ -90,6 +90,10 @@ SIGNATURES = {
     "me_output_png": (_i32, [_vp, _vp, _i32, _i32, C.c_char_p]),
     "me_output_depth_map_png": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _vp, _i32, _i32, C.c_char_p]),
     "me_output_stereogram_png": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _i32, _i32, _f32, _vp, C.c_char_p]),
+    "me_jpeg_encode_rgb8": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_i64)]),
+    "me_output_jpeg": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, C.c_char_p]),
+    "me_output_depth_map_jpeg": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _vp, _i32, _i32, _i32, _i32, C.c_char_p]),
+    "me_output_stereogram_jpeg": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _i32, _i32, _f32, _vp, _i32, _i32, C.c_char_p]),
     "me_mesh_index": (_i32, [_vp, _vp, _i32, _i32, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "me_mesh_vertices": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _u32, _u32, _vp, _vp]),
     "me_output_mesh": (_i32, [_vp, _vp, _i32, _i32, _u32, _u32, C.c_char_p, C.c_char_p, _i32, _vp]),
@@ -152,6 +156,8 @@ SIGNATURES = {
     "me_op_jpeg_decode_host": (_i32, [_vp, _i64, _vp, _i32, _i32]),
     "me_op_jpeg_coefficients_host": (_i32, [_vp, _i64, _vp, _i64]),
     "me_op_jpeg_entropy": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64]),
+    "me_op_jpeg_encode_host": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _i64, C.POINTER(_i64)]),
+    "me_last_jpeg_encode": (_i32, [_vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
     "me_op_gemm_config_count": (_i32, []),
     "me_op_gemm_config_name": (C.c_char_p, [_i32]),
 }

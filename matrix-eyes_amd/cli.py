@@ -116,8 +116,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     except UsageExit as e:
         return int(e.code)
     from ._lib import MatrixEyesError
-    from .depth_pro import (DepthProModelLoader, resolve_jpeg_decoder, resolve_jpeg_entropy, resolve_png_encoder,
-                            resolve_resampler)
+    from .depth_pro import (DepthProModelLoader, resolve_jpeg_decoder, resolve_jpeg_encoder, resolve_jpeg_entropy,
+                            resolve_jpeg_quality, resolve_jpeg_subsampling, resolve_png_encoder, resolve_resampler)
     from .reconstruction import extract_depth
     try:
         resolve_resampler()                  # MATRIX_EYES_RESAMPLER = pillow | device
@@ -139,6 +139,14 @@ def main(argv: Optional[List[str]] = None) -> int:
     except MatrixEyesError as err:
         print(f"MATRIX_EYES_JPEG_ENTROPY: {err.message}", file=sys.stderr)
         return 2
+    # MATRIX_EYES_JPEG_ENCODER = pillow | host | device, _QUALITY = 1..100, _SUBSAMPLING = 4:4:4 | 4:2:2 | 4:2:0
+    for name, resolve in (("MATRIX_EYES_JPEG_ENCODER", resolve_jpeg_encoder), ("MATRIX_EYES_JPEG_QUALITY", resolve_jpeg_quality),
+                          ("MATRIX_EYES_JPEG_SUBSAMPLING", resolve_jpeg_subsampling)):
+        try:
+            resolve()
+        except MatrixEyesError as err:
+            print(f"{name}: {err.message}", file=sys.stderr)
+            return 2
     import os
     from .config import ModelConfig
     # MATRIX_EYES_MODEL=tiny: the test geometry of the parity suite, as the compiled CLI takes it

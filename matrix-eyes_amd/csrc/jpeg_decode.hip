@@ -171,6 +171,7 @@ int16_t* jpeg_pinned_buffer(me_ctx* ctx, size_t count) { return pinned_coefficie
 
 void free_jpeg_scratch(me_ctx* ctx) {
     free_jpeg_entropy_scratch(ctx);
+    free_jpeg_encode_scratch(ctx);
     if (ctx->jpeg_pinned) (void)hipHostFree(ctx->jpeg_pinned);
     ctx->jpeg_pinned = nullptr, ctx->jpeg_pinned_count = 0;
     if (ctx->jpeg_uploaded) (void)hipEventDestroy(ctx->jpeg_uploaded);

@@ -136,6 +136,17 @@ struct JpegEntropyReport {
     double ms[3] = {0, 0, 0};   // host marker scan and destuffing (wall clock), upload, entropy kernels (HIP events)
 };
 
+// me_last_jpeg_encode: the context's last JPEG encode (jpeg_encode.hip)
+struct JpegEncodeReport {
+    int64_t blocks = 0;              // of the scan, dummy blocks included
+    int64_t scan_bits = 0;           // before the padding
+    int64_t stuffed = 0;             // 00 bytes inserted
+    int64_t file_bytes = 0;
+    int64_t fdct_groups = 0, wave_groups = 0, block_scan_groups = 0, stuff_groups = 0;   // workgroups per kernel
+    int64_t capacity = 0;            // bytes of the file buffer the encode was sized for
+    bool downloaded = false;         // the file was copied to the host (the sixth leg)
+};
+
 struct me_ctx {
     int device = 0;
     int32_t dtype = ME_DTYPE_F16;
@@ -267,6 +278,10 @@ struct me_ctx {
     bool jpeg_entropy_reported = false;
     hipEvent_t jpeg_entropy_ev[3] = {nullptr, nullptr, nullptr};
     int32_t* jpeg_entropy_status = nullptr;
+    // JPEG encoding (jpeg_encode.hip): the report of the last encode and the marks around its legs (me_last_jpeg_encode)
+    JpegEncodeReport jpeg_encode_report;
+    bool jpeg_encode_reported = false;
+    hipEvent_t jpeg_encode_ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 
     // The whole extract_depth step as one hipGraph (shapes are static per batch size).  A call whose pointers
     // all live on the device and that needs no host callback is enqueued eagerly the first time it is seen,
@@ -406,6 +421,8 @@ int16_t* jpeg_pinned_buffer(me_ctx* ctx, size_t count);
 bool jpeg_entropy_decode(me_ctx* ctx, const std::vector<uint8_t>& file, int32_t subseq_bits,
                          matrix_eyes::JpegEntropyPlan& plan);
 void free_jpeg_entropy_scratch(me_ctx* ctx);
+// jpeg_encode.hip
+void free_jpeg_encode_scratch(me_ctx* ctx);
 
 // calibrate.hip: the two fixed loops of bench.py's calibration leg (out[6])
 void calibrate(me_ctx* ctx, double* out);

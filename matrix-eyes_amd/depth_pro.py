@@ -73,6 +73,47 @@ def resolve_png_encoder(png_encoder=None) -> str:
     return value
 
 
+JPEG_ENCODERS = ("pillow", "host", "device")
+JPEG_SUBSAMPLINGS = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}
+
+
+def resolve_jpeg_encoder(jpeg_encoder=None) -> str:
+    """Who writes a ".jpg" / ".jpeg" destination (RgbImage::save, output.rs:138 and :192): "pillow" (the default; "host",
+    the compiled CLI's name for its own encoder, means the same here) or "device" (me_output_jpeg and the two whole-method
+    calls: colour conversion, DCT, Huffman coding and byte stuffing on the GPU, only the file's bytes come back).  With the
+    same quality and subsampling both write the same file, byte for byte.  None reads MATRIX_EYES_JPEG_ENCODER; anything
+    but these names is an argument error."""
+    value = os.environ.get("MATRIX_EYES_JPEG_ENCODER", "pillow") if jpeg_encoder is None else jpeg_encoder
+    if value not in JPEG_ENCODERS:
+        raise L.MatrixEyesError(1, f"jpeg encoder {value!r}: expected one of {', '.join(JPEG_ENCODERS)}")
+    return "pillow" if value == "host" else value
+
+
+def resolve_jpeg_quality(jpeg_quality=None) -> int:
+    """The quality a ".jpg" destination is written with, 1..100: None reads MATRIX_EYES_JPEG_QUALITY (default 75, Pillow's
+    own); anything else is an argument error."""
+    value = os.environ.get("MATRIX_EYES_JPEG_QUALITY", "75") if jpeg_quality is None else jpeg_quality
+    try:
+        quality = int(str(value).strip())
+    except ValueError:
+        quality = 0
+    if not 1 <= quality <= 100:
+        raise L.MatrixEyesError(1, f"jpeg quality {value!r}: expected an integer in 1..100")
+    return quality
+
+
+def resolve_jpeg_subsampling(jpeg_subsampling=None) -> int:
+    """The chroma subsampling a ".jpg" destination is written with, as Pillow numbers it: "4:4:4" -> 0, "4:2:2" -> 1,
+    "4:2:0" -> 2 (the numbers are accepted too).  None reads MATRIX_EYES_JPEG_SUBSAMPLING (default "4:2:0", Pillow's own);
+    anything else is an argument error."""
+    value = os.environ.get("MATRIX_EYES_JPEG_SUBSAMPLING", "4:2:0") if jpeg_subsampling is None else jpeg_subsampling
+    if value in JPEG_SUBSAMPLINGS:
+        return JPEG_SUBSAMPLINGS[value]
+    if not isinstance(value, (bool, str)) and value in (0, 1, 2):
+        return int(value)
+    raise L.MatrixEyesError(1, f"jpeg subsampling {value!r}: expected one of {', '.join(JPEG_SUBSAMPLINGS)}")
+
+
 JPEG_DECODERS = ("pillow", "host", "device")
 
 
@@ -409,6 +450,39 @@ class Context:
         h, w = self._rgb_shape(rgb, "output_png")
         p, keep = _in_ptr(rgb, np.uint8)
         self._check(self.lib.me_output_png(self._h, p, w, h, str(destination_path).encode()))
+
+    def jpeg_encode(self, rgb, quality: int = 75, subsampling: int = 2):
+        """RgbImage::save to ".jpg" without the file (me_jpeg_encode_rgb8): uint8 [h, w, 3] -> the complete baseline JPEG
+        file, encoded on the GPU; subsampling 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0.  numpy in -> `bytes`; a CUDA torch tensor
+        in -> a CUDA uint8 tensor (a copy of the context-owned buffer)."""
+        h, w = self._rgb_shape(rgb, "jpeg_encode")
+        p, keep = _in_ptr(rgb, np.uint8)
+        ptr, n = C.c_void_p(), C.c_int64()
+        self._check(self.lib.me_jpeg_encode_rgb8(self._h, p, w, h, int(quality), int(subsampling), C.byref(ptr), C.byref(n)))
+        import torch
+
+        class _DevMem:
+            def __init__(self, ptr, nbytes):
+                self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
+        on_device = _is_torch(rgb) and rgb.is_cuda
+        file = torch.as_tensor(_DevMem(int(ptr.value), int(n.value)), device=rgb.device if on_device else "cuda")
+        return file.clone() if on_device else file.cpu().numpy().tobytes()
+
+    def output_jpeg(self, rgb, destination_path: str, quality: int = 75, subsampling: int = 2):
+        """jpeg_encode, copied to the host once and written to destination_path (me_output_jpeg)"""
+        h, w = self._rgb_shape(rgb, "output_jpeg")
+        p, keep = _in_ptr(rgb, np.uint8)
+        self._check(self.lib.me_output_jpeg(self._h, p, w, h, int(quality), int(subsampling), str(destination_path).encode()))
+
+    def last_jpeg_encode(self):
+        """me_last_jpeg_encode: (dict of blocks, scan_bits, stuffed, file_bytes, fdct_groups, wave_groups,
+        block_scan_groups, stuff_groups, stuff_scan_groups, capacity; ms (upload, fdct, bits + scan, pack, stuffing,
+        download))"""
+        rep, ms = (C.c_int64 * 10)(), (C.c_double * 6)()
+        self._check(self.lib.me_last_jpeg_encode(self._h, rep, ms))
+        names = ("blocks", "scan_bits", "stuffed", "file_bytes", "fdct_groups", "wave_groups", "block_scan_groups",
+                 "stuff_groups", "stuff_scan_groups", "capacity")
+        return dict(zip(names, (int(v) for v in rep))), tuple(float(v) for v in ms)
 
     def vit_forward_features(self, which: int, xs, intermediate_blocks: Sequence[int] = ()):
         """vit.rs:328-346 -> (final [W,T,C], [intermediate ...])"""

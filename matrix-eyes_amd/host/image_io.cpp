@@ -352,7 +352,14 @@ void save_image(const RgbImage& img, const std::string& path) {
         if (!f.write((const char*)img.data.data(), (std::streamsize)img.data.size())) throw ImageError("cannot write " + path);
         return;
     }
-    throw ImageError(path + ": unsupported output image format (this host layer encodes .png and .ppm)");
+    if (ends_with_ci(path, ".jpg") || ends_with_ci(path, ".jpeg")) {
+        const JpegOutputParams p = jpeg_output_params();
+        const std::vector<uint8_t> file = encode_jpeg(img, p.quality, p.subsampling);
+        std::ofstream f(path, std::ios::binary);
+        if (!f.write((const char*)file.data(), (std::streamsize)file.size())) throw ImageError("cannot write " + path);
+        return;
+    }
+    throw ImageError(path + ": unsupported output image format (this host layer encodes .png, .jpg / .jpeg and .ppm)");
 }
 
 RgbImage resize_exact_lanczos3(const RgbImage& img, uint32_t width, uint32_t height) {

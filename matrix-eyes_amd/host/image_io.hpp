@@ -1,7 +1,7 @@
 // Image file I/O and resampling for the C++ host layer (the reference uses the `image` and `kamadak-exif`
 // crates: reconstruction.rs:96-113,133-143, output.rs:133-138,192,206-218).  Decoded here: JPEG (baseline and
-// progressive Huffman, jpeg_decoder.cpp), PNG (8/16-bit, non-interlaced, zlib) and binary PPM; encoded: PNG
-// and PPM.  Anything else is an ImageError, as an unsupported format is in the reference.
+// progressive Huffman, jpeg_decoder.cpp), PNG (8/16-bit, non-interlaced, zlib) and binary PPM; encoded: PNG,
+// baseline JPEG (jpeg_encoder.cpp) and PPM.  Anything else is an ImageError, as an unsupported format is in the reference.
 #pragma once
 #include <cstdint>
 #include <optional>
@@ -119,6 +119,16 @@ void check_jpeg_reconstructible(const JpegCoefficients& c, const std::string& pa
 // the 64 doubles basis[x][u] of the decoder's separable IDCT (csrc/jpeg_basis.cpp: one function for host and device)
 void jpeg_idct_basis(double basis[64]);
 void save_image(const RgbImage& img, const std::string& path);    // RgbImage::save: format from the extension
+// RgbImage::save to ".jpg" / ".jpeg": a baseline JFIF file (one interleaved scan, the Annex K tables, no restart markers),
+// byte for byte what libjpeg writes for the same quality (1..100) and subsampling (0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0) with
+// its integer DCT and optimize off.  Throws ImageError for parameters outside those ranges or a side above 65535.
+std::vector<uint8_t> encode_jpeg(const RgbImage& img, int quality, int subsampling);
+// what save_image encodes a JPEG with: MATRIX_EYES_JPEG_QUALITY (default 75) and MATRIX_EYES_JPEG_SUBSAMPLING ("4:4:4",
+// "4:2:2" or "4:2:0", the default); anything else in either variable is an ImageError
+struct JpegOutputParams {
+    int quality = 75, subsampling = 2;
+};
+JpegOutputParams jpeg_output_params();
 // DynamicImage::resize_exact(w, h, FilterType::Lanczos3); the identity when the size already matches
 RgbImage resize_exact_lanczos3(const RgbImage& img, uint32_t width, uint32_t height);
 

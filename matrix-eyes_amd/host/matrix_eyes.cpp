@@ -39,6 +39,8 @@ uint32_t round_u32(float x) {
     return r >= 4294967296.0f ? 4294967295u : (uint32_t)r;
 }
 
+bool is_jpeg_name(const std::string& path) { return ends_with_ci(path, ".jpg") || ends_with_ci(path, ".jpeg"); }
+
 void progress_trampoline(void* user, float pos, const char* message) {
     ProgressListener* pl = (ProgressListener*)user;
     pl->report_status(pos);
@@ -69,6 +71,17 @@ Device::Device() {
             device_jpeg_decoder_ = true;
         else if (std::strcmp(jd, "host") != 0)
             throw ModelError(ME_ERR_BAD_ARG, std::string("MATRIX_EYES_JPEG_DECODER=") + jd + ": expected host or device");
+    }
+    if (const char* je = std::getenv("MATRIX_EYES_JPEG_ENCODER")) {
+        if (std::strcmp(je, "device") == 0)
+            device_jpeg_encoder_ = true;
+        else if (std::strcmp(je, "host") != 0)
+            throw ModelError(ME_ERR_BAD_ARG, std::string("MATRIX_EYES_JPEG_ENCODER=") + je + ": expected host or device");
+    }
+    try {  // MATRIX_EYES_JPEG_QUALITY, MATRIX_EYES_JPEG_SUBSAMPLING: refused here, not at the first ".jpg" written
+        jpeg_params_ = jpeg_output_params();
+    } catch (const ImageError& err) {
+        throw ModelError(ME_ERR_BAD_ARG, err.what());
     }
     bool device_jpeg_entropy = false;  // acts only behind MATRIX_EYES_JPEG_DECODER=device: the host decoder has one entropy loop
     if (const char* je = std::getenv("MATRIX_EYES_JPEG_ENTROPY")) {
@@ -210,6 +223,14 @@ void DepthMap::output_depth_map(const std::string& destination_path) const {
                                                             destination_path.c_str()));
         return;
     }
+    if (device_.device_resampler() && device_.device_jpeg_encoder() && is_jpeg_name(destination_path)) {
+        // ... or, to a ".jpg": transformed, Huffman-coded and stuffed on the GPU
+        const JpegOutputParams& p = device_.jpeg_params();
+        check_output(device_.ctx(), me_output_depth_map_jpeg(device_.ctx(), data_.data(), (int32_t)data_width_, (int32_t)data_height_,
+                                                             min_, max_, nullptr, (int32_t)original_width_, (int32_t)original_height_,
+                                                             p.quality, p.subsampling, destination_path.c_str()));
+        return;
+    }
     if (device_.device_resampler()) {  // the colour map and the resize chained on the GPU
         RgbImage resized(original_width_, original_height_);
         check_output(device_.ctx(), me_depthmap_rgb_resized(device_.ctx(), data_.data(), (int32_t)data_width_, (int32_t)data_height_, min_,
@@ -251,6 +272,13 @@ void DepthMap::output_stereogram(const std::string& destination_path, std::optio
         check_output(device_.ctx(), me_output_stereogram_png(device_.ctx(), data_.data(), (int32_t)data_width_, (int32_t)data_height_,
                                                              min_, max_, (int32_t)w, (int32_t)h, amplitude, noise.data.data(),
                                                              destination_path.c_str()));
+        return;
+    }
+    if (device_.device_jpeg_encoder() && is_jpeg_name(destination_path)) {
+        const JpegOutputParams& p = device_.jpeg_params();
+        check_output(device_.ctx(), me_output_stereogram_jpeg(device_.ctx(), data_.data(), (int32_t)data_width_, (int32_t)data_height_,
+                                                              min_, max_, (int32_t)w, (int32_t)h, amplitude, noise.data.data(),
+                                                              p.quality, p.subsampling, destination_path.c_str()));
         return;
     }
     check_output(device_.ctx(), me_stereogram(device_.ctx(), data_.data(), (int32_t)data_width_, (int32_t)data_height_, min_, max_,

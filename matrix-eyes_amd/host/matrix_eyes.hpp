@@ -64,6 +64,12 @@ public:
     // me_output_stereogram_png) and only the file's bytes come back; "host" (the default) is image_io's encode_png.  Any
     // other value fails the constructor.  The files differ in their bytes, not in their pixels.
     bool device_png_encoder() const { return device_png_encoder_; }
+    // RgbImage::save to ".jpg" / ".jpeg": with MATRIX_EYES_JPEG_ENCODER=device output_depth_map and output_stereogram make
+    // and encode the picture on the GPU in one call (me_output_depth_map_jpeg, me_output_stereogram_jpeg); "host" (the
+    // default) is image_io's encode_jpeg.  Both write the same bytes, with MATRIX_EYES_JPEG_QUALITY (75) and
+    // MATRIX_EYES_JPEG_SUBSAMPLING ("4:2:0"); any other value of the three variables fails the constructor.
+    bool device_jpeg_encoder() const { return device_jpeg_encoder_; }
+    const JpegOutputParams& jpeg_params() const { return jpeg_params_; }
     // ImageReader::open(..).decode() of a JPEG photo (reconstruction.rs:95-106): with MATRIX_EYES_JPEG_DECODER=device the
     // entropy-coded segments are decoded on the host and the picture is reconstructed and oriented on the GPU
     // (me_jpeg_decode_rgb8), chained there with the resize when the device resampler is on (me_jpeg_decode_resized_rgb8:
@@ -81,6 +87,8 @@ private:
     int image_size_ = IMG_SIZE;
     bool device_resampler_ = true;
     bool device_png_encoder_ = false;
+    bool device_jpeg_encoder_ = false;
+    JpegOutputParams jpeg_params_;
     bool device_jpeg_decoder_ = false;
     mutable bool weights_loaded_ = false;
     friend class DepthProModelLoader;

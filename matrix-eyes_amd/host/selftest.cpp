@@ -1,6 +1,6 @@
 // Test driver for the pieces of the host layer that need no GPU (tests/test_host_cpp.py):
 //   host_selftest pt <checkpoint.pt>            one line per tensor: name dtype dims... fnv1a64(data)
-//   host_selftest png <in> <out>                decode, re-encode
+//   host_selftest png <in> <out>                decode, re-encode (<out>: .png, .ppm, .jpg or .jpeg)
 //   host_selftest resize <in> <w> <h> <out>     Lanczos3 resize_exact
 //   host_selftest resize-time <w> <h> <nw> <nh> the same loop on a picture of seeded random bytes, no files: prints
 //                                               "milliseconds fnv1a64(result)" (tools/bench_resize.py)

@@ -9,7 +9,8 @@ from typing import Optional
 import numpy as np
 
 from . import _lib as L
-from .depth_pro import Context, _in_ptr, resolve_png_encoder, resolve_resampler
+from .depth_pro import (Context, _in_ptr, resolve_jpeg_encoder, resolve_jpeg_quality, resolve_jpeg_subsampling,
+                        resolve_png_encoder, resolve_resampler)
 
 
 class VertexMode(enum.IntEnum):   # output.rs:33-38
@@ -158,16 +159,54 @@ class DepthMap:
             self.ctx.handle, C.c_void_p(self.data.ctypes.data), self.data_width, self.data_height, mn, mx,
             w, h, amplitude, pn, str(destination_path).encode()))
 
+    def output_depth_map_jpeg(self, destination_path: str, quality: int = 75, subsampling: int = 2):
+        """output.rs:123-139 whole, on the GPU (me_output_depth_map_jpeg): colour map, Lanczos3 resize, JPEG file"""
+        mn, mx = self._range
+        self.ctx._check(self.ctx.lib.me_output_depth_map_jpeg(
+            self.ctx.handle, C.c_void_p(self.data.ctypes.data), self.data_width, self.data_height, mn, mx, None,
+            self.original_width, self.original_height, int(quality), int(subsampling), str(destination_path).encode()))
+
+    def output_stereogram_jpeg(self, destination_path: str, resize_scale: Optional[float], amplitude: float, noise=None,
+                               quality: int = 75, subsampling: int = 2):
+        """output.rs:141-193 whole, on the GPU (me_output_stereogram_jpeg); noise as for `stereogram`"""
+        w, h = self.stereogram_size(resize_scale)
+        if noise is None:
+            noise = _noise_rng().integers(0, 256, size=(h, w, 3), dtype=np.uint8)
+        pn, keep = _in_ptr(noise, np.uint8)
+        if tuple(noise.shape) != (h, w, 3):
+            raise L.MatrixEyesError(2, f"noise must be [{h},{w},3]")
+        mn, mx = self._range
+        self.ctx._check(self.ctx.lib.me_output_stereogram_jpeg(
+            self.ctx.handle, C.c_void_p(self.data.ctypes.data), self.data_width, self.data_height, mn, mx,
+            w, h, amplitude, pn, int(quality), int(subsampling), str(destination_path).encode()))
+
     def output_image(self, destination_path: str, source_path: str, image_format: ImageOutputFormat,
-                     vertex_mode: VertexMode, noise=None, resampler=None, png_encoder=None):
+                     vertex_mode: VertexMode, noise=None, resampler=None, png_encoder=None, jpeg_encoder=None,
+                     jpeg_quality=None, jpeg_subsampling=None):
         """output.rs:100-121: dispatch on the destination suffix.  resampler: depth_pro.resolve_resampler;
-        png_encoder: depth_pro.resolve_png_encoder."""
+        png_encoder: depth_pro.resolve_png_encoder; jpeg_encoder, jpeg_quality, jpeg_subsampling:
+        depth_pro.resolve_jpeg_encoder / _quality / _subsampling (they act on a ".jpg" / ".jpeg" destination only)."""
         resampler = resolve_resampler(resampler)
         png_encoder = resolve_png_encoder(png_encoder)
+        jpeg_encoder = resolve_jpeg_encoder(jpeg_encoder)
         low = destination_path.lower()
         if low.endswith(".ply") or low.endswith(".obj"):
             return self.output_mesh(destination_path, source_path, vertex_mode, resampler=resampler)
         from PIL import Image
+        save_args = {}
+        if low.endswith(".jpg") or low.endswith(".jpeg"):
+            # both paths are defined by the same numbers: Pillow's own defaults, spelled out
+            quality, subsampling = resolve_jpeg_quality(jpeg_quality), resolve_jpeg_subsampling(jpeg_subsampling)
+            save_args = {"format": "JPEG", "quality": quality, "subsampling": subsampling, "optimize": False}
+            if jpeg_encoder == "device":
+                native = self.original_width == self.original_height == self.data_width == self.data_height
+                if image_format.kind != "depthmap":
+                    return self.output_stereogram_jpeg(destination_path, image_format.resize_scale, image_format.amplitude,
+                                                       noise, quality, subsampling)
+                if resampler == "device" or native:   # (the resize is the identity at the native size)
+                    return self.output_depth_map_jpeg(destination_path, quality, subsampling)
+                img = Image.fromarray(self.depth_map_rgb()).resize((self.original_width, self.original_height), Image.LANCZOS)
+                return self.ctx.output_jpeg(np.asarray(img, dtype=np.uint8), destination_path, quality, subsampling)
         if png_encoder == "device" and low.endswith(".png"):
             native = self.original_width == self.original_height == self.data_width == self.data_height
             if image_format.kind != "depthmap":
@@ -177,16 +216,16 @@ class DepthMap:
             img = Image.fromarray(self.depth_map_rgb()).resize((self.original_width, self.original_height), Image.LANCZOS)
             return self.ctx.output_png(np.asarray(img, dtype=np.uint8), destination_path)
         if image_format.kind == "depthmap" and resampler == "device":
-            Image.fromarray(self.depth_map_rgb_resized()).save(destination_path)
+            Image.fromarray(self.depth_map_rgb_resized()).save(destination_path, **save_args)
         elif image_format.kind == "depthmap":
             img = Image.fromarray(self.depth_map_rgb())
             size = (self.original_width, self.original_height)
             if img.size != size:   # output.rs:133-137 (identity at the native size)
                 img = img.resize(size, Image.LANCZOS)
-            img.save(destination_path)
+            img.save(destination_path, **save_args)
         else:
             Image.fromarray(self.stereogram(image_format.resize_scale, image_format.amplitude,
-                                            noise)).save(destination_path)
+                                            noise)).save(destination_path, **save_args)
 
     def output_mesh(self, destination_path: str, source_path: str, vertex_mode: VertexMode, resampler=None):
         """output.rs:195-261 with ObjWriter / PlyWriter."""
