@@ -1,6 +1,7 @@
 // extern "C" boundary of libmatrixeyes_hip.so (include/matrix_eyes_hip.h, matrix_eyes_hip_ops.h).
-// Every entry point converts internal me::Error into a status code + last_error text; nothing
-// throws or aborts across the boundary.
+// Every entry point converts internal me::Error into a status code + last_error text (model.h
+// ME_API_BEGIN / ME_API_END); nothing throws or aborts across the boundary.  The raster and file
+// entries of the output back end are in output_api.hip.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -16,29 +17,6 @@ using namespace me;
 namespace {
 
 thread_local std::string g_create_error;
-
-struct OutBuf {
-    void* dev = nullptr;
-    void* user = nullptr;
-    size_t bytes = 0;
-    bool staged = false;
-};
-
-OutBuf out_buf(me_ctx* ctx, void* user, size_t bytes, const std::string& name) {
-    OutBuf o;
-    o.user = user, o.bytes = bytes;
-    if (is_device_ptr(user)) {
-        o.dev = user;
-    } else {
-        o.dev = site_buf(ctx, name, bytes);
-        o.staged = true;
-    }
-    return o;
-}
-
-void finish(me_ctx* ctx, const OutBuf& o) {
-    if (o.staged) from_device(ctx, o.user, o.dev, o.bytes);
-}
 
 void check_ready(me_ctx* ctx) {
     ME_CHECK(ctx->finalized, ME_ERR_NOT_READY,
@@ -115,6 +93,29 @@ void check_pending_status(me_ctx* ctx) {
 }  // namespace
 
 namespace me {
+OutBuf out_buf(me_ctx* ctx, void* user, size_t bytes, const std::string& name) {
+    OutBuf o;
+    o.user = user, o.bytes = bytes;
+    if (is_device_ptr(user)) {
+        o.dev = user;
+    } else {
+        o.dev = site_buf(ctx, name, bytes);
+        o.staged = true;
+    }
+    return o;
+}
+
+void finish(me_ctx* ctx, const OutBuf& o) {
+    if (o.staged) from_device(ctx, o.user, o.dev, o.bytes);
+}
+
+void check_resize_shape(const char* who, int32_t w, int32_t h, int32_t nw, int32_t nh) {
+    ME_CHECK(w > 0 && h > 0 && nw > 0 && nh > 0, ME_ERR_BAD_SHAPE, "%s: %dx%d -> %dx%d", who, w, h, nw, nh);
+    ME_CHECK(w <= ME_RESIZE_MAX_DIM && h <= ME_RESIZE_MAX_DIM && nw <= ME_RESIZE_MAX_DIM && nh <= ME_RESIZE_MAX_DIM,
+             ME_ERR_BAD_SHAPE, "%s: %dx%d -> %dx%d: a side exceeds ME_RESIZE_MAX_DIM (%d)", who, w, h, nw, nh,
+             ME_RESIZE_MAX_DIM);
+}
+
 namespace {
 me_ctx::DepthSlot* find_depth_slot(me_ctx* ctx, const void* p) {
     const char* q = (const char*)p;
@@ -192,24 +193,6 @@ void mark_produced(me_ctx* ctx, const void* out, size_t bytes) {
     slot->has_produced = true;
 }
 }  // namespace
-
-#define ME_API_BEGIN(ctx)                                                      \
-    if (!(ctx)) return ME_ERR_BAD_ARG;                                         \
-    try {                                                                      \
-        ME_HIP(hipSetDevice((ctx)->device));                                   \
-        me::set_current_status_word((ctx)->status_dev);
-
-#define ME_API_END(ctx)                                                        \
-    }                                                                          \
-    catch (const me::Error& e) {                                               \
-        (ctx)->last_error = e.msg;                                             \
-        return e.code;                                                         \
-    }                                                                          \
-    catch (const std::exception& e) {                                          \
-        (ctx)->last_error = std::string("internal: ") + e.what();              \
-        return ME_ERR_BAD_ARG;                                                 \
-    }                                                                          \
-    return ME_OK;
 
 extern "C" {
 
@@ -919,59 +902,6 @@ int32_t me_depth_clamp_minmax_async(me_ctx* ctx, float* depth, int64_t count, fl
     ME_API_END(ctx)
 }
 
-namespace {
-void stereogram_impl(me_ctx* ctx, const float* depth, int32_t rows, int32_t cols, float min_depth, float max_depth,
-                     const float* range_dev, int32_t out_w, int32_t out_h, float amplitude, const uint8_t* noise,
-                     uint8_t* out) {
-    ME_CHECK(depth && noise && out, ME_ERR_BAD_ARG, "me_stereogram: null pointer");
-    ME_CHECK(rows > 0 && cols > 0 && out_w > 0 && out_h > 0, ME_ERR_BAD_SHAPE,
-             "me_stereogram: %dx%d -> %dx%d", rows, cols, out_w, out_h);
-    const size_t nout = (size_t)out_w * out_h * 3;
-    const float* d = (const float*)to_device(ctx, depth, (size_t)rows * cols * 4, "out.depth");
-    const uint8_t* nz = (const uint8_t*)to_device(ctx, noise, nout, "out.noise");
-    OutBuf o = out_buf(ctx, out, nout, "out.stereo");
-    stereogram_launch(d, rows, cols, min_depth, max_depth, range_dev, out_w, out_h, amplitude, nz,
-                      (uint8_t*)o.dev, ctx->stream);
-    finish(ctx, o);
-}
-void depthmap_rgb_impl(me_ctx* ctx, const float* depth, int64_t count, float min_depth, float max_depth,
-                       const float* range_dev, uint8_t* rgb) {
-    ME_CHECK(depth && rgb && count > 0, ME_ERR_BAD_ARG, "me_depthmap_rgb: bad argument");
-    const float* d = (const float*)to_device(ctx, depth, (size_t)count * 4, "out.depth");
-    OutBuf o = out_buf(ctx, rgb, (size_t)count * 3, "out.rgb");
-    depthmap_rgb_launch(d, count, min_depth, max_depth, range_dev, (uint8_t*)o.dev, ctx->stream);
-    finish(ctx, o);
-}
-}  // namespace
-
-int32_t me_stereogram(me_ctx* ctx, const float* depth, int32_t rows, int32_t cols, float min_depth,
-                      float max_depth, int32_t out_w, int32_t out_h, float amplitude,
-                      const uint8_t* noise, uint8_t* out) {
-    ME_API_BEGIN(ctx)
-    OutputScope out_scope(ctx, depth);
-    stereogram_impl(ctx, depth, rows, cols, min_depth, max_depth, nullptr, out_w, out_h, amplitude, noise, out);
-    ME_API_END(ctx)
-}
-
-int32_t me_stereogram_dev_range(me_ctx* ctx, const float* depth, int32_t rows, int32_t cols,
-                                const float* minmax_dev, int32_t out_w, int32_t out_h, float amplitude,
-                                const uint8_t* noise, uint8_t* out) {
-    ME_API_BEGIN(ctx)
-    OutputScope out_scope(ctx, depth);
-    ME_CHECK(minmax_dev && is_device_ptr(minmax_dev), ME_ERR_BAD_ARG, "me_stereogram_dev_range: minmax_dev");
-    stereogram_impl(ctx, depth, rows, cols, 0.f, 0.f, minmax_dev, out_w, out_h, amplitude, noise, out);
-    ME_API_END(ctx)
-}
-
-namespace {
-void check_resize_shape(const char* who, int32_t w, int32_t h, int32_t nw, int32_t nh) {
-    ME_CHECK(w > 0 && h > 0 && nw > 0 && nh > 0, ME_ERR_BAD_SHAPE, "%s: %dx%d -> %dx%d", who, w, h, nw, nh);
-    ME_CHECK(w <= ME_RESIZE_MAX_DIM && h <= ME_RESIZE_MAX_DIM && nw <= ME_RESIZE_MAX_DIM && nh <= ME_RESIZE_MAX_DIM,
-             ME_ERR_BAD_SHAPE, "%s: %dx%d -> %dx%d: a side exceeds ME_RESIZE_MAX_DIM (%d)", who, w, h, nw, nh,
-             ME_RESIZE_MAX_DIM);
-}
-}  // namespace
-
 int32_t me_resize_lanczos3_rgb8(me_ctx* ctx, const uint8_t* src, int32_t w, int32_t h, uint8_t* dst, int32_t nw,
                                 int32_t nh) {
     ME_API_BEGIN(ctx)
@@ -1128,43 +1058,6 @@ int32_t me_op_jpeg_coefficients_host(const uint8_t* file, int64_t nbytes, int16_
         return -3;
     }
     return 0;
-}
-
-int32_t me_depthmap_rgb_resized(me_ctx* ctx, const float* depth, int32_t data_width, int32_t data_height,
-                                float min_depth, float max_depth, const float* minmax_dev, int32_t out_w,
-                                int32_t out_h, uint8_t* rgb) {
-    ME_API_BEGIN(ctx)
-    OutputScope out_scope(ctx, depth);
-    ME_CHECK(depth && rgb, ME_ERR_BAD_ARG, "me_depthmap_rgb_resized: null pointer");
-    ME_CHECK(!minmax_dev || is_device_ptr(minmax_dev), ME_ERR_BAD_ARG, "me_depthmap_rgb_resized: minmax_dev");
-    check_resize_shape("me_depthmap_rgb_resized", data_width, data_height, out_w, out_h);
-    const int64_t count = (int64_t)data_width * data_height;
-    const float* d = (const float*)to_device(ctx, depth, (size_t)count * 4, "out.depth");
-    // output.rs:124-131: RgbImage::new(data_width, data_height) filled in data order, then :133-137 the resize
-    uint8_t* mapped = (uint8_t*)site_buf(ctx, "out.rgb.native", (size_t)count * 3);
-    depthmap_rgb_launch(d, count, min_depth, max_depth, minmax_dev, mapped, ctx->stream);
-    OutBuf o = out_buf(ctx, rgb, (size_t)out_w * out_h * 3, "out.rgb");
-    ME_CHECK((uint8_t*)o.dev != mapped, ME_ERR_BAD_ARG, "me_depthmap_rgb_resized: rgb is the context's own scratch");
-    resize_lanczos3_rgb8(ctx, mapped, data_width, data_height, (uint8_t*)o.dev, out_w, out_h);
-    finish(ctx, o);
-    ME_API_END(ctx)
-}
-
-int32_t me_depthmap_rgb(me_ctx* ctx, const float* depth, int64_t count, float min_depth,
-                        float max_depth, uint8_t* rgb) {
-    ME_API_BEGIN(ctx)
-    OutputScope out_scope(ctx, depth);
-    depthmap_rgb_impl(ctx, depth, count, min_depth, max_depth, nullptr, rgb);
-    ME_API_END(ctx)
-}
-
-int32_t me_depthmap_rgb_dev_range(me_ctx* ctx, const float* depth, int64_t count, const float* minmax_dev,
-                                  uint8_t* rgb) {
-    ME_API_BEGIN(ctx)
-    OutputScope out_scope(ctx, depth);
-    ME_CHECK(minmax_dev && is_device_ptr(minmax_dev), ME_ERR_BAD_ARG, "me_depthmap_rgb_dev_range: minmax_dev");
-    depthmap_rgb_impl(ctx, depth, count, 0.f, 0.f, minmax_dev, rgb);
-    ME_API_END(ctx)
 }
 
 int32_t me_mesh_index(me_ctx* ctx, const float* depth, int32_t width, int32_t height,

@@ -13,8 +13,6 @@
 // No kernel waits for another workgroup: workgroups meet at launch boundaries only.  Every loop is bounded by a block's 64
 // coefficients, a lane's 16 bytes, or a workgroup's share of the aggregates.  The host reads back two numbers: the scan's
 // bits (the packed stream is sized from them) and the file's size.
-#include <cerrno>
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
@@ -155,10 +153,17 @@ __global__ __launch_bounds__(kThreads) void jpeg_stuff_kernel(const EncTables* _
     }
 }
 
-struct DeviceJpeg {
-    const uint8_t* dev = nullptr;
-    int64_t bytes = 0;
-};
+void scan_launch(const uint32_t* counts, int64_t n, uint64_t* before, uint64_t* agg, uint64_t* carry, hipStream_t s) {
+    const int64_t ngroups = (int64_t)cdiv(n, kThreads);
+    hipLaunchKernelGGL(jpeg_encode_scan_kernel, dim3((unsigned)ngroups), dim3(kThreads), 0, s, counts, n, before, agg);
+    ME_HIP(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_encode_carry_kernel, dim3(1), dim3(kThreads), 0, s, (const uint64_t*)agg, ngroups, carry);
+    ME_HIP(hipGetLastError());
+}
+
+}  // namespace
+
+namespace me {
 
 void check_jpeg_encode_args(const char* who, int32_t w, int32_t h, int32_t quality, int32_t subsampling) {
     ME_CHECK(quality >= 1 && quality <= 100, ME_ERR_BAD_ARG, "%s: quality %d outside 1..100", who, quality);
@@ -169,17 +174,9 @@ void check_jpeg_encode_args(const char* who, int32_t w, int32_t h, int32_t quali
     ME_CHECK(w <= limit && h <= limit, ME_ERR_BAD_SHAPE, "%s: %dx%d: a side exceeds %d", who, w, h, limit);
 }
 
-void scan_launch(const uint32_t* counts, int64_t n, uint64_t* before, uint64_t* agg, uint64_t* carry, hipStream_t s) {
-    const int64_t ngroups = (int64_t)cdiv(n, kThreads);
-    hipLaunchKernelGGL(jpeg_encode_scan_kernel, dim3((unsigned)ngroups), dim3(kThreads), 0, s, counts, n, before, agg);
-    ME_HIP(hipGetLastError());
-    hipLaunchKernelGGL(jpeg_encode_carry_kernel, dim3(1), dim3(kThreads), 0, s, (const uint64_t*)agg, ngroups, carry);
-    ME_HIP(hipGetLastError());
-}
-
 // rgb [h,w,3], host or device -> the file in the context's scratch; synchronises twice (the scan's bits and the file's size
 // come back to the host).  Arguments are checked by the caller.
-DeviceJpeg jpeg_encode_device(me_ctx* ctx, const uint8_t* rgb_any, int32_t w, int32_t h, int32_t quality, int32_t subsampling) {
+DeviceFile jpeg_encode_device(me_ctx* ctx, const uint8_t* rgb_any, int32_t w, int32_t h, int32_t quality, int32_t subsampling) {
     hipStream_t s = ctx->stream;
     // the output back end may run on its own stream (me_ctx_set_output_overlap): its scratch is its own
     const std::string tag = (ctx->out_stream && s == ctx->out_stream) ? "out.jpegenc." : "jpegenc.";
@@ -251,7 +248,7 @@ DeviceJpeg jpeg_encode_device(me_ctx* ctx, const uint8_t* rgb_any, int32_t w, in
     ME_CHECK(stuffed <= (uint64_t)nbytes, ME_ERR_HIP, "jpeg encoder: %llu stuffed bytes in a stream of %lld", (unsigned long long)stuffed,
              (long long)nbytes);
 
-    DeviceJpeg f;
+    DeviceFile f;
     f.dev = file, f.bytes = (int64_t)header_len + nbytes + (int64_t)stuffed + 2;
     rep.blocks = nblocks, rep.scan_bits = (int64_t)total_bits, rep.stuffed = (int64_t)stuffed, rep.file_bytes = f.bytes;
     rep.fdct_groups = fdct_groups, rep.wave_groups = wave_groups, rep.block_scan_groups = block_groups;
@@ -261,110 +258,17 @@ DeviceJpeg jpeg_encode_device(me_ctx* ctx, const uint8_t* rgb_any, int32_t w, in
     return f;
 }
 
-void write_jpeg_file(me_ctx* ctx, const DeviceJpeg& f, const char* path) {
-    std::vector<uint8_t> host((size_t)f.bytes);
-    ME_HIP(hipMemcpyAsync(host.data(), f.dev, host.size(), hipMemcpyDeviceToHost, ctx->stream));
-    ME_HIP(hipEventRecord(ctx->jpeg_encode_ev[6], ctx->stream));
-    ctx->jpeg_encode_report.downloaded = true;
-    ME_HIP(hipStreamSynchronize(ctx->stream));
-    FILE* fp = fopen(path, "wb");
-    ME_CHECK(fp, ME_ERR_IO, "cannot create %s: %s", path, strerror(errno));
-    const bool ok = fwrite(host.data(), 1, host.size(), fp) == host.size();
-    const int werr = errno;
-    const int r = fclose(fp);
-    ME_CHECK(ok, ME_ERR_IO, "write failed: %s: %s", path, strerror(werr));
-    ME_CHECK(r == 0, ME_ERR_IO, "close failed: %s: %s", path, strerror(errno));
-}
-
-}  // namespace
-
-namespace me {
 void free_jpeg_encode_scratch(me_ctx* ctx) {
     for (hipEvent_t& e : ctx->jpeg_encode_ev) {
         if (e) (void)hipEventDestroy(e);
         e = nullptr;
     }
 }
+
 }  // namespace me
 
-#define ME_JPEGENC_API_BEGIN(ctx)               \
-    if (!(ctx)) return ME_ERR_BAD_ARG;          \
-    try {                                       \
-        ME_HIP(hipSetDevice((ctx)->device));
-
-#define ME_JPEGENC_API_END(ctx)                                   \
-    }                                                             \
-    catch (const me::Error& e) {                                  \
-        (ctx)->last_error = e.msg;                                \
-        return e.code;                                            \
-    }                                                             \
-    catch (const std::exception& e) {                             \
-        (ctx)->last_error = std::string("internal: ") + e.what(); \
-        return ME_ERR_BAD_ARG;                                    \
-    }                                                             \
-    return ME_OK;
-
-extern "C" int32_t me_jpeg_encode_rgb8(me_ctx* ctx, const uint8_t* rgb, int32_t w, int32_t h, int32_t quality, int32_t subsampling,
-                                       const uint8_t** jpg_dev, int64_t* nbytes) {
-    ME_JPEGENC_API_BEGIN(ctx)
-    ME_CHECK(rgb && jpg_dev && nbytes, ME_ERR_BAD_ARG, "me_jpeg_encode_rgb8: null pointer");
-    check_jpeg_encode_args("me_jpeg_encode_rgb8", w, h, quality, subsampling);
-    OutputScope out_scope(ctx, is_device_ptr(rgb) ? rgb : nullptr);
-    const DeviceJpeg f = jpeg_encode_device(ctx, rgb, w, h, quality, subsampling);
-    *jpg_dev = f.dev, *nbytes = f.bytes;
-    ME_JPEGENC_API_END(ctx)
-}
-
-extern "C" int32_t me_output_jpeg(me_ctx* ctx, const uint8_t* rgb, int32_t w, int32_t h, int32_t quality, int32_t subsampling,
-                                  const char* destination_path) {
-    ME_JPEGENC_API_BEGIN(ctx)
-    ME_CHECK(rgb && destination_path, ME_ERR_BAD_ARG, "me_output_jpeg: null pointer");
-    check_jpeg_encode_args("me_output_jpeg", w, h, quality, subsampling);
-    OutputScope out_scope(ctx, is_device_ptr(rgb) ? rgb : nullptr);
-    write_jpeg_file(ctx, jpeg_encode_device(ctx, rgb, w, h, quality, subsampling), destination_path);
-    ME_JPEGENC_API_END(ctx)
-}
-
-extern "C" int32_t me_output_depth_map_jpeg(me_ctx* ctx, const float* depth, int32_t data_width, int32_t data_height,
-                                            float min_depth, float max_depth, const float* minmax_dev, int32_t out_w,
-                                            int32_t out_h, int32_t quality, int32_t subsampling, const char* destination_path) {
-    ME_JPEGENC_API_BEGIN(ctx)
-    OutputScope out_scope(ctx, depth);
-    ME_CHECK(depth && destination_path, ME_ERR_BAD_ARG, "me_output_depth_map_jpeg: null pointer");
-    ME_CHECK(!minmax_dev || is_device_ptr(minmax_dev), ME_ERR_BAD_ARG, "me_output_depth_map_jpeg: minmax_dev");
-    check_jpeg_encode_args("me_output_depth_map_jpeg", data_width, data_height, quality, subsampling);
-    check_jpeg_encode_args("me_output_depth_map_jpeg", out_w, out_h, quality, subsampling);
-    const int64_t count = (int64_t)data_width * data_height;
-    const float* d = (const float*)to_device(ctx, depth, (size_t)count * 4, "out.depth");
-    // output.rs:124-131 the colour map in data order, :133-137 the resize, :138 the save
-    uint8_t* mapped = (uint8_t*)site_buf(ctx, "out.rgb.native", (size_t)count * 3);
-    depthmap_rgb_launch(d, count, min_depth, max_depth, minmax_dev, mapped, ctx->stream);
-    uint8_t* rgb = (uint8_t*)site_buf(ctx, "out.rgb", (size_t)out_w * out_h * 3);
-    resize_lanczos3_rgb8(ctx, mapped, data_width, data_height, rgb, out_w, out_h);
-    write_jpeg_file(ctx, jpeg_encode_device(ctx, rgb, out_w, out_h, quality, subsampling), destination_path);
-    ME_JPEGENC_API_END(ctx)
-}
-
-extern "C" int32_t me_output_stereogram_jpeg(me_ctx* ctx, const float* depth, int32_t rows, int32_t cols, float min_depth,
-                                             float max_depth, int32_t out_w, int32_t out_h, float amplitude,
-                                             const uint8_t* noise, int32_t quality, int32_t subsampling,
-                                             const char* destination_path) {
-    ME_JPEGENC_API_BEGIN(ctx)
-    OutputScope out_scope(ctx, depth);
-    ME_CHECK(depth && noise && destination_path, ME_ERR_BAD_ARG, "me_output_stereogram_jpeg: null pointer");
-    ME_CHECK(rows > 0 && cols > 0, ME_ERR_BAD_SHAPE, "me_output_stereogram_jpeg: %dx%d -> %dx%d", rows, cols, out_w, out_h);
-    check_jpeg_encode_args("me_output_stereogram_jpeg", out_w, out_h, quality, subsampling);
-    const size_t nout = (size_t)out_w * out_h * 3;
-    const float* d = (const float*)to_device(ctx, depth, (size_t)rows * cols * 4, "out.depth");
-    const uint8_t* nz = (const uint8_t*)to_device(ctx, noise, nout, "out.noise");
-    uint8_t* rgb = (uint8_t*)site_buf(ctx, "out.stereo", nout);
-    stereogram_launch(d, rows, cols, min_depth, max_depth, nullptr, out_w, out_h, amplitude, nz, rgb, ctx->stream);
-    write_jpeg_file(ctx, jpeg_encode_device(ctx, rgb, out_w, out_h, quality, subsampling), destination_path);
-    ME_JPEGENC_API_END(ctx)
-}
-
 extern "C" int32_t me_last_jpeg_encode(me_ctx* ctx, int64_t report[10], double ms[6]) {
-    ME_JPEGENC_API_BEGIN(ctx)
+    ME_API_BEGIN(ctx)
     ME_CHECK(report && ms, ME_ERR_BAD_ARG, "me_last_jpeg_encode: null pointer");
     ME_CHECK(ctx->jpeg_encode_reported, ME_ERR_NOT_READY, "me_last_jpeg_encode: no JPEG encode has completed on this context");
     const JpegEncodeReport& r = ctx->jpeg_encode_report;
@@ -376,7 +280,7 @@ extern "C" int32_t me_last_jpeg_encode(me_ctx* ctx, int64_t report[10], double m
         if (i < 5 || r.downloaded) ME_HIP(hipEventElapsedTime(&t, ctx->jpeg_encode_ev[i], ctx->jpeg_encode_ev[i + 1]));
         ms[i] = t;
     }
-    ME_JPEGENC_API_END(ctx)
+    ME_API_END(ctx)
 }
 
 extern "C" int32_t me_op_jpeg_encode_host(const uint8_t* rgb, int32_t w, int32_t h, int32_t quality, int32_t subsampling,

@@ -338,27 +338,18 @@ extern "C" int32_t me_mesh_obj_text(me_ctx* ctx, const float* depth, int32_t wid
                                     uint32_t original_width, uint32_t original_height, const char* stem,
                                     int32_t vertex_mode, const uint8_t* vertex_colors, const uint8_t** text_dev,
                                     int64_t* nbytes) {
-    if (!ctx) return ME_ERR_BAD_ARG;
-    try {
-        ME_HIP(hipSetDevice(ctx->device));
-        ME_CHECK(depth && stem && text_dev && nbytes, ME_ERR_BAD_ARG, "me_mesh_obj_text: null pointer");
-        ME_CHECK(vertex_mode >= ME_VERTEX_PLAIN && vertex_mode <= ME_VERTEX_TEXTURE, ME_ERR_BAD_ARG,
-                 "vertex mode %d", vertex_mode);
-        ME_CHECK(width >= 2 && height >= 2, ME_ERR_BAD_SHAPE, "me_mesh_obj_text: %dx%d", width, height);
-        ME_CHECK(original_width > 0 && original_height > 0, ME_ERR_BAD_ARG, "original size 0");
-        OutputScope out_scope(ctx, depth);
-        const DeviceMesh m = build_mesh(ctx, depth, width, height, original_width, original_height);
-        const DeviceText t = obj_text_on_device(ctx, m, width, height, stem, vertex_mode, vertex_colors);
-        ME_HIP(hipStreamSynchronize(ctx->stream));
-        *text_dev = (const uint8_t*)t.dev, *nbytes = t.bytes;
-    } catch (const me::Error& e) {
-        ctx->last_error = e.msg;
-        return e.code;
-    } catch (const std::exception& e) {
-        ctx->last_error = std::string("internal: ") + e.what();
-        return ME_ERR_BAD_ARG;
-    }
-    return ME_OK;
+    ME_API_BEGIN(ctx)
+    ME_CHECK(depth && stem && text_dev && nbytes, ME_ERR_BAD_ARG, "me_mesh_obj_text: null pointer");
+    ME_CHECK(vertex_mode >= ME_VERTEX_PLAIN && vertex_mode <= ME_VERTEX_TEXTURE, ME_ERR_BAD_ARG,
+             "vertex mode %d", vertex_mode);
+    ME_CHECK(width >= 2 && height >= 2, ME_ERR_BAD_SHAPE, "me_mesh_obj_text: %dx%d", width, height);
+    ME_CHECK(original_width > 0 && original_height > 0, ME_ERR_BAD_ARG, "original size 0");
+    OutputScope out_scope(ctx, depth);
+    const DeviceMesh m = build_mesh(ctx, depth, width, height, original_width, original_height);
+    const DeviceText t = obj_text_on_device(ctx, m, width, height, stem, vertex_mode, vertex_colors);
+    ME_HIP(hipStreamSynchronize(ctx->stream));
+    *text_dev = (const uint8_t*)t.dev, *nbytes = t.bytes;
+    ME_API_END(ctx)
 }
 
 extern "C" int32_t me_output_mesh(me_ctx* ctx, const float* depth, int32_t width, int32_t height,

@@ -1,5 +1,6 @@
 // Context, packed weights and stage functions of the Depth Pro forward pass.
 #pragma once
+#include <exception>
 #include <map>
 #include <string>
 #include <thread>
@@ -361,6 +362,15 @@ bool is_device_ptr(const void* p);
 const void* to_device(me_ctx* ctx, const void* p, size_t bytes, const std::string& name);
 // device result -> caller pointer (host or device)
 void from_device(me_ctx* ctx, void* dst, const void* src_dev, size_t bytes);
+// a caller's output pointer (api.hip): itself if it is device memory, else site buffer `name`, which finish copies out
+struct OutBuf {
+    void* dev = nullptr;
+    void* user = nullptr;
+    size_t bytes = 0;
+    bool staged = false;
+};
+OutBuf out_buf(me_ctx* ctx, void* user, size_t bytes, const std::string& name);
+void finish(me_ctx* ctx, const OutBuf& o);
 
 // ---- stages (all device pointers; see pipeline.hip) ----
 struct VitTaps {
@@ -406,6 +416,8 @@ struct OutputScope {
 // resample.hip: DynamicImage::resize_exact(nw, nh, Lanczos3) for 8-bit RGB, device pointers, on ctx->stream
 void resize_lanczos3_rgb8(me_ctx* ctx, const uint8_t* src_dev, int32_t w, int32_t h, uint8_t* dst_dev, int32_t nw, int32_t nh);
 void free_resample_tables(me_ctx* ctx);
+// api.hip: the sizes a resize entry accepts (ME_ERR_BAD_SHAPE otherwise, in the name of entry `who`)
+void check_resize_shape(const char* who, int32_t w, int32_t h, int32_t nw, int32_t nh);
 
 // jpeg_decode.hip: a JPEG file in host memory -> its oriented RGB picture [oh][ow][3] in device memory, on ctx->stream.
 // Throws me::Error (ME_ERR_BAD_ARG with the host decoder's message for a file it refuses, ME_ERR_BAD_SHAPE for a size that
@@ -421,10 +433,39 @@ int16_t* jpeg_pinned_buffer(me_ctx* ctx, size_t count);
 bool jpeg_entropy_decode(me_ctx* ctx, const std::vector<uint8_t>& file, int32_t subseq_bits,
                          matrix_eyes::JpegEntropyPlan& plan);
 void free_jpeg_entropy_scratch(me_ctx* ctx);
-// jpeg_encode.hip
+// png_encode.hip, jpeg_encode.hip: a finished file in the context's scratch, and the encoders that leave one there.  Both
+// synchronise (the file's size comes back to the host); the entries (output_api.hip) check the arguments first.
+struct DeviceFile {
+    const uint8_t* dev = nullptr;
+    int64_t bytes = 0;
+};
+void check_png_shape(const char* who, int32_t w, int32_t h);
+DeviceFile png_encode_device(me_ctx* ctx, const uint8_t* rgb_dev, int32_t w, int32_t h);
+void check_jpeg_encode_args(const char* who, int32_t w, int32_t h, int32_t quality, int32_t subsampling);
+DeviceFile jpeg_encode_device(me_ctx* ctx, const uint8_t* rgb_any, int32_t w, int32_t h, int32_t quality, int32_t subsampling);
 void free_jpeg_encode_scratch(me_ctx* ctx);
 
 // calibrate.hip: the two fixed loops of bench.py's calibration leg (out[6])
 void calibrate(me_ctx* ctx, double* out);
 
 }  // namespace me
+
+// Every extern "C" entry that takes a context: nothing throws across the boundary.  An me::Error becomes its code and the
+// context's last_error; the calling thread's status word is the context's for the kernels that raise bits in it.
+#define ME_API_BEGIN(ctx)                      \
+    if (!(ctx)) return ME_ERR_BAD_ARG;         \
+    try {                                      \
+        ME_HIP(hipSetDevice((ctx)->device));   \
+        me::set_current_status_word((ctx)->status_dev);
+
+#define ME_API_END(ctx)                                           \
+    }                                                             \
+    catch (const me::Error& e) {                                  \
+        (ctx)->last_error = e.msg;                                \
+        return e.code;                                            \
+    }                                                             \
+    catch (const std::exception& e) {                             \
+        (ctx)->last_error = std::string("internal: ") + e.what(); \
+        return ME_ERR_BAD_ARG;                                    \
+    }                                                             \
+    return ME_OK;

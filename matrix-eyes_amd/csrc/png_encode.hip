@@ -7,11 +7,6 @@
 //                       signature, IHDR, IEND
 //   png_gather_kernel   one workgroup per chunk: its IDAT (one per deflate chunk) with the CRC-32, into the file
 // The chunk kernels never wait for each other and use integer atomics only: the file is a pure function of the picture.
-#include <cerrno>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
 #include "model.h"
 #include "png_chunk.h"
 
@@ -45,10 +40,9 @@ __global__ __launch_bounds__(me_png::kThreads) void png_gather_kernel(const me_p
     me_png::gather_idat(S, info, slots + c * me_png::kSlot, c, nchunks, offsets, meta, file);
 }
 
-struct DevicePng {
-    const uint8_t* dev = nullptr;
-    int64_t bytes = 0;
-};
+}  // namespace
+
+namespace me {
 
 void check_png_shape(const char* who, int32_t w, int32_t h) {
     ME_CHECK(w > 0 && h > 0, ME_ERR_BAD_SHAPE, "%s: %dx%d", who, w, h);
@@ -57,7 +51,7 @@ void check_png_shape(const char* who, int32_t w, int32_t h) {
 }
 
 // rgb [h,w,3] in device memory -> the file in the context's scratch; synchronises (the size comes back to the host)
-DevicePng png_encode_device(me_ctx* ctx, const uint8_t* rgb, int32_t w, int32_t h) {
+DeviceFile png_encode_device(me_ctx* ctx, const uint8_t* rgb, int32_t w, int32_t h) {
     using namespace me_png;
     hipStream_t s = ctx->stream;
     // the output back end may run on its own stream (me_ctx_set_output_overlap): its scratch is its own
@@ -86,98 +80,9 @@ DevicePng png_encode_device(me_ctx* ctx, const uint8_t* rgb, int32_t w, int32_t 
     ME_CHECK(host_meta[0] > 0 && (size_t)host_meta[0] <= capacity && !(host_meta[2] & 2), ME_ERR_HIP,
              "png: a chunk's packed size differs from its estimate (file %lld bytes, flags %lld)", (long long)host_meta[0],
              (long long)host_meta[2]);
-    DevicePng f;
+    DeviceFile f;
     f.dev = file, f.bytes = host_meta[0];
     return f;
 }
 
-void write_png_file(me_ctx* ctx, const DevicePng& f, const char* path) {
-    std::vector<uint8_t> host((size_t)f.bytes);
-    ME_HIP(hipMemcpyAsync(host.data(), f.dev, host.size(), hipMemcpyDeviceToHost, ctx->stream));
-    ME_HIP(hipStreamSynchronize(ctx->stream));
-    FILE* fp = fopen(path, "wb");
-    ME_CHECK(fp, ME_ERR_IO, "cannot create %s: %s", path, strerror(errno));
-    const bool ok = fwrite(host.data(), 1, host.size(), fp) == host.size();
-    const int werr = errno;
-    const int r = fclose(fp);
-    ME_CHECK(ok, ME_ERR_IO, "write failed: %s: %s", path, strerror(werr));
-    ME_CHECK(r == 0, ME_ERR_IO, "close failed: %s: %s", path, strerror(errno));
-}
-
-}  // namespace
-
-#define ME_PNG_API_BEGIN(ctx)                   \
-    if (!(ctx)) return ME_ERR_BAD_ARG;          \
-    try {                                       \
-        ME_HIP(hipSetDevice((ctx)->device));
-
-#define ME_PNG_API_END(ctx)                                       \
-    }                                                             \
-    catch (const me::Error& e) {                                  \
-        (ctx)->last_error = e.msg;                                \
-        return e.code;                                            \
-    }                                                             \
-    catch (const std::exception& e) {                             \
-        (ctx)->last_error = std::string("internal: ") + e.what(); \
-        return ME_ERR_BAD_ARG;                                    \
-    }                                                             \
-    return ME_OK;
-
-extern "C" int32_t me_png_encode_rgb8(me_ctx* ctx, const uint8_t* rgb, int32_t w, int32_t h, const uint8_t** png_dev,
-                                      int64_t* nbytes) {
-    ME_PNG_API_BEGIN(ctx)
-    ME_CHECK(rgb && png_dev && nbytes, ME_ERR_BAD_ARG, "me_png_encode_rgb8: null pointer");
-    check_png_shape("me_png_encode_rgb8", w, h);
-    OutputScope out_scope(ctx, is_device_ptr(rgb) ? rgb : nullptr);
-    const uint8_t* d = (const uint8_t*)to_device(ctx, rgb, (size_t)w * h * 3, "png.rgb");
-    const DevicePng f = png_encode_device(ctx, d, w, h);
-    *png_dev = f.dev, *nbytes = f.bytes;
-    ME_PNG_API_END(ctx)
-}
-
-extern "C" int32_t me_output_png(me_ctx* ctx, const uint8_t* rgb, int32_t w, int32_t h, const char* destination_path) {
-    ME_PNG_API_BEGIN(ctx)
-    ME_CHECK(rgb && destination_path, ME_ERR_BAD_ARG, "me_output_png: null pointer");
-    check_png_shape("me_output_png", w, h);
-    OutputScope out_scope(ctx, is_device_ptr(rgb) ? rgb : nullptr);
-    const uint8_t* d = (const uint8_t*)to_device(ctx, rgb, (size_t)w * h * 3, "png.rgb");
-    write_png_file(ctx, png_encode_device(ctx, d, w, h), destination_path);
-    ME_PNG_API_END(ctx)
-}
-
-extern "C" int32_t me_output_depth_map_png(me_ctx* ctx, const float* depth, int32_t data_width, int32_t data_height,
-                                           float min_depth, float max_depth, const float* minmax_dev, int32_t out_w,
-                                           int32_t out_h, const char* destination_path) {
-    ME_PNG_API_BEGIN(ctx)
-    OutputScope out_scope(ctx, depth);
-    ME_CHECK(depth && destination_path, ME_ERR_BAD_ARG, "me_output_depth_map_png: null pointer");
-    ME_CHECK(!minmax_dev || is_device_ptr(minmax_dev), ME_ERR_BAD_ARG, "me_output_depth_map_png: minmax_dev");
-    check_png_shape("me_output_depth_map_png", data_width, data_height);
-    check_png_shape("me_output_depth_map_png", out_w, out_h);
-    const int64_t count = (int64_t)data_width * data_height;
-    const float* d = (const float*)to_device(ctx, depth, (size_t)count * 4, "out.depth");
-    // output.rs:124-131 the colour map in data order, :133-137 the resize, :138 the save
-    uint8_t* mapped = (uint8_t*)site_buf(ctx, "out.rgb.native", (size_t)count * 3);
-    depthmap_rgb_launch(d, count, min_depth, max_depth, minmax_dev, mapped, ctx->stream);
-    uint8_t* rgb = (uint8_t*)site_buf(ctx, "out.rgb", (size_t)out_w * out_h * 3);
-    resize_lanczos3_rgb8(ctx, mapped, data_width, data_height, rgb, out_w, out_h);
-    write_png_file(ctx, png_encode_device(ctx, rgb, out_w, out_h), destination_path);
-    ME_PNG_API_END(ctx)
-}
-
-extern "C" int32_t me_output_stereogram_png(me_ctx* ctx, const float* depth, int32_t rows, int32_t cols, float min_depth,
-                                            float max_depth, int32_t out_w, int32_t out_h, float amplitude,
-                                            const uint8_t* noise, const char* destination_path) {
-    ME_PNG_API_BEGIN(ctx)
-    OutputScope out_scope(ctx, depth);
-    ME_CHECK(depth && noise && destination_path, ME_ERR_BAD_ARG, "me_output_stereogram_png: null pointer");
-    ME_CHECK(rows > 0 && cols > 0, ME_ERR_BAD_SHAPE, "me_output_stereogram_png: %dx%d -> %dx%d", rows, cols, out_w, out_h);
-    check_png_shape("me_output_stereogram_png", out_w, out_h);
-    const size_t nout = (size_t)out_w * out_h * 3;
-    const float* d = (const float*)to_device(ctx, depth, (size_t)rows * cols * 4, "out.depth");
-    const uint8_t* nz = (const uint8_t*)to_device(ctx, noise, nout, "out.noise");
-    uint8_t* rgb = (uint8_t*)site_buf(ctx, "out.stereo", nout);
-    stereogram_launch(d, rows, cols, min_depth, max_depth, nullptr, out_w, out_h, amplitude, nz, rgb, ctx->stream);
-    write_png_file(ctx, png_encode_device(ctx, rgb, out_w, out_h), destination_path);
-    ME_PNG_API_END(ctx)
-}
+}  // namespace me

@@ -45,6 +45,16 @@ def _out(out, shape, dtype=np.float32):
     return C.c_void_p(out.ctypes.data), out
 
 
+def _resolve_choice(value, env_name, default, choices, what, alias=None):
+    """`value`, or with None the environment's `env_name` (unset: `default`), if it is one of `choices`: itself, or what
+    `alias` names for it.  Anything else is an argument error that calls the setting `what`."""
+    if value is None:
+        value = os.environ.get(env_name, default)
+    if value not in choices:
+        raise L.MatrixEyesError(1, f"{what} {value!r}: expected one of {', '.join(choices)}")
+    return (alias or {}).get(value, value)
+
+
 RESAMPLERS = ("pillow", "device")
 
 
@@ -53,10 +63,7 @@ def resolve_resampler(resampler=None) -> str:
     default: Pillow's filter, within one code of the reference's) or "device" (me_resize_lanczos3_rgb8: the `image`
     crate's sampler byte for byte, as the compiled CLI runs it).  None reads MATRIX_EYES_RESAMPLER; anything but the
     two names is an argument error."""
-    value = os.environ.get("MATRIX_EYES_RESAMPLER", "pillow") if resampler is None else resampler
-    if value not in RESAMPLERS:
-        raise L.MatrixEyesError(1, f"resampler {value!r}: expected one of {', '.join(RESAMPLERS)}")
-    return value
+    return _resolve_choice(resampler, "MATRIX_EYES_RESAMPLER", "pillow", RESAMPLERS, "resampler")
 
 
 PNG_ENCODERS = ("pillow", "device")
@@ -67,10 +74,7 @@ def resolve_png_encoder(png_encoder=None) -> str:
     (me_output_png and the two whole-method calls: row filters, deflate and CRCs on the GPU, only the file's bytes come
     back).  The files decode to the same pixels.  None reads MATRIX_EYES_PNG_ENCODER; anything but the two names is an
     argument error."""
-    value = os.environ.get("MATRIX_EYES_PNG_ENCODER", "pillow") if png_encoder is None else png_encoder
-    if value not in PNG_ENCODERS:
-        raise L.MatrixEyesError(1, f"png encoder {value!r}: expected one of {', '.join(PNG_ENCODERS)}")
-    return value
+    return _resolve_choice(png_encoder, "MATRIX_EYES_PNG_ENCODER", "pillow", PNG_ENCODERS, "png encoder")
 
 
 JPEG_ENCODERS = ("pillow", "host", "device")
@@ -83,10 +87,7 @@ def resolve_jpeg_encoder(jpeg_encoder=None) -> str:
     calls: colour conversion, DCT, Huffman coding and byte stuffing on the GPU, only the file's bytes come back).  With the
     same quality and subsampling both write the same file, byte for byte.  None reads MATRIX_EYES_JPEG_ENCODER; anything
     but these names is an argument error."""
-    value = os.environ.get("MATRIX_EYES_JPEG_ENCODER", "pillow") if jpeg_encoder is None else jpeg_encoder
-    if value not in JPEG_ENCODERS:
-        raise L.MatrixEyesError(1, f"jpeg encoder {value!r}: expected one of {', '.join(JPEG_ENCODERS)}")
-    return "pillow" if value == "host" else value
+    return _resolve_choice(jpeg_encoder, "MATRIX_EYES_JPEG_ENCODER", "pillow", JPEG_ENCODERS, "jpeg encoder", {"host": "pillow"})
 
 
 def resolve_jpeg_quality(jpeg_quality=None) -> int:
@@ -106,12 +107,10 @@ def resolve_jpeg_subsampling(jpeg_subsampling=None) -> int:
     """The chroma subsampling a ".jpg" destination is written with, as Pillow numbers it: "4:4:4" -> 0, "4:2:2" -> 1,
     "4:2:0" -> 2 (the numbers are accepted too).  None reads MATRIX_EYES_JPEG_SUBSAMPLING (default "4:2:0", Pillow's own);
     anything else is an argument error."""
-    value = os.environ.get("MATRIX_EYES_JPEG_SUBSAMPLING", "4:2:0") if jpeg_subsampling is None else jpeg_subsampling
-    if value in JPEG_SUBSAMPLINGS:
-        return JPEG_SUBSAMPLINGS[value]
-    if not isinstance(value, (bool, str)) and value in (0, 1, 2):
-        return int(value)
-    raise L.MatrixEyesError(1, f"jpeg subsampling {value!r}: expected one of {', '.join(JPEG_SUBSAMPLINGS)}")
+    if not isinstance(jpeg_subsampling, (bool, str)) and jpeg_subsampling in (0, 1, 2):
+        return int(jpeg_subsampling)
+    return _resolve_choice(jpeg_subsampling, "MATRIX_EYES_JPEG_SUBSAMPLING", "4:2:0", JPEG_SUBSAMPLINGS, "jpeg subsampling",
+                           JPEG_SUBSAMPLINGS)
 
 
 JPEG_DECODERS = ("pillow", "host", "device")
@@ -122,10 +121,7 @@ def resolve_jpeg_decoder(jpeg_decoder=None) -> str:
     CLI's name for its own decoder, means the same here) or "device" (me_jpeg_decode_rgb8 / me_jpeg_decode_resized_rgb8:
     entropy decoding on the host, reconstruction and orientation on the GPU, the C++ host decoder's bytes).  None reads
     MATRIX_EYES_JPEG_DECODER; anything but these names is an argument error."""
-    value = os.environ.get("MATRIX_EYES_JPEG_DECODER", "pillow") if jpeg_decoder is None else jpeg_decoder
-    if value not in JPEG_DECODERS:
-        raise L.MatrixEyesError(1, f"jpeg decoder {value!r}: expected one of {', '.join(JPEG_DECODERS)}")
-    return "pillow" if value == "host" else value
+    return _resolve_choice(jpeg_decoder, "MATRIX_EYES_JPEG_DECODER", "pillow", JPEG_DECODERS, "jpeg decoder", {"host": "pillow"})
 
 
 JPEG_ENTROPIES = ("host", "device")
@@ -137,10 +133,23 @@ def resolve_jpeg_entropy(jpeg_entropy=None) -> str:
     Huffman-decoded on the GPU; a file that decoder declines -- progressive, several scans, damaged -- takes the host loop).
     The same bytes either way.  Acts only with jpeg_decoder "device".  None reads MATRIX_EYES_JPEG_ENTROPY; anything but
     the two names is an argument error."""
-    value = os.environ.get("MATRIX_EYES_JPEG_ENTROPY", "host") if jpeg_entropy is None else jpeg_entropy
-    if value not in JPEG_ENTROPIES:
-        raise L.MatrixEyesError(1, f"jpeg entropy decoder {value!r}: expected one of {', '.join(JPEG_ENTROPIES)}")
-    return value
+    return _resolve_choice(jpeg_entropy, "MATRIX_EYES_JPEG_ENTROPY", "host", JPEG_ENTROPIES, "jpeg entropy decoder")
+
+
+class _DevMem:
+    """`nbytes` of device memory at `ptr`, as torch.as_tensor takes it"""
+
+    def __init__(self, ptr, nbytes):
+        self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
+
+
+def _device_file(ptr, n, rgb):
+    """The context-owned file of `n` bytes at `ptr` for the caller who passed `rgb`: numpy in -> `bytes`; a CUDA torch
+    tensor in -> a CUDA uint8 tensor on its device (a copy)."""
+    import torch
+    on_device = _is_torch(rgb) and rgb.is_cuda
+    file = torch.as_tensor(_DevMem(int(ptr.value), int(n.value)), device=rgb.device if on_device else "cuda")
+    return file.clone() if on_device else file.cpu().numpy().tobytes()
 
 
 class Context:
@@ -316,11 +325,6 @@ class Context:
         """The packed weight arena as a zero-copy uint8 torch tensor on this context's GPU (for a
         caller-side collective)."""
         import torch
-
-        class _DevMem:
-            def __init__(self, ptr, nbytes):
-                self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1",
-                                                 "data": (ptr, False), "version": 2}
         ptr = self.lib.me_weight_arena_ptr(self._h)
         return torch.as_tensor(_DevMem(int(ptr), self.weight_arena_bytes()), device="cuda")
 
@@ -436,14 +440,7 @@ class Context:
         p, keep = _in_ptr(rgb, np.uint8)
         ptr, n = C.c_void_p(), C.c_int64()
         self._check(self.lib.me_png_encode_rgb8(self._h, p, w, h, C.byref(ptr), C.byref(n)))
-        import torch
-
-        class _DevMem:
-            def __init__(self, ptr, nbytes):
-                self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
-        on_device = _is_torch(rgb) and rgb.is_cuda
-        file = torch.as_tensor(_DevMem(int(ptr.value), int(n.value)), device=rgb.device if on_device else "cuda")
-        return file.clone() if on_device else file.cpu().numpy().tobytes()
+        return _device_file(ptr, n, rgb)
 
     def output_png(self, rgb, destination_path: str):
         """png_encode, copied to the host once and written to destination_path (me_output_png)"""
@@ -459,14 +456,7 @@ class Context:
         p, keep = _in_ptr(rgb, np.uint8)
         ptr, n = C.c_void_p(), C.c_int64()
         self._check(self.lib.me_jpeg_encode_rgb8(self._h, p, w, h, int(quality), int(subsampling), C.byref(ptr), C.byref(n)))
-        import torch
-
-        class _DevMem:
-            def __init__(self, ptr, nbytes):
-                self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
-        on_device = _is_torch(rgb) and rgb.is_cuda
-        file = torch.as_tensor(_DevMem(int(ptr.value), int(n.value)), device=rgb.device if on_device else "cuda")
-        return file.clone() if on_device else file.cpu().numpy().tobytes()
+        return _device_file(ptr, n, rgb)
 
     def output_jpeg(self, rgb, destination_path: str, quality: int = 75, subsampling: int = 2):
         """jpeg_encode, copied to the host once and written to destination_path (me_output_jpeg)"""

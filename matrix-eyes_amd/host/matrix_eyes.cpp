@@ -41,6 +41,24 @@ uint32_t round_u32(float x) {
 
 bool is_jpeg_name(const std::string& path) { return ends_with_ci(path, ".jpg") || ends_with_ci(path, ".jpeg"); }
 
+// NAME=host | device in the environment -> whether the device does it; unset: `fallback`
+bool env_host_or_device(const char* name, bool fallback) {
+    const char* value = std::getenv(name);
+    if (!value) return fallback;
+    if (std::strcmp(value, "device") == 0) return true;
+    if (std::strcmp(value, "host") != 0) throw ModelError(ME_ERR_BAD_ARG, std::string(name) + "=" + value + ": expected host or device");
+    return false;
+}
+
+// save_image for the output methods: its ImageError is their OutputError
+void save_or_throw(const RgbImage& image, const std::string& path) {
+    try {
+        save_image(image, path);
+    } catch (const ImageError& err) {
+        throw output::OutputError(err.what());
+    }
+}
+
 void progress_trampoline(void* user, float pos, const char* message) {
     ProgressListener* pl = (ProgressListener*)user;
     pl->report_status(pos);
@@ -54,42 +72,17 @@ Device::Device() {
     const char* dev = std::getenv("MATRIX_EYES_DEVICE");
     const char* dt = std::getenv("MATRIX_EYES_DTYPE");
     const char* model = std::getenv("MATRIX_EYES_MODEL");  // "tiny": the test geometry of the parity suite
-    if (const char* rs = std::getenv("MATRIX_EYES_RESAMPLER")) {
-        if (std::strcmp(rs, "host") == 0)
-            device_resampler_ = false;
-        else if (std::strcmp(rs, "device") != 0)
-            throw ModelError(ME_ERR_BAD_ARG, std::string("MATRIX_EYES_RESAMPLER=") + rs + ": expected host or device");
-    }
-    if (const char* pe = std::getenv("MATRIX_EYES_PNG_ENCODER")) {
-        if (std::strcmp(pe, "device") == 0)
-            device_png_encoder_ = true;
-        else if (std::strcmp(pe, "host") != 0)
-            throw ModelError(ME_ERR_BAD_ARG, std::string("MATRIX_EYES_PNG_ENCODER=") + pe + ": expected host or device");
-    }
-    if (const char* jd = std::getenv("MATRIX_EYES_JPEG_DECODER")) {
-        if (std::strcmp(jd, "device") == 0)
-            device_jpeg_decoder_ = true;
-        else if (std::strcmp(jd, "host") != 0)
-            throw ModelError(ME_ERR_BAD_ARG, std::string("MATRIX_EYES_JPEG_DECODER=") + jd + ": expected host or device");
-    }
-    if (const char* je = std::getenv("MATRIX_EYES_JPEG_ENCODER")) {
-        if (std::strcmp(je, "device") == 0)
-            device_jpeg_encoder_ = true;
-        else if (std::strcmp(je, "host") != 0)
-            throw ModelError(ME_ERR_BAD_ARG, std::string("MATRIX_EYES_JPEG_ENCODER=") + je + ": expected host or device");
-    }
+    device_resampler_ = env_host_or_device("MATRIX_EYES_RESAMPLER", true);
+    device_png_encoder_ = env_host_or_device("MATRIX_EYES_PNG_ENCODER", false);
+    device_jpeg_decoder_ = env_host_or_device("MATRIX_EYES_JPEG_DECODER", false);
+    device_jpeg_encoder_ = env_host_or_device("MATRIX_EYES_JPEG_ENCODER", false);
     try {  // MATRIX_EYES_JPEG_QUALITY, MATRIX_EYES_JPEG_SUBSAMPLING: refused here, not at the first ".jpg" written
         jpeg_params_ = jpeg_output_params();
     } catch (const ImageError& err) {
         throw ModelError(ME_ERR_BAD_ARG, err.what());
     }
-    bool device_jpeg_entropy = false;  // acts only behind MATRIX_EYES_JPEG_DECODER=device: the host decoder has one entropy loop
-    if (const char* je = std::getenv("MATRIX_EYES_JPEG_ENTROPY")) {
-        if (std::strcmp(je, "device") == 0)
-            device_jpeg_entropy = true;
-        else if (std::strcmp(je, "host") != 0)
-            throw ModelError(ME_ERR_BAD_ARG, std::string("MATRIX_EYES_JPEG_ENTROPY=") + je + ": expected host or device");
-    }
+    // acts only behind MATRIX_EYES_JPEG_DECODER=device: the host decoder has one entropy loop
+    const bool device_jpeg_entropy = env_host_or_device("MATRIX_EYES_JPEG_ENTROPY", false);
     me_model_config cfg;
     me_default_config(&cfg);
     if (model && std::strcmp(model, "tiny") == 0) {
@@ -236,12 +229,7 @@ void DepthMap::output_depth_map(const std::string& destination_path) const {
         check_output(device_.ctx(), me_depthmap_rgb_resized(device_.ctx(), data_.data(), (int32_t)data_width_, (int32_t)data_height_, min_,
                                                             max_, nullptr, (int32_t)original_width_, (int32_t)original_height_,
                                                             resized.data.data()));
-        try {
-            save_image(resized, destination_path);
-        } catch (const ImageError& err) {
-            throw OutputError(err.what());
-        }
-        return;
+        return save_or_throw(resized, destination_path);
     }
     RgbImage out((uint32_t)data_width_, (uint32_t)data_height_);
     check_output(device_.ctx(), me_depthmap_rgb(device_.ctx(), data_.data(), (int64_t)data_.size(), min_, max_, out.data.data()));
@@ -283,11 +271,7 @@ void DepthMap::output_stereogram(const std::string& destination_path, std::optio
     }
     check_output(device_.ctx(), me_stereogram(device_.ctx(), data_.data(), (int32_t)data_width_, (int32_t)data_height_, min_, max_,
                                               (int32_t)w, (int32_t)h, amplitude, noise.data.data(), out.data.data()));
-    try {
-        save_image(out, destination_path);
-    } catch (const ImageError& err) {
-        throw OutputError(err.what());
-    }
+    save_or_throw(out, destination_path);
 }
 
 void DepthMap::output_mesh(const std::string& destination_path, const std::string& source_path, VertexMode mode) const {

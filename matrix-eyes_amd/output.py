@@ -9,7 +9,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib as L
-from .depth_pro import (Context, _in_ptr, resolve_jpeg_encoder, resolve_jpeg_quality, resolve_jpeg_subsampling,
+from .depth_pro import (Context, _device_file, _in_ptr, resolve_jpeg_encoder, resolve_jpeg_quality, resolve_jpeg_subsampling,
                         resolve_png_encoder, resolve_resampler)
 
 
@@ -89,16 +89,21 @@ class DepthMap:
             return w, h
         return self.original_width, self.original_height
 
-    def stereogram(self, resize_scale: Optional[float], amplitude: float, noise=None) -> np.ndarray:
-        """output.rs:141-193 -> u8 [out_h, out_w, 3].  noise u8 [out_h, out_w, 3] stands in for the
-        reference's rand::rng() stream (row by row, pixel by pixel); drawn from os.urandom-seeded
-        numpy when omitted."""
+    def _stereogram_noise(self, resize_scale, noise):
+        """(out_w, out_h, the noise's pointer, its keepalive) of the stereogram methods; noise as for `stereogram`"""
         w, h = self.stereogram_size(resize_scale)
         if noise is None:
             noise = _noise_rng().integers(0, 256, size=(h, w, 3), dtype=np.uint8)
         pn, keep = _in_ptr(noise, np.uint8)
         if tuple(noise.shape) != (h, w, 3):
             raise L.MatrixEyesError(2, f"noise must be [{h},{w},3]")
+        return w, h, pn, keep
+
+    def stereogram(self, resize_scale: Optional[float], amplitude: float, noise=None) -> np.ndarray:
+        """output.rs:141-193 -> u8 [out_h, out_w, 3].  noise u8 [out_h, out_w, 3] stands in for the
+        reference's rand::rng() stream (row by row, pixel by pixel); drawn from os.urandom-seeded
+        numpy when omitted."""
+        w, h, pn, keep = self._stereogram_noise(resize_scale, noise)
         mn, mx = self._range
         out = np.empty((h, w, 3), np.uint8)
         self.ctx._check(self.ctx.lib.me_stereogram(
@@ -148,12 +153,7 @@ class DepthMap:
 
     def output_stereogram_png(self, destination_path: str, resize_scale: Optional[float], amplitude: float, noise=None):
         """output.rs:141-193 whole, on the GPU (me_output_stereogram_png); noise as for `stereogram`"""
-        w, h = self.stereogram_size(resize_scale)
-        if noise is None:
-            noise = _noise_rng().integers(0, 256, size=(h, w, 3), dtype=np.uint8)
-        pn, keep = _in_ptr(noise, np.uint8)
-        if tuple(noise.shape) != (h, w, 3):
-            raise L.MatrixEyesError(2, f"noise must be [{h},{w},3]")
+        w, h, pn, keep = self._stereogram_noise(resize_scale, noise)
         mn, mx = self._range
         self.ctx._check(self.ctx.lib.me_output_stereogram_png(
             self.ctx.handle, C.c_void_p(self.data.ctypes.data), self.data_width, self.data_height, mn, mx,
@@ -169,12 +169,7 @@ class DepthMap:
     def output_stereogram_jpeg(self, destination_path: str, resize_scale: Optional[float], amplitude: float, noise=None,
                                quality: int = 75, subsampling: int = 2):
         """output.rs:141-193 whole, on the GPU (me_output_stereogram_jpeg); noise as for `stereogram`"""
-        w, h = self.stereogram_size(resize_scale)
-        if noise is None:
-            noise = _noise_rng().integers(0, 256, size=(h, w, 3), dtype=np.uint8)
-        pn, keep = _in_ptr(noise, np.uint8)
-        if tuple(noise.shape) != (h, w, 3):
-            raise L.MatrixEyesError(2, f"noise must be [{h},{w},3]")
+        w, h, pn, keep = self._stereogram_noise(resize_scale, noise)
         mn, mx = self._range
         self.ctx._check(self.ctx.lib.me_output_stereogram_jpeg(
             self.ctx.handle, C.c_void_p(self.data.ctypes.data), self.data_width, self.data_height, mn, mx,
@@ -193,28 +188,22 @@ class DepthMap:
         if low.endswith(".ply") or low.endswith(".obj"):
             return self.output_mesh(destination_path, source_path, vertex_mode, resampler=resampler)
         from PIL import Image
-        save_args = {}
-        if low.endswith(".jpg") or low.endswith(".jpeg"):
+        jpeg = low.endswith(".jpg") or low.endswith(".jpeg")
+        save_args, jpeg_args = {}, ()
+        if jpeg:
             # both paths are defined by the same numbers: Pillow's own defaults, spelled out
-            quality, subsampling = resolve_jpeg_quality(jpeg_quality), resolve_jpeg_subsampling(jpeg_subsampling)
+            jpeg_args = quality, subsampling = resolve_jpeg_quality(jpeg_quality), resolve_jpeg_subsampling(jpeg_subsampling)
             save_args = {"format": "JPEG", "quality": quality, "subsampling": subsampling, "optimize": False}
-            if jpeg_encoder == "device":
-                native = self.original_width == self.original_height == self.data_width == self.data_height
-                if image_format.kind != "depthmap":
-                    return self.output_stereogram_jpeg(destination_path, image_format.resize_scale, image_format.amplitude,
-                                                       noise, quality, subsampling)
-                if resampler == "device" or native:   # (the resize is the identity at the native size)
-                    return self.output_depth_map_jpeg(destination_path, quality, subsampling)
-                img = Image.fromarray(self.depth_map_rgb()).resize((self.original_width, self.original_height), Image.LANCZOS)
-                return self.ctx.output_jpeg(np.asarray(img, dtype=np.uint8), destination_path, quality, subsampling)
-        if png_encoder == "device" and low.endswith(".png"):
+        if (jpeg_encoder == "device") if jpeg else (png_encoder == "device" and low.endswith(".png")):
+            stereogram, depth_map, picture = ((self.output_stereogram_jpeg, self.output_depth_map_jpeg, self.ctx.output_jpeg) if jpeg
+                                              else (self.output_stereogram_png, self.output_depth_map_png, self.ctx.output_png))
             native = self.original_width == self.original_height == self.data_width == self.data_height
             if image_format.kind != "depthmap":
-                return self.output_stereogram_png(destination_path, image_format.resize_scale, image_format.amplitude, noise)
+                return stereogram(destination_path, image_format.resize_scale, image_format.amplitude, noise, *jpeg_args)
             if resampler == "device" or native:   # (the resize is the identity at the native size)
-                return self.output_depth_map_png(destination_path)
+                return depth_map(destination_path, *jpeg_args)
             img = Image.fromarray(self.depth_map_rgb()).resize((self.original_width, self.original_height), Image.LANCZOS)
-            return self.ctx.output_png(np.asarray(img, dtype=np.uint8), destination_path)
+            return picture(np.asarray(img, dtype=np.uint8), destination_path, *jpeg_args)
         if image_format.kind == "depthmap" and resampler == "device":
             Image.fromarray(self.depth_map_rgb_resized()).save(destination_path, **save_args)
         elif image_format.kind == "depthmap":
@@ -301,17 +290,12 @@ class DeviceDepthMap:
     def obj_text(self, stem: str = "mesh", vertex_mode: VertexMode = VertexMode.Texture, colors=None):
         """The OBJ file's bytes as a CUDA uint8 tensor (me_mesh_obj_text: the text formatted on the GPU; a copy of the
         context-owned buffer)."""
-        import torch
-
-        class _DevMem:
-            def __init__(self, ptr, nbytes):
-                self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
         ptr, n = C.c_void_p(), C.c_int64()
         self.ctx._check(self.ctx.lib.me_mesh_obj_text(
             self.ctx.handle, C.c_void_p(self.data.data_ptr()), self.data_width, self.data_height, self.original_width,
             self.original_height, stem.encode(), int(vertex_mode),
             C.c_void_p(colors.data_ptr()) if colors is not None else None, C.byref(ptr), C.byref(n)))
-        return torch.as_tensor(_DevMem(int(ptr.value), int(n.value)), device=self.data.device).clone()
+        return _device_file(ptr, n, self.data)
 
     def stereogram(self, amplitude: float, noise, out=None):
         """noise: CUDA u8 [out_h, out_w, 3]"""

@@ -4,7 +4,6 @@ file of tests/jpeg_files.py, through host and device pointers, queued back to ba
 through both command lines.  Every comparison is np.array_equal: there is no tolerance."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -13,7 +12,7 @@ import torch
 
 import matrix_eyes_amd as m
 from oracle import output_oracle as OO
-from util import ctx_for, ptr
+from util import ctx_for, ptr, run_cli, tiny_checkpoint
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import jpeg_files as J  # noqa: E402
@@ -190,10 +189,9 @@ def test_command_lines_agree(tmp_path):
     device decoder and resampler writes the same depth pixels."""
     from PIL import Image
     from matrix_eyes_amd import reconstruction as R
-    from matrix_eyes_amd.synthetic import synthetic_checkpoint
     cfg = m.ModelConfig.tiny()
     ckpt = str(tmp_path / "tiny.pt")
-    torch.save({k: torch.as_tensor(v) for k, v in synthetic_checkpoint(cfg).items()}, ckpt)
+    tiny_checkpoint(ckpt)
     src = str(tmp_path / "photo.jpg")
     exif = Image.Exif()
     exif[0x0112] = 6
@@ -203,9 +201,8 @@ def test_command_lines_agree(tmp_path):
     base = {k: v for k, v in os.environ.items() if k not in ("MATRIX_EYES_RESAMPLER", "MATRIX_EYES_JPEG_DECODER")}
 
     def cli(out, *args, **extra):
-        r = subprocess.run([CLI, f"--checkpoint-path={ckpt}", *args, src, str(tmp_path / out)],
-                           env=dict(base, MATRIX_EYES_MODEL="tiny", **extra), capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stdout + r.stderr
+        run_cli([CLI, f"--checkpoint-path={ckpt}", *args, src, str(tmp_path / out)], dict(base, MATRIX_EYES_MODEL="tiny", **extra),
+                timeout=300)
         return (tmp_path / out).read_bytes()
 
     depth_host = cli("depth_host.png", MATRIX_EYES_JPEG_DECODER="host")
@@ -217,9 +214,8 @@ def test_command_lines_agree(tmp_path):
     ply_host = cli("mesh_host.ply", "--mesh=vertex-colors", MATRIX_EYES_JPEG_DECODER="host")
     ply_dev = cli("mesh_dev.ply", "--mesh=vertex-colors", MATRIX_EYES_JPEG_DECODER="device")
     assert ply_dev == ply_host and len(ply_dev) > 1000
-    r = subprocess.run([CLI, f"--checkpoint-path={ckpt}", src, str(tmp_path / "x.png")],
-                       env=dict(base, MATRIX_EYES_MODEL="tiny", MATRIX_EYES_JPEG_DECODER="gpu"), capture_output=True, text=True,
-                       timeout=300)
+    r = run_cli([CLI, f"--checkpoint-path={ckpt}", src, str(tmp_path / "x.png")],
+                dict(base, MATRIX_EYES_MODEL="tiny", MATRIX_EYES_JPEG_DECODER="gpu"), expect=None, timeout=300)
     assert r.returncode != 0 and "MATRIX_EYES_JPEG_DECODER" in r.stdout + r.stderr        # not a silent default
 
     loader = m.DepthProModelLoader(ckpt, False, cfg)

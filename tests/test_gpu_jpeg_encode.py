@@ -8,7 +8,6 @@ One context for the module; the yardstick's files are computed once (tests/jpeg_
 import ctypes as C
 import io
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -19,6 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import jpeg_encode_pictures as P  # noqa: E402
 
 import matrix_eyes_amd as m  # noqa: E402
+from util import run_cli, tiny_checkpoint  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -230,11 +230,6 @@ def test_round_trip_on_the_device(ctx, tmp_path):
 
 # ---- both command lines ---------------------------------------------------------------------------------------------------------
 
-def _tiny_checkpoint(path):
-    from matrix_eyes_amd.synthetic import synthetic_checkpoint
-    torch.save({k: torch.as_tensor(v) for k, v in synthetic_checkpoint(m.ModelConfig.tiny()).items()}, path)
-
-
 @pytest.mark.parametrize("which", ["compiled", "python"])
 def test_command_lines(tmp_path, which):
     """MATRIX_EYES_JPEG_ENCODER=device writes the file the default (host / Pillow) writes, for the depth picture and the
@@ -245,7 +240,7 @@ def test_command_lines(tmp_path, which):
     turbo = features.check_feature("libjpeg_turbo")
     S = m.ModelConfig.tiny().img_size
     ckpt, src = str(tmp_path / "tiny.pt"), str(tmp_path / "photo.png")
-    _tiny_checkpoint(ckpt)
+    tiny_checkpoint(ckpt)
     Image.fromarray(synthetic_images(1, S, "structured", seed=11)[0]).resize((S + 88, S - 40)).save(src)
     argv = [CLI] if which == "compiled" else [sys.executable, "-m", "matrix_eyes_amd"]
     base = dict(os.environ, MATRIX_EYES_MODEL="tiny", MATRIX_EYES_SEED="7", PYTHONPATH=ROOT)
@@ -253,10 +248,7 @@ def test_command_lines(tmp_path, which):
         base.pop(name, None)
 
     def run(env, *args, expect=0):
-        r = subprocess.run(argv + [f"--checkpoint-path={ckpt}", "--focal-length=35", *args], env=env, cwd=ROOT,
-                           capture_output=True, text=True, timeout=600)
-        assert r.returncode == expect, r.stdout + r.stderr
-        return r
+        return run_cli(argv + [f"--checkpoint-path={ckpt}", "--focal-length=35", *args], env, expect)
 
     dev = dict(base, MATRIX_EYES_JPEG_ENCODER="device")
     for name, flags, extra in (("depth", [], {}),
@@ -310,6 +302,16 @@ def test_errors(ctx, tmp_path):
     assert lib.me_output_stereogram_jpeg(h, pd, 8, 8, 0.1, 1.0, 8, 8, 0.0625, pn, 75, 5, good) == BAD_ARG
     assert lib.me_output_stereogram_jpeg(h, pd, 8, 8, 0.1, 1.0, 8, 16385, 0.0625, pn, 75, 2, good) == BAD_SHAPE
     assert lib.me_output_stereogram_jpeg(h, pd, 8, 8, 0.1, 1.0, 8, 8, 0.0625, pn, 75, 2, str(tmp_path / "no" / "s.jpg").encode()) == IO
+    # wrong in two ways: the quality is checked before the picture's size, the depth's rows and columns before either; and no
+    # entry touches a missing context
+    assert lib.me_output_jpeg(h, p, 0, 8, 0, 2, good) == BAD_ARG
+    assert lib.me_output_depth_map_jpeg(h, pd, 8, 8, 0.1, 1.0, None, 0, 8, 101, 2, good) == BAD_ARG
+    assert lib.me_output_stereogram_jpeg(h, pd, 0, 8, 0.1, 1.0, 8, 8, 0.0625, pn, 101, 2, good) == BAD_SHAPE
+    assert lib.me_output_stereogram_jpeg(h, pd, 8, 8, 0.1, 1.0, 8, 16385, 0.0625, pn, 101, 2, good) == BAD_ARG
+    assert lib.me_output_jpeg(None, p, 8, 8, 75, 2, good) == BAD_ARG
+    assert lib.me_output_depth_map_jpeg(None, pd, 8, 8, 0.1, 1.0, None, 8, 8, 75, 2, good) == BAD_ARG
+    assert lib.me_output_stereogram_jpeg(None, pd, 8, 8, 0.1, 1.0, 8, 8, 0.0625, pn, 75, 2, good) == BAD_ARG
+    assert not os.path.exists(good)
     assert lib.me_last_jpeg_encode(h, None, None) == BAD_ARG
     # the context still encodes
     assert ctx.jpeg_encode(rgb, 75, 2) == P.reference("shape", 16, 16, 75, 2)[0]

@@ -6,7 +6,6 @@ host decoder, whose pixels or words stand; both command lines write the same fil
 =host.  Every comparison is np.array_equal: there is no tolerance."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -14,7 +13,7 @@ import pytest
 import torch
 
 import matrix_eyes_amd as m
-from util import ctx_for, ptr
+from util import ctx_for, ptr, run_cli, tiny_checkpoint
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import jpeg_files as J  # noqa: E402
@@ -202,10 +201,9 @@ def test_command_lines_agree(tmp_path):
     mirror writes the same depth pixels with either."""
     from PIL import Image
     from matrix_eyes_amd import reconstruction as R
-    from matrix_eyes_amd.synthetic import synthetic_checkpoint
     cfg = m.ModelConfig.tiny()
     ckpt = str(tmp_path / "tiny.pt")
-    torch.save({k: torch.as_tensor(v) for k, v in synthetic_checkpoint(cfg).items()}, ckpt)
+    tiny_checkpoint(ckpt)
     src = str(tmp_path / "photo.jpg")
     exif = Image.Exif()
     exif[0x0112] = 6
@@ -216,9 +214,8 @@ def test_command_lines_agree(tmp_path):
     base = {k: v for k, v in os.environ.items() if k not in drop}
 
     def cli(out, **extra):
-        r = subprocess.run([CLI, f"--checkpoint-path={ckpt}", src, str(tmp_path / out)],
-                           env=dict(base, MATRIX_EYES_MODEL="tiny", MATRIX_EYES_JPEG_DECODER="device", **extra),
-                           capture_output=True, text=True, timeout=300)
+        r = run_cli([CLI, f"--checkpoint-path={ckpt}", src, str(tmp_path / out)],
+                    dict(base, MATRIX_EYES_MODEL="tiny", MATRIX_EYES_JPEG_DECODER="device", **extra), expect=None, timeout=300)
         return r, ((tmp_path / out).read_bytes() if r.returncode == 0 else None)
 
     r, on_host = cli("depth_host.png", MATRIX_EYES_JPEG_ENTROPY="host")

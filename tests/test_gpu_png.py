@@ -7,7 +7,6 @@ One context for the module; the 12-megapixel pictures are encoded once each."""
 import ctypes as C
 import io
 import os
-import subprocess
 import sys
 import zlib
 
@@ -20,6 +19,7 @@ import png_check as P       # noqa: E402
 import png_pictures as pic  # noqa: E402
 
 import matrix_eyes_amd as m  # noqa: E402
+from util import run_cli, tiny_checkpoint  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -216,11 +216,6 @@ def test_output_calls_write_the_same_files(ctx, field, tmp_path):
 
 # ---- 8: both command lines ----------------------------------------------------------------------------------------------------
 
-def _tiny_checkpoint(path):
-    from matrix_eyes_amd.synthetic import synthetic_checkpoint
-    torch.save({k: torch.as_tensor(v) for k, v in synthetic_checkpoint(m.ModelConfig.tiny()).items()}, path)
-
-
 @pytest.mark.parametrize("which", ["compiled", "python"])
 def test_command_lines(tmp_path, which):
     from PIL import Image
@@ -228,17 +223,14 @@ def test_command_lines(tmp_path, which):
     assert os.path.exists(CLI), "the compiled command line is built by __graft_entry__.build()"
     S = m.ModelConfig.tiny().img_size
     ckpt, src = str(tmp_path / "tiny.pt"), str(tmp_path / "photo.png")
-    _tiny_checkpoint(ckpt)
+    tiny_checkpoint(ckpt)
     Image.fromarray(synthetic_images(1, S, "structured", seed=11)[0]).resize((S + 88, S - 40)).save(src)
     argv = [CLI] if which == "compiled" else [sys.executable, "-m", "matrix_eyes_amd"]
     base = dict(os.environ, MATRIX_EYES_MODEL="tiny", MATRIX_EYES_SEED="7", PYTHONPATH=ROOT)
     base.pop("MATRIX_EYES_PNG_ENCODER", None)
 
     def run(env, *args, expect=0):
-        r = subprocess.run(argv + [f"--checkpoint-path={ckpt}", "--focal-length=35", *args], env=env, cwd=ROOT,
-                           capture_output=True, text=True, timeout=600)
-        assert r.returncode == expect, r.stdout + r.stderr
-        return r
+        return run_cli(argv + [f"--checkpoint-path={ckpt}", "--focal-length=35", *args], env, expect)
 
     dev = dict(base, MATRIX_EYES_PNG_ENCODER="device")
     for name, flags in (("depth", []), ("stereo", ["--image-output-format=stereogram"])):
@@ -283,6 +275,11 @@ def test_errors(ctx, tmp_path):
     assert lib.me_output_stereogram_png(h, dp, 8, 8, 0.1, 1.0, 8, 8, 0.0625, None, b"x.png") == 1
     assert lib.me_output_stereogram_png(h, dp, 8, 8, 0.1, 1.0, 8, -8, 0.0625, p, b"x.png") == 2
     assert lib.me_output_stereogram_png(h, dp, 8, 8, 0.1, 1.0, 8, 8, 0.0625, p, nowhere) == 7
+    # wrong in two ways: the first check of the entry decides; and no entry touches a missing context
+    assert lib.me_output_depth_map_png(h, None, 8, 8, 0.1, 1.0, None, 0, 8, b"x.png") == 1
+    assert lib.me_output_png(None, p, 8, 8, b"x.png") == 1
+    assert lib.me_output_depth_map_png(None, dp, 8, 8, 0.1, 1.0, None, 8, 8, b"x.png") == 1
+    assert lib.me_output_stereogram_png(None, dp, 8, 8, 0.1, 1.0, 8, 8, 0.0625, p, b"x.png") == 1
     with pytest.raises(m.MatrixEyesError):
         ctx.png_encode(np.zeros((4, 4), np.uint8))
     # the context still works

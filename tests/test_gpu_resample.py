@@ -4,7 +4,6 @@ and output.rs:206-218 call -- for every size pair, through host and device point
 colour map, and through both command lines.  Every comparison is np.array_equal: there is no tolerance."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,7 +11,7 @@ import torch
 
 import matrix_eyes_amd as m
 from oracle import output_oracle as OO
-from util import ctx_for, loaded_ctx, ptr
+from util import ctx_for, loaded_ctx, ptr, run_cli, tiny_checkpoint
 
 pytestmark = pytest.mark.gpu
 
@@ -214,18 +213,16 @@ def test_command_lines_agree(tmp_path):
     resampler="device" writes the same depth pixels, which it does not with Pillow's filter."""
     from PIL import Image
     from matrix_eyes_amd import reconstruction as R
-    from matrix_eyes_amd.synthetic import synthetic_checkpoint
     cfg = m.ModelConfig.tiny()
     ckpt = str(tmp_path / "tiny.pt")
-    torch.save({k: torch.as_tensor(v) for k, v in synthetic_checkpoint(cfg).items()}, ckpt)
+    tiny_checkpoint(ckpt)
     src = str(tmp_path / "photo.png")
     Image.fromarray(photo(300, 200, 9)).save(src)
     base = {k: v for k, v in os.environ.items() if k != "MATRIX_EYES_RESAMPLER"}
 
     def cli(out, *args, **extra):
-        r = subprocess.run([CLI, f"--checkpoint-path={ckpt}", "--focal-length=35", *args, src, str(tmp_path / out)],
-                           env=dict(base, MATRIX_EYES_MODEL="tiny", **extra), capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stdout + r.stderr
+        run_cli([CLI, f"--checkpoint-path={ckpt}", "--focal-length=35", *args, src, str(tmp_path / out)],
+                dict(base, MATRIX_EYES_MODEL="tiny", **extra), timeout=300)
         return (tmp_path / out).read_bytes()
 
     depth_dev = cli("depth_dev.png")
@@ -234,9 +231,8 @@ def test_command_lines_agree(tmp_path):
     ply_dev = cli("mesh_dev.ply", "--mesh=vertex-colors")
     ply_host = cli("mesh_host.ply", "--mesh=vertex-colors", MATRIX_EYES_RESAMPLER="host")
     assert ply_dev == ply_host and len(ply_dev) > 1000
-    r = subprocess.run([CLI, f"--checkpoint-path={ckpt}", src, str(tmp_path / "x.png")],
-                       env=dict(base, MATRIX_EYES_MODEL="tiny", MATRIX_EYES_RESAMPLER="gpu"), capture_output=True, text=True,
-                       timeout=300)
+    r = run_cli([CLI, f"--checkpoint-path={ckpt}", src, str(tmp_path / "x.png")],
+                dict(base, MATRIX_EYES_MODEL="tiny", MATRIX_EYES_RESAMPLER="gpu"), expect=None, timeout=300)
     assert r.returncode != 0 and "MATRIX_EYES_RESAMPLER" in r.stdout + r.stderr          # not a silent default
 
     loader = m.DepthProModelLoader(ckpt, False, cfg)

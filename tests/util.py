@@ -1,6 +1,8 @@
 """Shared helpers of the GPU parity tests: device tensors come from torch (plumbing only), every
 compute call goes through the C ABI of libmatrixeyes_hip.so."""
 import ctypes as C
+import os
+import subprocess
 
 import numpy as np
 import torch
@@ -40,6 +42,19 @@ def loaded_ctx(cfg_name: str, dtype: str):
         ctx.load_state_dict(weights_for(cfg_name))
         _CTX[key] = ctx
     return _CTX[key]
+
+
+def tiny_checkpoint(path):
+    """The synthetic checkpoint of the tiny configuration as a torch.save file at `path` (what the command lines load)"""
+    torch.save({k: torch.as_tensor(v) for k, v in weights_for("tiny").items()}, path)
+
+
+def run_cli(argv, env, expect=0, timeout=600):
+    """One run of a command line from the repository root; its exit status must be `expect` (None: any)"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run(argv, env=env, cwd=root, capture_output=True, text=True, timeout=timeout)
+    assert expect is None or r.returncode == expect, r.stdout + r.stderr
+    return r
 
 
 def oracle_cfg(cfg: m.ModelConfig, dtype=torch.float32) -> O.OracleConfig:
