@@ -432,9 +432,9 @@ int32_t me_output_mesh(me_ctx* ctx, const float* depth, int32_t width, int32_t h
                        const char* destination_path, const char* source_path, int32_t vertex_mode,
                        const uint8_t* vertex_colors);
 
-/* Write-behind for me_output_mesh(".obj") (BASELINE configs[4]: a batch of images, each ending in a file of 70 - 450 MB).
-   files_in_flight >= 2: the call returns once the text sits in pinned host memory; a host thread writes the file (and
-   the .mtl) while the caller goes on to the next image.  That many pinned buffers are used in turn, so that many files
+/* Write-behind for me_output_mesh(".obj" and ".ply") (BASELINE configs[4]: a batch of images, each ending in a file of
+   70 - 450 MB).  files_in_flight >= 2: the call returns once the file's bytes sit in pinned host memory; a host thread
+   writes the file (and an OBJ's .mtl) while the caller goes on to the next image.  That many pinned buffers are used in turn, so that many files
    can be in flight; the next call waits for the oldest (1 is taken as 2) -- and for any pending write to its own
    destination path -- before it starts any work of its own.  A failed write is reported (ME_ERR_IO, me_last_error) by
    the call that next waits for it: a later me_output_mesh (which then has written nothing and can be repeated),
@@ -461,10 +461,20 @@ int32_t me_mesh_obj_text(me_ctx* ctx, const float* depth, int32_t width, int32_t
                          uint32_t original_height, const char* stem, int32_t vertex_mode,
                          const uint8_t* vertex_colors, const uint8_t** text_dev, int64_t* nbytes);
 
-/* Where the last me_output_mesh(".obj") call on this context spent its time, host wall clock in milliseconds:
-   ms_out[0] mesh indexing + vertex kernels (incl. their read-back of the counts), [1] the text formatting kernels,
-   [2] the D2H copy of the text into pinned memory, [3] the file write (the host kernel's page-cache copy);
-   *text_bytes (optional): the size of the file. */
+/* The PLY file of me_output_mesh without the file: the mesh is indexed and its binary records packed on the GPU
+   (output.rs:385-482 PlyWriter: x, -y, -z as big-endian f64 and, in ME_VERTEX_COLOR mode with vertex_colors, r g b per
+   vertex; the byte 3 and three big-endian u32 ids per face) behind the ASCII header.  *bytes_dev: DEVICE address, owned
+   by the context, valid until its next mesh call; *nbytes: the size of the file.  me_output_mesh(".ply") is these
+   bytes copied to the host once and written to the file. */
+int32_t me_mesh_ply_bytes(me_ctx* ctx, const float* depth, int32_t width, int32_t height,
+                          uint32_t original_width, uint32_t original_height, int32_t vertex_mode,
+                          const uint8_t* vertex_colors, const uint8_t** bytes_dev, int64_t* nbytes);
+
+/* Where the last me_output_mesh(".obj" or ".ply") call on this context spent its time, host wall clock in milliseconds:
+   ms_out[0] mesh indexing + vertex kernels (incl. their read-back of the counts), [1] the kernels that format the OBJ
+   text or pack the PLY records, [2] the D2H copy of the file's bytes into pinned memory, [3] the file write (the host
+   kernel's page-cache copy; with write-behind, the hand-over to the writing thread); *text_bytes (optional): the size
+   of the file.  (A call served by a host serialiser -- ME_OBJ_HOST_FORMAT, ME_PLY_HOST_FORMAT -- is not reported.) */
 int32_t me_last_mesh_timing(const me_ctx* ctx, double ms_out[4], int64_t* text_bytes);
 
 #ifdef __cplusplus

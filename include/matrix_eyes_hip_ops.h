@@ -189,6 +189,12 @@ int32_t me_op_attention_fp8(me_ctx* ctx, const void* qkv16, uint8_t* out8, uint8
    printed as Rust's `{}` prints an f64 -- shortest round-trip digits, positional notation -- into the `stride`-byte
    slot i of `text` (stride >= 344), its length into lengths[i]. */
 int32_t me_op_format_f64(me_ctx* ctx, const double* values, int64_t count, char* text, int32_t stride, int32_t* lengths);
+/* The record packing of the device PLY writer (csrc/ply_format.h, ply_format.hip) on its own: xyz [nverts][3] and
+   faces [nfaces][3] (vertex ids) as the binary records of me_mesh_ply_bytes, from out + header_bytes on: nverts vertex
+   records of 24 bytes, or 27 with vertex_rgb [nverts][3], then nfaces face records of 13.  Host or device pointers. */
+int32_t me_op_ply_pack(me_ctx* ctx, const float* xyz, const uint8_t* vertex_rgb /* per vertex id, or NULL */,
+                       int64_t nverts, const int32_t* faces, int64_t nfaces, int64_t header_bytes,
+                       uint8_t* out /* header_bytes + nverts*(24|27) + nfaces*13; the first header_bytes untouched */);
 /* Box calibration (csrc/calibrate.hip; bench.py's `calibration` object): two FIXED loops on the context's stream, about
    50 ms, synchronous.  out[0] = TFLOP/s of an MFMA-only loop (v_mfma_f32_16x16x32_f16, operands in registers, two waves per
    SIMD on 256 workgroups), out[1] = the shader clock the part held inside it (GHz, s_memtime / s_memrealtime),

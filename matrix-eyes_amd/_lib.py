@@ -98,6 +98,7 @@ SIGNATURES = {
     "me_mesh_vertices": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _u32, _u32, _vp, _vp]),
     "me_output_mesh": (_i32, [_vp, _vp, _i32, _i32, _u32, _u32, C.c_char_p, C.c_char_p, _i32, _vp]),
     "me_mesh_obj_text": (_i32, [_vp, _vp, _i32, _i32, _u32, _u32, C.c_char_p, _i32, _vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "me_mesh_ply_bytes": (_i32, [_vp, _vp, _i32, _i32, _u32, _u32, _i32, _vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "me_last_mesh_timing": (_i32, [_vp, C.POINTER(C.c_double), C.POINTER(_i64)]),
     "me_ctx_set_write_behind": (_i32, [_vp, _i32]),
     "me_output_flush": (_i32, [_vp]),
@@ -147,6 +148,7 @@ SIGNATURES = {
     "me_op_linear_fp8_residual_layernorm": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, C.POINTER(_vp), C.POINTER(_vp),
                                                    C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _f32, _vp, _vp, _vp]),
     "me_op_format_f64": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp]),
+    "me_op_ply_pack": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp]),
     "me_calibrate": (_i32, [_vp, C.POINTER(C.c_double)]),
     "me_op_cast_to16": (_i32, [_vp, _vp, _vp, _i64]),
     "me_op_cast_to32": (_i32, [_vp, _vp, _vp, _i64]),

@@ -1623,6 +1623,26 @@ int32_t me_op_format_f64(me_ctx* ctx, const double* values, int64_t count, char*
     ME_API_END(ctx)
 }
 
+int32_t me_op_ply_pack(me_ctx* ctx, const float* xyz, const uint8_t* vertex_rgb, int64_t nverts, const int32_t* faces,
+                       int64_t nfaces, int64_t header_bytes, uint8_t* out) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(out && nverts >= 0 && nfaces >= 0 && header_bytes >= 0 && (xyz || nverts == 0) && (faces || nfaces == 0),
+             ME_ERR_BAD_ARG, "me_op_ply_pack: bad argument");
+    ME_CHECK(nverts <= (int64_t)INT32_MAX && nfaces <= (int64_t)1 << 40, ME_ERR_BAD_ARG, "me_op_ply_pack: %lld vertices, %lld faces",
+             (long long)nverts, (long long)nfaces);
+    const bool rgb = vertex_rgb && nverts > 0;
+    const float* x = nverts ? (const float*)to_device(ctx, xyz, (size_t)nverts * 12, "op.ply.xyz") : nullptr;
+    const uint8_t* c = rgb ? (const uint8_t*)to_device(ctx, vertex_rgb, (size_t)nverts * 3, "op.ply.rgb") : nullptr;
+    const int32_t* f = nfaces ? (const int32_t*)to_device(ctx, faces, (size_t)nfaces * 12, "op.ply.faces") : nullptr;
+    const int64_t body = ply_pack_bytes(nverts, rgb, nfaces, 0);
+    if (body == 0) return ME_OK;
+    // a host `out` is staged without its header: the first header_bytes of the caller's array are never written
+    OutBuf o = out_buf(ctx, out + header_bytes, (size_t)body, "op.ply.out");
+    ply_pack_launch(x, c, nverts, f, nfaces, o.staged ? 0 : header_bytes, o.staged ? (uint8_t*)o.dev : out, ctx->stream);
+    finish(ctx, o);
+    ME_API_END(ctx)
+}
+
 int32_t me_op_cast_to16(me_ctx* ctx, const float* src, void* dst16, int64_t count) {
     ME_API_BEGIN(ctx)
     cast_f32_to_16_launch(src, dst16, count, ctx->dtype, ctx->stream);

@@ -436,5 +436,10 @@ void obj_format_write(const float* uv, const float* xyz, const uint8_t* vertex_r
 void format_f64_launch(const double* v, int64_t n, char* out, int stride, int* lens, hipStream_t stream);
 void obj_vertex_colors_launch(const int32_t* vindex, const uint8_t* pixel_rgb, int64_t npix, uint8_t* vertex_rgb,
                               hipStream_t stream);
+// Binary PLY records on the device (ply_format.hip): the vertex records (24 bytes, or 27 with vertex_rgb) and the face
+// records (13 bytes) back to back from out + header_bytes; the size of the whole file, header included
+int64_t ply_pack_bytes(int64_t nverts, bool with_rgb, int64_t nfaces, int64_t header_bytes);
+void ply_pack_launch(const float* xyz, const uint8_t* vertex_rgb, int64_t nverts, const int32_t* faces, int64_t nfaces,
+                     int64_t header_bytes, uint8_t* out, hipStream_t stream);
 
 }  // namespace me

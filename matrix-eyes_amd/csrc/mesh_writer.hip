@@ -1,6 +1,8 @@
 // output.rs:195-261 output_mesh and its two writers (ObjWriter :484-630, PlyWriter :385-482).
-// Vertex ids, faces and coordinates come from the GPU kernels in output.hip; this file is the
-// host-side serialisation, byte-for-byte the reference's text/binary layout.
+// Vertex ids, faces and coordinates come from the GPU kernels in output.hip, the OBJ text from obj_format.hip and the
+// PLY records from ply_format.hip; this file drives them, copies the finished bytes to the host once and writes the
+// file (write-behind included).  The host-side serialisers, byte-for-byte the reference's text/binary layout, stay as
+// the A/B of both (ME_OBJ_HOST_FORMAT, ME_PLY_HOST_FORMAT).
 #include <atomic>
 #include <charconv>
 #include <chrono>
@@ -220,6 +222,40 @@ DeviceText obj_text_on_device(me_ctx* ctx, const DeviceMesh& m, int32_t width, i
     return t;
 }
 
+// output.rs:415-438: the ASCII header of a PLY file.  The colour properties follow the vertex MODE; whether the records
+// carry colours follows the colour array (ME_VERTEX_COLOR without one: colour properties, 24-byte records).
+std::string ply_header(int64_t nverts, int64_t nfaces, bool color_properties) {
+    std::string b = "ply\nformat binary_big_endian 1.0\ncomment Matrix Eyes 3D surface\n";
+    b += "element vertex " + std::to_string(nverts) + "\n";
+    b += "property double x\nproperty double y\nproperty double z\n";
+    if (color_properties) b += "property uchar red\nproperty uchar green\nproperty uchar blue\n";
+    b += "element face " + std::to_string(nfaces) + "\n";
+    b += "property list uchar int vertex_indices\nend_header\n";
+    return b;
+}
+
+// The PLY file in device memory (site buffer "out.plybytes"): the header, copied in, + the records ply_format.hip packs
+// behind it.  The size is closed-form, so nothing comes back to the host in between.
+DeviceText ply_bytes_on_device(me_ctx* ctx, const DeviceMesh& m, int32_t width, int32_t height, int32_t vertex_mode,
+                               const uint8_t* vertex_colors) {
+    const uint8_t* vrgb = nullptr;
+    if (vertex_mode == ME_VERTEX_COLOR && vertex_colors) {
+        const size_t nv = (size_t)width * height;
+        const uint8_t* pix = (const uint8_t*)to_device(ctx, vertex_colors, nv * 3, "out.pixel_rgb");
+        uint8_t* v = (uint8_t*)site_buf(ctx, "out.vertex_rgb", (size_t)m.nverts * 3 + 16);
+        obj_vertex_colors_launch(m.vindex, pix, (int64_t)nv, v, ctx->stream);
+        vrgb = v;
+    }
+    const std::string header = ply_header(m.nverts, m.nfaces, vertex_mode == ME_VERTEX_COLOR);
+    DeviceText t;
+    t.bytes = ply_pack_bytes(m.nverts, vrgb != nullptr, m.nfaces, (int64_t)header.size());
+    const size_t step = (size_t)64 << 20;   // as "out.objtext": a sequence of images settles
+    t.dev = (char*)site_buf(ctx, "out.plybytes", ((size_t)t.bytes + 64 + step - 1) / step * step);
+    ME_HIP(hipMemcpyAsync(t.dev, header.data(), header.size(), hipMemcpyHostToDevice, ctx->stream));
+    ply_pack_launch(m.xyz, vrgb, m.nverts, m.faces, m.nfaces, (int64_t)header.size(), (uint8_t*)t.dev, ctx->stream);
+    return t;
+}
+
 // `bytes` from pinned host memory into a new file: chunks of 8 MiB by up to 8 threads (page-cache copies scale
 // with threads; one thread moves ~2 GB/s)
 void write_file_parallel(const std::string& path, const char* data, size_t bytes) {
@@ -352,6 +388,23 @@ extern "C" int32_t me_mesh_obj_text(me_ctx* ctx, const float* depth, int32_t wid
     ME_API_END(ctx)
 }
 
+extern "C" int32_t me_mesh_ply_bytes(me_ctx* ctx, const float* depth, int32_t width, int32_t height,
+                                     uint32_t original_width, uint32_t original_height, int32_t vertex_mode,
+                                     const uint8_t* vertex_colors, const uint8_t** bytes_dev, int64_t* nbytes) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(depth && bytes_dev && nbytes, ME_ERR_BAD_ARG, "me_mesh_ply_bytes: null pointer");
+    ME_CHECK(vertex_mode >= ME_VERTEX_PLAIN && vertex_mode <= ME_VERTEX_TEXTURE, ME_ERR_BAD_ARG,
+             "vertex mode %d", vertex_mode);
+    ME_CHECK(width >= 2 && height >= 2, ME_ERR_BAD_SHAPE, "me_mesh_ply_bytes: %dx%d", width, height);
+    ME_CHECK(original_width > 0 && original_height > 0, ME_ERR_BAD_ARG, "original size 0");
+    OutputScope out_scope(ctx, depth);
+    const DeviceMesh m = build_mesh(ctx, depth, width, height, original_width, original_height);
+    const DeviceText t = ply_bytes_on_device(ctx, m, width, height, vertex_mode, vertex_colors);
+    ME_HIP(hipStreamSynchronize(ctx->stream));
+    *bytes_dev = (const uint8_t*)t.dev, *nbytes = t.bytes;
+    ME_API_END(ctx)
+}
+
 extern "C" int32_t me_output_mesh(me_ctx* ctx, const float* depth, int32_t width, int32_t height,
                                   uint32_t original_width, uint32_t original_height,
                                   const char* destination_path, const char* source_path,
@@ -372,7 +425,7 @@ extern "C" int32_t me_output_mesh(me_ctx* ctx, const float* depth, int32_t width
         const bool with_color = vertex_mode == ME_VERTEX_COLOR && vertex_colors;
         OutputScope out_scope(ctx, depth);
         const auto t_entry = std::chrono::steady_clock::now();
-        if (ctx->write_behind && obj) {
+        if (ctx->write_behind) {
             // Before any GPU work of this call: the pinned buffer it will use must be free, and a failed earlier write
             // is reported NOW (this call has produced nothing yet; the caller can repeat it).  A pending write to the
             // same destination is waited for as well -- a second fopen("wb") would truncate the file under it.
@@ -388,16 +441,20 @@ extern "C" int32_t me_output_mesh(me_ctx* ctx, const float* depth, int32_t width
         int32_t* vindex = mesh.vindex;
         int32_t* faces_dev = mesh.faces;
         float *uv_dev = mesh.uv, *xyz_dev = mesh.xyz;
-        // ---- OBJ: the text is formatted on the GPU too (obj_format.hip); one D2H copy into pinned memory, one file
-        // write.  ME_OBJ_HOST_FORMAT=1 keeps the host formatter below (the same Ryu digits; A/B and PLY path).
-        static const bool host_format = getenv("ME_OBJ_HOST_FORMAT") != nullptr;
-        if (obj && !host_format) {
+        // ---- the file's bytes are produced on the GPU too (OBJ: the text, obj_format.hip; PLY: the binary records,
+        // ply_format.hip); one D2H copy into pinned memory, one file write.  ME_OBJ_HOST_FORMAT=1 / ME_PLY_HOST_FORMAT=1
+        // keep the host serialisers below (the same bytes; the A/B of each).
+        static const bool obj_host_format = getenv("ME_OBJ_HOST_FORMAT") != nullptr;
+        static const bool ply_host_format = getenv("ME_PLY_HOST_FORMAT") != nullptr;
+        if (obj ? !obj_host_format : !ply_host_format) {
             static const bool timing = getenv("ME_OBJ_TIMING") != nullptr;  // diagnostic: the legs on stderr
             const auto now = [] { return std::chrono::steady_clock::now(); };
             const auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
             const auto t0 = now();
             const std::string stem = file_stem(dest);
-            const DeviceText t = obj_text_on_device(ctx, mesh, width, height, stem, vertex_mode, vertex_colors);
+            const DeviceText t = obj ? obj_text_on_device(ctx, mesh, width, height, stem, vertex_mode, vertex_colors)
+                                     : ply_bytes_on_device(ctx, mesh, width, height, vertex_mode, vertex_colors);
+            const bool tex = obj && vertex_mode == ME_VERTEX_TEXTURE;   // the .mtl beside the file
             // write-behind: this call's text goes into the pinned buffer whose earlier write has finished (waited for
             // here, a failure of it reported here), and a host thread writes the file while the caller moves on
             const int slot = ctx->write_behind ? ctx->write_next : 0;
@@ -412,7 +469,6 @@ extern "C" int32_t me_output_mesh(me_ctx* ctx, const float* depth, int32_t width
                 me_ctx::WriteSlot& w = ctx->write_slots[(size_t)slot];
                 const std::string src(source_path);
                 const size_t nbytes = (size_t)t.bytes;
-                const bool tex = vertex_mode == ME_VERTEX_TEXTURE;
                 w.active = true, w.code = 0, w.msg.clear(), w.dest = dest;
                 w.th = std::thread([&w, dest, stem, src, host, nbytes, tex]() {
                     try {
@@ -427,7 +483,7 @@ extern "C" int32_t me_output_mesh(me_ctx* ctx, const float* depth, int32_t width
                 ctx->write_next = (ctx->write_next + 1) % ctx->write_behind;
             } else {
                 write_file_parallel(dest, host, (size_t)t.bytes);
-                if (vertex_mode == ME_VERTEX_TEXTURE) write_mtl(dest, stem, source_path);
+                if (tex) write_mtl(dest, stem, source_path);
             }
             const auto t3 = now();
             ctx->mesh_ms[0] = ms(t_entry, t0), ctx->mesh_ms[1] = ms(t0, t1), ctx->mesh_ms[2] = ms(t1, t2), ctx->mesh_ms[3] = ms(t2, t3);
@@ -514,14 +570,7 @@ extern "C" int32_t me_output_mesh(me_ctx* ctx, const float* depth, int32_t width
             w.close();
             if (tex) write_mtl(dest, stem, source_path);
         } else {
-            // output.rs:415-438
-            b += "ply\nformat binary_big_endian 1.0\ncomment Matrix Eyes 3D surface\n";
-            b += "element vertex " + std::to_string(nverts) + "\n";
-            b += "property double x\nproperty double y\nproperty double z\n";
-            if (vertex_mode == ME_VERTEX_COLOR)
-                b += "property uchar red\nproperty uchar green\nproperty uchar blue\n";
-            b += "element face " + std::to_string(nfaces) + "\n";
-            b += "property list uchar int vertex_indices\nend_header\n";
+            b += ply_header(nverts, nfaces, vertex_mode == ME_VERTEX_COLOR);
             write_section(w, nverts, [&](int64_t i, std::string& b) {  // output.rs:440-458
                 put_be64(b, (double)xyz[3 * i]);
                 put_be64(b, (double)(-xyz[3 * i + 1]));

@@ -233,6 +233,18 @@ class DepthMap:
             self.original_width, self.original_height, destination_path.encode(), source_path.encode(),
             int(vertex_mode), C.c_void_p(colors.ctypes.data) if colors is not None else None))
 
+    def mesh_ply_bytes(self, vertex_mode: VertexMode = VertexMode.Plain, colors=None) -> bytes:
+        """The PLY file output_mesh(".ply") writes, as `bytes` (me_mesh_ply_bytes: the records packed on the GPU).
+        colors: u8 [data_height, data_width, 3] (the source resized to the depth map) or None, read in VertexMode.Color only."""
+        if colors is not None:
+            colors = np.ascontiguousarray(colors, dtype=np.uint8)
+        ptr, n = C.c_void_p(), C.c_int64()
+        self.ctx._check(self.ctx.lib.me_mesh_ply_bytes(
+            self.ctx.handle, C.c_void_p(self.data.ctypes.data), self.data_width, self.data_height, self.original_width,
+            self.original_height, int(vertex_mode), C.c_void_p(colors.ctypes.data) if colors is not None else None,
+            C.byref(ptr), C.byref(n)))
+        return _device_file(ptr, n, self.data)
+
 
 class DeviceDepthMap:
     """DepthMap::new -> output_image chained on the GPU (BASELINE configs[4]: depth -> stereogram / depth map
@@ -295,6 +307,16 @@ class DeviceDepthMap:
             self.ctx.handle, C.c_void_p(self.data.data_ptr()), self.data_width, self.data_height, self.original_width,
             self.original_height, stem.encode(), int(vertex_mode),
             C.c_void_p(colors.data_ptr()) if colors is not None else None, C.byref(ptr), C.byref(n)))
+        return _device_file(ptr, n, self.data)
+
+    def mesh_ply_bytes(self, vertex_mode: VertexMode = VertexMode.Plain, colors=None):
+        """The PLY file's bytes as a CUDA uint8 tensor (me_mesh_ply_bytes: the records packed on the GPU; a copy of the
+        context-owned buffer).  colors: CUDA u8 [rows, cols, 3] or None, read in VertexMode.Color only."""
+        ptr, n = C.c_void_p(), C.c_int64()
+        self.ctx._check(self.ctx.lib.me_mesh_ply_bytes(
+            self.ctx.handle, C.c_void_p(self.data.data_ptr()), self.data_width, self.data_height, self.original_width,
+            self.original_height, int(vertex_mode), C.c_void_p(colors.data_ptr()) if colors is not None else None,
+            C.byref(ptr), C.byref(n)))
         return _device_file(ptr, n, self.data)
 
     def stereogram(self, amplitude: float, noise, out=None):
