@@ -195,6 +195,11 @@ int32_t me_op_format_f64(me_ctx* ctx, const double* values, int64_t count, char*
 int32_t me_op_ply_pack(me_ctx* ctx, const float* xyz, const uint8_t* vertex_rgb /* per vertex id, or NULL */,
                        int64_t nverts, const int32_t* faces, int64_t nfaces, int64_t header_bytes,
                        uint8_t* out /* header_bytes + nverts*(24|27) + nfaces*13; the first header_bytes untouched */);
+/* The prefix sums of the byte-stream producers (csrc/scan.h) on their own: offsets[i] = base + the sum of counts[0 .. i),
+   offsets[n] = base + the total, in 64 bits.  form 0: the one-workgroup scan of the OBJ text (n >= 0); form 1: the
+   two-level scan of the JPEG encoder (n > 0).  Host or device pointers. */
+int32_t me_op_exclusive_scan_u32(me_ctx* ctx, const uint32_t* counts, int64_t n, uint64_t base, int32_t form,
+                                 uint64_t* offsets /* n + 1 */);
 /* Box calibration (csrc/calibrate.hip; bench.py's `calibration` object): two FIXED loops on the context's stream, about
    50 ms, synchronous.  out[0] = TFLOP/s of an MFMA-only loop (v_mfma_f32_16x16x32_f16, operands in registers, two waves per
    SIMD on 256 workgroups), out[1] = the shader clock the part held inside it (GHz, s_memtime / s_memrealtime),

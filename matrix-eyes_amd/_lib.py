@@ -149,6 +149,7 @@ SIGNATURES = {
                                                    C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _f32, _vp, _vp, _vp]),
     "me_op_format_f64": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp]),
     "me_op_ply_pack": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp]),
+    "me_op_exclusive_scan_u32": (_i32, [_vp, _vp, _i64, C.c_uint64, _i32, _vp]),
     "me_calibrate": (_i32, [_vp, C.POINTER(C.c_double)]),
     "me_op_cast_to16": (_i32, [_vp, _vp, _vp, _i64]),
     "me_op_cast_to32": (_i32, [_vp, _vp, _vp, _i64]),

@@ -1643,6 +1643,18 @@ int32_t me_op_ply_pack(me_ctx* ctx, const float* xyz, const uint8_t* vertex_rgb,
     ME_API_END(ctx)
 }
 
+int32_t me_op_exclusive_scan_u32(me_ctx* ctx, const uint32_t* counts, int64_t n, uint64_t base, int32_t form, uint64_t* offsets) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(offsets && n >= 0 && (counts || n == 0), ME_ERR_BAD_ARG, "me_op_exclusive_scan_u32: bad argument");
+    ME_CHECK(form == 0 || (form == 1 && n > 0), ME_ERR_BAD_ARG, "me_op_exclusive_scan_u32: form %d with %lld counts", form, (long long)n);
+    const uint32_t* c = n ? (const uint32_t*)to_device(ctx, counts, (size_t)n * 4, "op.scan.counts") : nullptr;
+    OutBuf o = out_buf(ctx, offsets, (size_t)(n + 1) * 8, "op.scan.out");
+    if (form == 0) obj_offsets_launch(c, n, base, (uint64_t*)o.dev, ctx->stream);
+    else jpeg_encode_scan_offsets(ctx, c, n, base, (uint64_t*)o.dev);
+    finish(ctx, o);
+    ME_API_END(ctx)
+}
+
 int32_t me_op_cast_to16(me_ctx* ctx, const float* src, void* dst16, int64_t count) {
     ME_API_BEGIN(ctx)
     cast_f32_to_16_launch(src, dst16, count, ctx->dtype, ctx->stream);

@@ -434,6 +434,9 @@ int64_t obj_format_measure(const float* uv, const float* xyz, const uint8_t* ver
 void obj_format_write(const float* uv, const float* xyz, const uint8_t* vertex_rgb, const int32_t* faces, int64_t nverts,
                       int64_t nfaces, bool tex, char* text, void* workspace, hipStream_t stream);
 void format_f64_launch(const double* v, int64_t n, char* out, int stride, int* lens, hipStream_t stream);
+// the prefix sums of scan.h as the OBJ text (one workgroup) and the JPEG encoder (two levels, n > 0) run them
+void obj_offsets_launch(const uint32_t* bytes, int64_t n, uint64_t base, uint64_t* off, hipStream_t stream);
+void jpeg_encode_scan_offsets(me_ctx* ctx, const uint32_t* counts, int64_t n, uint64_t base, uint64_t* offsets);
 void obj_vertex_colors_launch(const int32_t* vindex, const uint8_t* pixel_rgb, int64_t npix, uint8_t* vertex_rgb,
                               hipStream_t stream);
 // Binary PLY records on the device (ply_format.hip): the vertex records (24 bytes, or 27 with vertex_rgb) and the face

@@ -4,8 +4,8 @@
 //   jpeg_fdct_kernel          8 lanes per block, 32 blocks per workgroup, blocks in scan order: samples gathered from the RGB
 //                             picture, row pass, transpose through LDS, column pass, quantisation -> int16 zigzag coefficients
 //   jpeg_bits_kernel          one wave per block, lane k = zigzag position k: the block's bit count
-//   jpeg_encode_scan_kernel   exclusive sums inside a workgroup (Hillis-Steele) and the workgroup's aggregate, 64-bit ...
-//   jpeg_encode_carry_kernel  ... and one workgroup over the aggregates; both are used twice (block bits, stuffed bytes)
+//   scan_groups_kernel        exclusive sums inside a workgroup and the workgroup's aggregate, 64-bit (scan.h) ...
+//   scan_slices_kernel        ... and one workgroup over the aggregates; both are used twice (block bits, stuffed bytes)
 //   jpeg_pack_kernel          the codes again, ORed into the zeroed big-endian stream at their bit offsets (vector atomic OR:
 //                             OR commutes, so the bytes do not depend on the order); the last lane pads with ones
 //   jpeg_stuff_count_kernel   FF bytes per 16 bytes of the packed stream
@@ -18,6 +18,7 @@
 
 #include "jpeg_encode.h"
 #include "model.h"
+#include "scan.h"
 
 using namespace me;
 
@@ -25,18 +26,11 @@ namespace {
 
 using namespace me_jpeg_encode;
 
-__device__ __forceinline__ void stage_codes(EncCodes& lds, const EncTables* g) {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(&g->c);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(&lds);
-    for (int k = (int)threadIdx.x; k < (int)(sizeof(EncCodes) / 4); k += kThreads) dst[k] = src[k];
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(kThreads) void jpeg_fdct_kernel(const EncTables* __restrict__ tables, const uint8_t* __restrict__ rgb,
                                                             int16_t* __restrict__ coef) {
     __shared__ EncCodes T;
     __shared__ int32_t tile[kFdctBlocks][8][kTileStride];
-    stage_codes(T, tables);
+    me_scan::stage_to_lds<kThreads>(T, &tables->c);
     const int local = (int)threadIdx.x >> 3, lane = (int)threadIdx.x & 7;
     const int64_t at = (int64_t)blockIdx.x * kFdctBlocks + local;
     const bool live = at < T.d.total_blocks;
@@ -55,74 +49,24 @@ __device__ __forceinline__ LaneCode wave_lane_code(const EncCodes& T, const int1
 __global__ __launch_bounds__(kThreads) void jpeg_bits_kernel(const EncTables* __restrict__ tables, const int16_t* __restrict__ coef,
                                                             uint32_t* __restrict__ nbits) {
     __shared__ EncCodes T;
-    stage_codes(T, tables);
+    me_scan::stage_to_lds<kThreads>(T, &tables->c);
     const int k = (int)threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * kWaveBlocks + ((int)threadIdx.x >> 6);
     if (i >= T.d.total_blocks) return;  // a whole wave
-    int32_t sum = wave_lane_code(T, coef, (int32_t)i, k).len;
-    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_down(sum, d, 64);
+    const int32_t sum = me_scan::wave_sum(wave_lane_code(T, coef, (int32_t)i, k).len);
     if (k == 0) nbits[i] = (uint32_t)sum;
-}
-
-// before[i]: the sum of counts[j] over the j < i of i's workgroup; agg[g]: workgroup g's sum
-__global__ __launch_bounds__(kThreads) void jpeg_encode_scan_kernel(const uint32_t* __restrict__ counts, int64_t n,
-                                                                   uint64_t* __restrict__ before, uint64_t* __restrict__ agg) {
-    __shared__ uint64_t val[kThreads];
-    const int tid = (int)threadIdx.x;
-    const int64_t i = (int64_t)blockIdx.x * kThreads + tid;
-    const uint64_t mine = i < n ? counts[i] : 0;
-    val[tid] = mine;
-    __syncthreads();
-    for (int d = 1; d < kThreads; d <<= 1) {
-        const uint64_t left = tid >= d ? val[tid - d] : 0;
-        __syncthreads();
-        val[tid] += left;
-        __syncthreads();
-    }
-    if (i < n) before[i] = val[tid] - mine;
-    if (tid == kThreads - 1) agg[blockIdx.x] = val[tid];
-}
-
-// carry[g]: the sum of agg[0 .. g); carry[ngroups]: the total.  One workgroup: a thread sums a slice of the aggregates, the
-// slices' sums are scanned in LDS, and the thread walks its slice again.
-__global__ __launch_bounds__(kThreads) void jpeg_encode_carry_kernel(const uint64_t* __restrict__ agg, int64_t ngroups,
-                                                                    uint64_t* __restrict__ carry) {
-    __shared__ uint64_t val[kThreads];
-    const int tid = (int)threadIdx.x;
-    const int64_t per = (ngroups + kThreads - 1) / kThreads;
-    const int64_t lo = (int64_t)tid * per < ngroups ? (int64_t)tid * per : ngroups, hi = lo + per < ngroups ? lo + per : ngroups;
-    uint64_t mine = 0;
-    for (int64_t g = lo; g < hi; ++g) mine += agg[g];
-    val[tid] = mine;
-    __syncthreads();
-    for (int d = 1; d < kThreads; d <<= 1) {
-        const uint64_t left = tid >= d ? val[tid - d] : 0;
-        __syncthreads();
-        val[tid] += left;
-        __syncthreads();
-    }
-    uint64_t run = val[tid] - mine;
-    for (int64_t g = lo; g < hi; ++g) {
-        carry[g] = run;
-        run += agg[g];
-    }
-    if (tid == kThreads - 1) carry[ngroups] = val[tid];
 }
 
 __global__ __launch_bounds__(kThreads) void jpeg_pack_kernel(const EncTables* __restrict__ tables, const int16_t* __restrict__ coef,
                                                             const uint64_t* __restrict__ before, const uint64_t* __restrict__ carry,
                                                             uint32_t* words) {
     __shared__ EncCodes T;
-    stage_codes(T, tables);
+    me_scan::stage_to_lds<kThreads>(T, &tables->c);
     const int k = (int)threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * kWaveBlocks + ((int)threadIdx.x >> 6);
     if (i >= T.d.total_blocks) return;  // a whole wave
     const LaneCode c = wave_lane_code(T, coef, (int32_t)i, k);
-    int32_t incl = c.len;  // at most 64 * 59 bits
-    for (int d = 1; d < 64; d <<= 1) {
-        const int32_t left = __shfl_up(incl, d, 64);
-        if (k >= d) incl += left;
-    }
+    const int32_t incl = me_scan::wave_scan(c.len);  // at most 64 * 59 bits
     const uint64_t at = before[i] + carry[i / kThreads] + (uint64_t)(incl - c.len);
     put_bits(words, at, c.bits, c.len);
     if (i == T.d.total_blocks - 1 && k == 63) {  // the scan's last bit is behind this lane's: ones up to the byte
@@ -153,17 +97,28 @@ __global__ __launch_bounds__(kThreads) void jpeg_stuff_kernel(const EncTables* _
     }
 }
 
-void scan_launch(const uint32_t* counts, int64_t n, uint64_t* before, uint64_t* agg, uint64_t* carry, hipStream_t s) {
-    const int64_t ngroups = (int64_t)cdiv(n, kThreads);
-    hipLaunchKernelGGL(jpeg_encode_scan_kernel, dim3((unsigned)ngroups), dim3(kThreads), 0, s, counts, n, before, agg);
-    ME_HIP(hipGetLastError());
-    hipLaunchKernelGGL(jpeg_encode_carry_kernel, dim3(1), dim3(kThreads), 0, s, (const uint64_t*)agg, ngroups, carry);
-    ME_HIP(hipGetLastError());
+// test surface (me_op_exclusive_scan_u32, form 1): the two-level scan's arrays put together as the kernels above read them
+__global__ __launch_bounds__(kThreads) void scan_combine_kernel(const uint64_t* __restrict__ before, const uint64_t* __restrict__ carry,
+                                                               int64_t n, uint64_t base, uint64_t* __restrict__ offsets) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + (int)threadIdx.x;
+    if (i < n) offsets[i] = before[i] + carry[i / kThreads] + base;
+    if (i == n - 1) offsets[n] = carry[(n + kThreads - 1) / kThreads] + base;
 }
 
 }  // namespace
 
 namespace me {
+
+void jpeg_encode_scan_offsets(me_ctx* ctx, const uint32_t* counts, int64_t n, uint64_t base, uint64_t* offsets) {
+    const int64_t groups = (int64_t)cdiv(n, kThreads);
+    uint64_t* before = (uint64_t*)site_buf(ctx, "op.scan.before", (size_t)n * sizeof(uint64_t));
+    uint64_t* agg = (uint64_t*)site_buf(ctx, "op.scan.agg", (size_t)groups * sizeof(uint64_t));
+    uint64_t* carry = (uint64_t*)site_buf(ctx, "op.scan.carry", (size_t)(groups + 1) * sizeof(uint64_t));
+    me_scan::launch_two_level<kThreads>(counts, n, before, agg, carry, ctx->stream);
+    hipLaunchKernelGGL(scan_combine_kernel, dim3((unsigned)groups), dim3(kThreads), 0, ctx->stream, (const uint64_t*)before,
+                       (const uint64_t*)carry, n, base, offsets);
+    ME_HIP(hipGetLastError());
+}
 
 void check_jpeg_encode_args(const char* who, int32_t w, int32_t h, int32_t quality, int32_t subsampling) {
     ME_CHECK(quality >= 1 && quality <= 100, ME_ERR_BAD_ARG, "%s: quality %d outside 1..100", who, quality);
@@ -210,7 +165,7 @@ DeviceFile jpeg_encode_device(me_ctx* ctx, const uint8_t* rgb_any, int32_t w, in
     hipLaunchKernelGGL(jpeg_bits_kernel, dim3((unsigned)wave_groups), dim3(kThreads), 0, s, (const EncTables*)dtab,
                        (const int16_t*)coef, nbits);
     ME_HIP(hipGetLastError());
-    scan_launch(nbits, nblocks, before, agg, carry, s);
+    me_scan::launch_two_level<kThreads>(nbits, nblocks, before, agg, carry, s);
     ME_HIP(hipEventRecord(ctx->jpeg_encode_ev[3], s));
     uint64_t total_bits = 0;
     ME_HIP(hipMemcpyAsync(&total_bits, carry + block_groups, sizeof(total_bits), hipMemcpyDeviceToHost, s));
@@ -237,7 +192,7 @@ DeviceFile jpeg_encode_device(me_ctx* ctx, const uint8_t* rgb_any, int32_t w, in
     ME_HIP(hipEventRecord(ctx->jpeg_encode_ev[4], s));
     hipLaunchKernelGGL(jpeg_stuff_count_kernel, dim3((unsigned)chunk_groups), dim3(kThreads), 0, s, (const uint32_t*)words, nchunks, ff);
     ME_HIP(hipGetLastError());
-    scan_launch(ff, nchunks, ff_before, ff_agg, ff_carry, s);
+    me_scan::launch_two_level<kThreads>(ff, nchunks, ff_before, ff_agg, ff_carry, s);
     hipLaunchKernelGGL(jpeg_stuff_kernel, dim3((unsigned)chunk_groups), dim3(kThreads), 0, s, (const EncTables*)dtab,
                        (const uint32_t*)words, nbytes, nchunks, (const uint64_t*)ff_before, (const uint64_t*)ff_carry, file);
     ME_HIP(hipGetLastError());

@@ -7,6 +7,7 @@
 //   jpeg_entropy_speculate_kernel   cold-start decode of every subsequence
 //   jpeg_entropy_sync_kernel        one Jacobi round; a workgroup none of whose predecessors changed only copies its states
 //   jpeg_entropy_scan_kernel        segmented exclusive sums of blocks / DC differences inside a workgroup, its aggregate
+//                                   (the workgroup scan of scan.h over (sums, head flag) pairs)
 //   jpeg_entropy_carry_kernel       the aggregates' running sums (one thread: a few hundred workgroups)
 //   jpeg_entropy_write_kernel       the true chain: coefficients, and the status word when it meets garbage
 #include <algorithm>
@@ -16,6 +17,7 @@
 
 #include "jpeg_entropy.h"
 #include "model.h"
+#include "scan.h"
 
 namespace me {
 
@@ -28,17 +30,10 @@ struct Aggregate {
     int32_t has_head;
 };
 
-__device__ __forceinline__ void stage_tables(EntropyTables& lds, const EntropyTables* g) {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(g);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(&lds);
-    for (int k = (int)threadIdx.x; k < (int)(sizeof(EntropyTables) / 4); k += kThreads) dst[k] = src[k];
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(kThreads) void jpeg_entropy_speculate_kernel(const Stream st, uint64_t* __restrict__ state0,
                                                                           Counts* __restrict__ counts) {
     __shared__ EntropyTables tab;
-    stage_tables(tab, st.tables);
+    me_scan::stage_to_lds<kThreads>(tab, st.tables);
     const int32_t i = (int32_t)blockIdx.x * kThreads + (int32_t)threadIdx.x;
     if (i < tab.scan.nsub) speculate_thread(tab, st, i, state0, counts);
 }
@@ -55,7 +50,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_entropy_sync_kernel(const Strea
         if (i < nsub) out[i] = in[i];
         return;
     }
-    stage_tables(tab, st.tables);
+    me_scan::stage_to_lds<kThreads>(tab, st.tables);
     if (i < nsub && sync_thread(tab, st, i, prev, in, out, counts)) atomicAdd(changed, 1);
 }
 
@@ -66,41 +61,33 @@ __device__ __forceinline__ Counts add_counts(const Counts& a, const Counts& b) {
     return r;
 }
 
-// before[i]: the sums over the subsequences of i's segment in front of i that lie in i's workgroup.  A Counts travels as
-// one uint4 (x: blocks, y z w: the DC sums) so that it stays in registers.
+// a segmented sum as a scan: the sums behind the last segment head, and whether there was a head
+struct Seg {
+    uint4 sum;  // a Counts (x: blocks, y z w: the DC sums), so that it stays in registers
+    uint32_t head;
+};
+struct SegAdd {
+    __device__ Seg operator()(const Seg& a, const Seg& b) const {
+        if (b.head) return b;
+        return {make_uint4(a.sum.x + b.sum.x, a.sum.y + b.sum.y, a.sum.z + b.sum.z, a.sum.w + b.sum.w), a.head};
+    }
+};
+
+// before[i]: the sums over the subsequences of i's segment in front of i that lie in i's workgroup
 __global__ __launch_bounds__(kThreads) void jpeg_entropy_scan_kernel(const Stream st, const Counts* __restrict__ counts,
                                                                      int32_t nsub, Counts* __restrict__ before,
                                                                      Aggregate* __restrict__ agg) {
     static_assert(sizeof(Counts) == sizeof(uint4), "a Counts is read and written as one uint4");
-    __shared__ uint4 val[kThreads];
-    __shared__ int32_t flag[kThreads];
-    const int tid = (int)threadIdx.x;
-    const int32_t i = (int32_t)blockIdx.x * kThreads + tid;
-    uint4 mine = make_uint4(0, 0, 0, 0);
-    bool head = false;
-    if (i < nsub) {
-        mine = reinterpret_cast<const uint4*>(counts)[i];
-        head = st.seg_sub0[st.sub_seg[i]] == i;
-    }
-    val[tid] = mine, flag[tid] = head ? 1 : 0;
-    __syncthreads();
-    for (int d = 1; d < kThreads; d <<= 1) {  // inclusive, restarting at every head
-        uint4 left = make_uint4(0, 0, 0, 0);
-        int32_t left_flag = 0;
-        if (tid >= d) left = val[tid - d], left_flag = flag[tid - d];
-        __syncthreads();
-        if (tid >= d && !flag[tid]) {
-            const uint4 v = val[tid];
-            val[tid] = make_uint4(left.x + v.x, left.y + v.y, left.z + v.z, left.w + v.w);
-            flag[tid] = left_flag;
-        }
-        __syncthreads();
-    }
-    if (i < nsub) reinterpret_cast<uint4*>(before)[i] = head || tid == 0 ? make_uint4(0, 0, 0, 0) : val[tid - 1];
-    const int32_t last = min(nsub - (int32_t)blockIdx.x * kThreads, kThreads) - 1;
-    if (tid == last) {
-        reinterpret_cast<uint4*>(&agg[blockIdx.x].sum)[0] = val[tid];
-        agg[blockIdx.x].has_head = flag[tid];
+    __shared__ Seg totals[kThreads / 64];
+    const int32_t i = (int32_t)blockIdx.x * kThreads + (int32_t)threadIdx.x;
+    Seg mine = {make_uint4(0, 0, 0, 0), 0};
+    if (i < nsub) mine = {reinterpret_cast<const uint4*>(counts)[i], st.seg_sub0[st.sub_seg[i]] == i ? 1u : 0u};
+    Seg all;
+    const Seg front = me_scan::block_scan<kThreads>(mine, totals, all, SegAdd());
+    if (i < nsub) reinterpret_cast<uint4*>(before)[i] = mine.head ? make_uint4(0, 0, 0, 0) : front.sum;
+    if (threadIdx.x == 0) {
+        reinterpret_cast<uint4*>(&agg[blockIdx.x].sum)[0] = all.sum;
+        agg[blockIdx.x].has_head = (int32_t)all.head;
     }
 }
 
@@ -118,7 +105,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_entropy_write_kernel(const Stre
                                                                       Counts* before, const Counts* __restrict__ carry,
                                                                       int16_t* __restrict__ coef, int32_t* status) {
     __shared__ EntropyTables tab;
-    stage_tables(tab, st.tables);
+    me_scan::stage_to_lds<kThreads>(tab, st.tables);
     const int32_t group0 = (int32_t)blockIdx.x * kThreads, i = group0 + (int32_t)threadIdx.x;
     if (i >= tab.scan.nsub) return;
     if (st.seg_sub0[st.sub_seg[i]] < group0) before[i] = add_counts(carry[blockIdx.x], before[i]);  // its segment began earlier

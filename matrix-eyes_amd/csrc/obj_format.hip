@@ -6,12 +6,13 @@
 //
 // Three launches per file:
 //   measure: every line is formatted into an LDS slot and only its length kept; one byte count per workgroup;
-//   scan:    exclusive prefix over the workgroups of all sections in file order (one workgroup);
-//   write:   the lines are formatted again, a workgroup's lines are laid end to end with an LDS scan of their
+//   scan:    exclusive prefix over the workgroups of all sections in file order (one workgroup: scan.h);
+//   write:   the lines are formatted again, a workgroup's lines are laid end to end with a workgroup scan of their
 //            lengths and copied out as aligned 16-byte chunks (byte stores only at a workgroup's ragged ends).
 // Formatting twice costs ~200 integer instructions per number and saves a 200-byte slot per line in HBM.
 #include "model.h"
 #include "ryu_f64.h"
+#include "scan.h"
 
 namespace me {
 
@@ -77,15 +78,6 @@ __device__ __forceinline__ int format_line(const ObjArgs& a, int64_t i, char* ou
     return n;
 }
 
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
 // WRITE = false: block_bytes[first_block + blockIdx.x] = bytes of this workgroup's lines.
 // WRITE = true: the lines, packed, at text + block_off[first_block + blockIdx.x].
 template <int SEC, int SLOT, bool WRITE>
@@ -96,22 +88,18 @@ __global__ __launch_bounds__(kThreads) void obj_lines_kernel(ObjArgs a, int64_t 
     __shared__ __attribute__((aligned(16))) char slots[kThreads * SLOT];
     __shared__ int off[kThreads + 1];
     __shared__ int wave_tot[kThreads / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const int64_t i = (int64_t)blockIdx.x * kThreads + t;
     int len = 0;
     if (i < a.count) len = format_line<SEC>(a, i, slots + t * SLOT);
-    const int incl = wave_incl_scan(len, lane);
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += wave_tot[w];
+    int total;
+    const int before = me_scan::block_scan<kThreads>(len, wave_tot, total);
     if constexpr (!WRITE) {
-        if (t == kThreads - 1) block_bytes[first_block + blockIdx.x] = (unsigned)(base + incl);
+        if (t == 0) block_bytes[first_block + blockIdx.x] = (unsigned)total;
     } else {
-        off[t] = base + incl - len;
-        if (t == kThreads - 1) off[kThreads] = base + incl;
+        off[t] = before;
+        if (t == 0) off[kThreads] = total;
         __syncthreads();
-        const int total = off[kThreads];
         char* dst = text + block_off[first_block + blockIdx.x];
         const int mis = (int)((uintptr_t)dst & 15);
         const int nchunks = (mis + total + 15) >> 4;
@@ -147,32 +135,6 @@ __global__ __launch_bounds__(kThreads) void obj_lines_kernel(ObjArgs a, int64_t 
             }
         }
     }
-}
-
-// exclusive prefix of `n` byte counts -> 64-bit offsets from `base`; out_off[n] = the end
-__global__ __launch_bounds__(1024) void obj_scan_kernel(const unsigned* __restrict__ bytes, int64_t n,
-                                                         unsigned long long base,
-                                                         unsigned long long* __restrict__ out_off) {
-    __shared__ unsigned long long part[1024];
-    const int t = threadIdx.x;
-    const int64_t per = (n + 1023) / 1024;
-    const int64_t b = (int64_t)t * per, e = b + per < n ? b + per : n;
-    unsigned long long s = 0;
-    for (int64_t i = b; i < e; ++i) s += bytes[i];
-    part[t] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {  // Hillis-Steele inclusive scan
-        const unsigned long long v = t >= o ? part[t - o] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    unsigned long long run = base + part[t] - s;
-    for (int64_t i = b; i < e; ++i) {
-        out_off[i] = run;
-        run += bytes[i];
-    }
-    if (t == 1023) out_off[n] = base + part[1023];
 }
 
 // colours by vertex id: the pixel that first used a vertex gives it its colour (output.rs:206-218, 578-587)
@@ -223,6 +185,11 @@ void format_f64_launch(const double* v, int64_t n, char* out, int stride, int* l
     ME_HIP(hipGetLastError());
 }
 
+// n byte counts -> their n + 1 offsets from `base`, one workgroup (also the test surface me_op_exclusive_scan_u32, form 0)
+void obj_offsets_launch(const uint32_t* bytes, int64_t n, uint64_t base, uint64_t* off, hipStream_t s) {
+    me_scan::launch_offsets<1024>(bytes, n, base, off, s);
+}
+
 // Scratch for the byte counts and offsets of every workgroup of the three sections.
 size_t obj_format_workspace_bytes(int64_t nverts, int64_t nfaces) {
     const int64_t blocks = 2 * cdiv(nverts, kThreads) + cdiv(nfaces, kThreads);
@@ -238,16 +205,15 @@ int64_t obj_format_measure(const float* uv, const float* xyz, const uint8_t* ver
     const int64_t bv = cdiv(nverts, kThreads), bf = cdiv(nfaces, kThreads);
     const int64_t first_v = tex ? bv : 0, first_f = first_v + bv, blocks = first_f + bf;
     unsigned* bytes = (unsigned*)workspace;
-    unsigned long long* off = (unsigned long long*)((char*)workspace + ((size_t)blocks * 4 + 255) / 256 * 256);
+    uint64_t* off = (uint64_t*)((char*)workspace + ((size_t)blocks * 4 + 255) / 256 * 256);
     ObjArgs vt = {uv, nullptr, nullptr, nullptr, nverts, 0};
     ObjArgs v = {nullptr, xyz, vertex_rgb, nullptr, nverts, 0};
     ObjArgs f = {nullptr, nullptr, nullptr, faces, nfaces, tex ? 1 : 0};
     if (tex) launch_lines<0, kSlotVt, false>(vt, 0, bytes, nullptr, nullptr, s);
     launch_lines<1, kSlotV, false>(v, first_v, bytes, nullptr, nullptr, s);
     launch_lines<2, kSlotF, false>(f, first_f, bytes, nullptr, nullptr, s);
-    hipLaunchKernelGGL(obj_scan_kernel, dim3(1), dim3(1024), 0, s, bytes, blocks, (unsigned long long)header_bytes, off);
-    ME_HIP(hipGetLastError());
-    unsigned long long total = 0;
+    obj_offsets_launch(bytes, blocks, (uint64_t)header_bytes, off, s);
+    uint64_t total = 0;
     ME_HIP(hipMemcpyAsync(&total, off + blocks, 8, hipMemcpyDeviceToHost, s));
     ME_HIP(hipStreamSynchronize(s));
     return (int64_t)total;

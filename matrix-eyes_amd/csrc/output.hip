@@ -8,6 +8,7 @@
 // compiled with floating-point contraction off.
 #include "common.h"
 #include "../../include/me_viridis_lut.h"
+#include "scan.h"
 
 // The rounded intrinsics are plain operators in the HIP headers, so contraction has to be switched
 // off for this translation unit as well (the Makefile also passes -ffp-contract=off).
@@ -297,18 +298,9 @@ __global__ __launch_bounds__(256) void mesh_scan_kernel(const float* __restrict_
     }
     // exclusive scan inside the workgroup
     const unsigned long long tsum = cnt[0] + cnt[1] + cnt[2] + cnt[3];
-    unsigned long long inc = tsum;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    unsigned long long woff = 0;
-    for (int w = 0; w < wave; ++w) woff += wsum[w];
-    const unsigned long long block_total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    unsigned long long block_total;
+    const unsigned long long before = me_scan::block_scan<256>(tsum, wsum, block_total);
     // decoupled look-back by wave 0: publish the aggregate, walk the predecessors 64 at a time
     if (wave == 0) {
         const uint32_t bv = (uint32_t)block_total, bf = (uint32_t)(block_total >> 32);
@@ -346,7 +338,7 @@ __global__ __launch_bounds__(256) void mesh_scan_kernel(const float* __restrict_
         }
     }
     __syncthreads();
-    unsigned long long run = s_prefix + woff + inc - tsum;
+    unsigned long long run = s_prefix + before;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int64_t q = q0 + k;

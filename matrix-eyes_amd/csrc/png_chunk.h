@@ -11,6 +11,9 @@
 #pragma once
 #include <stdint.h>
 #include <string.h>
+#ifndef ME_PNG_HOST
+#include "scan.h"
+#endif
 
 namespace me_png {
 
@@ -167,21 +170,9 @@ PNG_FN void block_scan(ChunkShared& S) {
     }
     S.scan_total = run;
 #else
-    const int t = (int)threadIdx.x, lane = t & 63;
-    const uint32_t v = S.scan[t];
-    uint32_t inc = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) S.wave_total[t >> 6] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (int k = 0; k < kThreads / 64; ++k) {
-        if (k < (t >> 6)) before += S.wave_total[k];
-        all += S.wave_total[k];
-    }
-    S.scan[t] = before + inc - v;
+    const int t = (int)threadIdx.x;
+    uint32_t all;
+    S.scan[t] = me_scan::block_scan<kThreads>(S.scan[t], S.wave_total, all);
     if (t == 0) S.scan_total = all;
     __syncthreads();
 #endif
