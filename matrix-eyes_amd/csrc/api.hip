@@ -9,7 +9,7 @@
 
 #include "../../include/matrix_eyes_hip_ops.h"
 #include "../host/image_io.hpp"
-#include "model.h"
+#include "gemm_params.h"
 #include "mx_fp8.h"
 
 using namespace me;
@@ -1117,10 +1117,8 @@ extern "C" int32_t me_debug_set_stamps(void* dev_ptr) {
 int32_t me_op_linear(me_ctx* ctx, int32_t M, int32_t N, int32_t K, const void* A16, const void* W16,
                      const float* bias, void* out16, float* out32, int32_t act, int32_t tile_cfg) {
     ME_API_BEGIN(ctx)
-    GemmParams p = GemmParams();
+    GemmParams p = linear_params(M, N, K, A16, W16, bias, out16, out32, act);
     p.stamps = g_stamps;
-    p.M = M, p.N = N, p.K = K, p.A = A16, p.lda = K, p.W = W16, p.bias = bias;
-    p.out16 = out16, p.out32 = out32, p.ldc = N, p.act = act;
     gemm_launch(p, A_PLAIN, EPI_STORE, ctx->dtype, ctx->stream, tile_cfg);
     ME_API_END(ctx)
 }
@@ -1130,10 +1128,8 @@ int32_t me_op_linear_residual(me_ctx* ctx, int32_t M, int32_t N, int32_t K, cons
                               int32_t tile_cfg) {
     ME_API_BEGIN(ctx)
     ME_CHECK(bias && gamma && x32, ME_ERR_BAD_ARG, "me_op_linear_residual: null pointer");
-    GemmParams p = GemmParams();
+    GemmParams p = resid_params(M, N, K, A16, W16, bias, gamma, x32);
     p.stamps = g_stamps;
-    p.M = M, p.N = N, p.K = K, p.A = A16, p.lda = K, p.W = W16, p.bias = bias, p.gamma = gamma;
-    p.res32 = x32, p.out32 = x32, p.ldc = N;
     gemm_launch(p, A_PLAIN, EPI_RESID_SCALE, ctx->dtype, ctx->stream, tile_cfg);
     ME_API_END(ctx)
 }
@@ -1158,10 +1154,8 @@ int32_t me_op_linear_scaled_cols(me_ctx* ctx, int32_t M, int32_t N, int32_t K, c
                                  const float* bias, void* out16, int32_t qcols, float qscale, int32_t tile_cfg) {
     ME_API_BEGIN(ctx)
     ME_CHECK(A16 && W16 && bias && out16, ME_ERR_BAD_ARG, "me_op_linear_scaled_cols: null pointer");
-    GemmParams p = GemmParams();
-    p.clamp_lo = -INFINITY, p.clamp_hi = INFINITY;
-    p.M = M, p.N = N, p.K = K, p.A = A16, p.lda = K, p.W = W16, p.bias = bias, p.out16 = out16, p.ldc = N;
-    p.qcols = qcols, p.qscale = qscale;
+    GemmParams p = linear_params(M, N, K, A16, W16, bias, out16, nullptr);
+    set_scaled_cols(p, qcols, qscale);
     gemm_launch(p, A_PLAIN, EPI_STORE, ctx->dtype, ctx->stream, tile_cfg);
     ME_API_END(ctx)
 }
@@ -1174,6 +1168,16 @@ int32_t me_op_layernorm(me_ctx* ctx, const float* x32, const float* weight, cons
     ME_API_END(ctx)
 }
 
+// me_op_conv2d and me_op_conv2d_forms: the pipeline's conv() with the tile the caller names
+static void conv2d_launch(me_ctx* ctx, const void* in16b, int32_t B, int32_t H, int32_t W, int32_t Cin, const void* w16, int32_t Cout,
+                          int32_t k, int32_t stride, const float* bias, const float* res32, const float* res32b, float* out32,
+                          void* out16, int32_t border16, int32_t out16_parts, int32_t act, int32_t act_both, int32_t tile_cfg) {
+    ConvOut o;
+    o.out32 = out32, o.out16 = out16, o.border16 = border16 != 0, o.parts16 = out16_parts, o.act = act, o.act16_only = !act_both;
+    o.res32 = res32, o.res32b = res32b;
+    gemm_launch(conv_params(in16b, B, H, W, Cin, w16, Cout, k, stride, bias, o), A_CONV, EPI_STORE, ctx->dtype, ctx->stream, tile_cfg);
+}
+
 int32_t me_op_conv2d(me_ctx* ctx, const void* in16b, int32_t B, int32_t H, int32_t W, int32_t Cin,
                      const void* w16, int32_t Cout, int32_t k, int32_t stride, const float* bias,
                      const float* res32, const float* res32b, float* out32, void* out16,
@@ -1181,14 +1185,7 @@ int32_t me_op_conv2d(me_ctx* ctx, const void* in16b, int32_t B, int32_t H, int32
     ME_API_BEGIN(ctx)
     ME_CHECK((k == 1 || k == 3) && (stride == 1 || stride == 2), ME_ERR_BAD_SHAPE,
              "me_op_conv2d: k=%d stride=%d", k, stride);
-    GemmParams p = GemmParams();
-    const int Ho = H / stride, Wo = W / stride;
-    p.M = B * Ho * Wo, p.N = Cout, p.K = k * k * Cin, p.A = in16b;
-    p.in_Hp = H + 2, p.in_Wp = W + 2, p.Cin = Cin, p.out_H = Ho, p.out_W = Wo;
-    p.KH = k, p.KW = k, p.stride = stride, p.W = w16, p.bias = bias;
-    p.res32 = res32, p.res32b = res32b, p.out32 = out32, p.out16 = out16, p.ldc = Cout;
-    p.out16_border = border16, p.act = act, p.act16_only = act_both ? 0 : 1;
-    gemm_launch(p, A_CONV, EPI_STORE, ctx->dtype, ctx->stream, tile_cfg);
+    conv2d_launch(ctx, in16b, B, H, W, Cin, w16, Cout, k, stride, bias, res32, res32b, out32, out16, border16, 1, act, act_both, tile_cfg);
     ME_API_END(ctx)
 }
 
@@ -1199,12 +1196,8 @@ int32_t me_op_head_final(me_ctx* ctx, const void* in16b, int32_t B, int32_t H, i
     ME_CHECK(in16b && w16 && bias && w2 && b2 && out32, ME_ERR_BAD_ARG, "me_op_head_final: null pointer");
     ME_CHECK(B > 0 && H > 0 && W > 0 && Cin % 64 == 0 && Cmid > 0 && Cmid <= 32 && Cmid % 4 == 0, ME_ERR_BAD_SHAPE,
              "me_op_head_final: %d x %d x %d, %d -> %d", B, H, W, Cin, Cmid);
-    GemmParams p = GemmParams();
-    p.M = B * H * W, p.N = Cmid, p.K = 9 * Cin, p.A = in16b;
-    p.in_Hp = H + 2, p.in_Wp = W + 2, p.Cin = Cin, p.out_H = H, p.out_W = W;
-    p.KH = 3, p.KW = 3, p.stride = 1, p.W = w16, p.bias = bias, p.w2 = w2, p.b2 = b2, p.f_norm = f_norm;
-    p.pixels_per_image = H * W, p.out32 = out32, p.clamp_lo = clamp_lo, p.clamp_hi = clamp_hi, p.ldc = Cmid;
-    gemm_launch(p, A_CONV, EPI_HEAD_FINAL, ctx->dtype, ctx->stream, tile_cfg);
+    gemm_launch(head_final_params(in16b, B, H, W, Cin, w16, Cmid, bias, w2, b2, f_norm, clamp_lo, clamp_hi, out32), A_CONV, EPI_HEAD_FINAL,
+                ctx->dtype, ctx->stream, tile_cfg);
     ME_API_END(ctx)
 }
 
@@ -1212,15 +1205,12 @@ int32_t me_op_conv_transpose2x2(me_ctx* ctx, const void* in16, int32_t B, int32_
                                 int32_t Cin, const void* w16, int32_t Cout, const float* bias,
                                 float* out32, void* out16, int32_t border16, int32_t tile_cfg) {
     ME_API_BEGIN(ctx)
-    GemmParams p = GemmParams();
-    p.M = B * H * W, p.N = 4 * Cout, p.K = Cin, p.A = in16, p.lda = Cin, p.W = w16, p.bias = bias;
-    p.out_H = H, p.out_W = W, p.Cout = Cout, p.out32 = out32, p.out16 = out16;
-    p.out16_border = border16, p.ldc = Cout;
-    gemm_launch(p, A_PLAIN, EPI_CONVT, ctx->dtype, ctx->stream, tile_cfg);
+    gemm_launch(convt_params(in16, B, H, W, Cin, w16, Cout, bias, out32, out16, border16 != 0, 0, ACT_NONE), A_PLAIN, EPI_CONVT, ctx->dtype,
+                ctx->stream, tile_cfg);
     ME_API_END(ctx)
 }
 
-// ---- the split-operand output forms, GemmParams filled as pipeline.hip's conv / linear / convt helpers fill them ----
+// ---- the split-operand output forms: the descriptors of pipeline.hip's conv / linear / convt helpers (gemm_params.h), the same code ----
 int32_t me_op_conv2d_forms(me_ctx* ctx, const void* in16b, int32_t B, int32_t H, int32_t W, int32_t Cin,
                            const void* w16, int32_t Cout, int32_t k, int32_t stride, const float* bias,
                            const float* res32, const float* res32b, float* out32, void* out16,
@@ -1233,17 +1223,8 @@ int32_t me_op_conv2d_forms(me_ctx* ctx, const void* in16b, int32_t B, int32_t H,
     ME_CHECK(out16_parts >= 1 && out16_parts <= 3 && (out16_parts == 1 || out16), ME_ERR_BAD_ARG,
              "me_op_conv2d_forms: out16_parts=%d", out16_parts);
     ME_CHECK(act == ME_ACT_NONE || act == ME_ACT_RELU, ME_ERR_BAD_ARG, "me_op_conv2d_forms: act=%d", act);
-    GemmParams p = GemmParams();
-    p.clamp_lo = -INFINITY, p.clamp_hi = INFINITY;
-    const int Ho = H / stride, Wo = W / stride;
-    p.M = B * Ho * Wo, p.N = Cout, p.K = k * k * Cin, p.A = in16b;
-    p.in_Hp = H + 2, p.in_Wp = W + 2, p.Cin = Cin, p.out_H = Ho, p.out_W = Wo;
-    p.KH = k, p.KW = k, p.stride = stride, p.W = w16, p.bias = bias;
-    p.res32 = res32, p.res32b = res32b, p.out32 = out32, p.out16 = out16, p.ldc = Cout;
-    p.out16_border = border16 ? 1 : 0, p.act = act, p.act16_only = act_both ? 0 : 1;
-    if (out16_parts >= 2) p.ldc16 = 2 * (int64_t)Cout, p.lo_off16 = Cout;          // pipeline.hip set_out16_split
-    if (out16_parts == 3) p.ldc16 = 3 * (int64_t)Cout, p.hi2_off16 = 2 * Cout;     // ... ConvOut::triple16
-    gemm_launch(p, A_CONV, EPI_STORE, ctx->dtype, ctx->stream, tile_cfg);
+    conv2d_launch(ctx, in16b, B, H, W, Cin, w16, Cout, k, stride, bias, res32, res32b, out32, out16, border16, out16_parts, act, act_both,
+                  tile_cfg);
     ME_API_END(ctx)
 }
 
@@ -1251,11 +1232,8 @@ int32_t me_op_linear_split(me_ctx* ctx, int32_t M, int32_t N, int32_t K, const v
                            const float* bias, void* out16, float* out32, int32_t act, int32_t tile_cfg) {
     ME_API_BEGIN(ctx)
     ME_CHECK(A16 && W16 && out16, ME_ERR_BAD_ARG, "me_op_linear_split: null pointer");
-    GemmParams p = GemmParams();
-    p.clamp_lo = -INFINITY, p.clamp_hi = INFINITY;
-    p.M = M, p.N = N, p.K = K, p.A = A16, p.lda = K, p.W = W16, p.bias = bias;
-    p.out16 = out16, p.out32 = out32, p.ldc = N, p.act = act;
-    p.ldc16 = 2 * (int64_t)N, p.lo_off16 = N;
+    GemmParams p = linear_params(M, N, K, A16, W16, bias, out16, out32, act);
+    set_out16_parts(p, N, 2);
     gemm_launch(p, A_PLAIN, EPI_STORE, ctx->dtype, ctx->stream, tile_cfg);
     ME_API_END(ctx)
 }
@@ -1276,18 +1254,9 @@ int32_t me_op_conv_transpose2x2_forms(me_ctx* ctx, const void* in16, int32_t B, 
     ME_CHECK(pixel_stride >= 0 && pixel_stride % 8 == 0 && lo % 8 == 0 && (!out_split || lo >= Cout) &&
                  (!pixel_stride || pixel_stride >= lo + Cout),
              ME_ERR_BAD_SHAPE, "me_op_conv_transpose2x2_forms: pixel_stride=%d lo_off=%d for %d channels", pixel_stride, lo_off, Cout);
-    GemmParams p = GemmParams();
-    p.clamp_lo = -INFINITY, p.clamp_hi = INFINITY;
-    p.M = B * H * W, p.N = 4 * Cout, p.K = Cin, p.A = in16, p.lda = Cin, p.W = w16, p.bias = bias;
-    p.out_H = H, p.out_W = W, p.Cout = Cout, p.out32 = out32, p.out16 = out16;
-    p.out16_border = border16 ? 1 : 0, p.ldc = Cout, p.act = act16;
-    if (out_split) {
-        p.lo_off16 = lo;
-        p.ldc16 = pixel_stride ? pixel_stride : 2 * Cout;
-    } else if (pixel_stride) {
-        p.ldc16 = pixel_stride;
-    }
-    gemm_launch(p, A_PLAIN, EPI_CONVT, ctx->dtype, ctx->stream, tile_cfg);
+    gemm_launch(convt_params(in16, B, H, W, Cin, w16, Cout, bias, out32, out16, border16 != 0, pixel_stride, act16, false, out_split != 0,
+                             lo_off),
+                A_PLAIN, EPI_CONVT, ctx->dtype, ctx->stream, tile_cfg);
     ME_API_END(ctx)
 }
 
@@ -1297,11 +1266,8 @@ int32_t me_op_patch_embed(me_ctx* ctx, const void* patches16, int32_t windows, i
     ME_CHECK(patches16 && W16 && bias && pos && tokens32, ME_ERR_BAD_ARG, "me_op_patch_embed: null pointer");
     ME_CHECK(windows > 0 && P > 0 && C > 0 && (int64_t)windows * P < (1 << 30), ME_ERR_BAD_SHAPE,
              "me_op_patch_embed: %d windows of %d patches, dim %d", windows, P, C);
-    GemmParams p = GemmParams();
-    p.clamp_lo = -INFINITY, p.clamp_hi = INFINITY;
-    p.M = windows * P, p.N = C, p.K = 768, p.A = patches16, p.lda = 768, p.W = W16;
-    p.bias = bias, p.pos = pos, p.out32 = tokens32, p.ldc = C, p.tokens_per_window = P;
-    gemm_launch(p, A_PLAIN, EPI_PATCH_EMBED, ctx->dtype, ctx->stream, tile_cfg);
+    gemm_launch(patch_embed_params(windows, P, C, patches16, W16, bias, pos, tokens32), A_PLAIN, EPI_PATCH_EMBED, ctx->dtype, ctx->stream,
+                tile_cfg);
     ME_API_END(ctx)
 }
 
@@ -1463,25 +1429,25 @@ int32_t me_op_layernorm_fp8(me_ctx* ctx, const float* x32, const float* weight, 
     ME_API_END(ctx)
 }
 
+// the three forms of me_op_linear_fp8 and me_op_linear_fp8_segments: the residual update of x32, fc1 (GELU) as the next GEMM's
+// fp8 operand, or a plain 16-bit output
+static GemmParams linear_fp8_params(int32_t M, int32_t N, int32_t K, const uint8_t* A8, const uint8_t* a_scale, const uint8_t* W8,
+                                    const uint8_t* w_scale, const float* bias, const float* gamma, void* out16, uint8_t* out8,
+                                    uint8_t* out8_scale, float* x32) {
+    GemmParams p = x32 ? resid_params(M, N, K, A8, W8, bias, gamma, x32)
+                       : linear_params(M, N, K, A8, W8, bias, out8 ? nullptr : out16, nullptr, out8 ? ACT_GELU : ACT_NONE);
+    set_fp8_operands(p, a_scale, w_scale);
+    if (!x32 && out8) set_out8(p, out8, out8_scale);
+    return p;
+}
+
 int32_t me_op_linear_fp8(me_ctx* ctx, int32_t M, int32_t N, int32_t K, const uint8_t* A8, const uint8_t* a_scale,
                          const uint8_t* W8, const uint8_t* w_scale, const float* bias, void* out16, uint8_t* out8,
                          uint8_t* out8_scale, const float* gamma, float* x32) {
     ME_API_BEGIN(ctx)
-    GemmParams p = GemmParams();
-    p.M = M, p.N = N, p.K = K, p.A = A8, p.lda = K, p.a_scale = a_scale, p.a_mt = (int)cdiv(M, 128);
-    p.W = W8, p.w_scale = w_scale, p.bias = bias, p.ldc = N;
-    p.clamp_lo = -INFINITY, p.clamp_hi = INFINITY;
-    if (x32) {
-        ME_CHECK(gamma && bias, ME_ERR_BAD_ARG, "me_op_linear_fp8: the residual form takes bias and gamma");
-        p.gamma = gamma, p.res32 = x32, p.out32 = x32;
-        gemm_fp8_launch(p, EPI_RESID_SCALE, ctx->stream);
-    } else if (out8) {
-        p.act = ACT_GELU, p.out8 = out8, p.out8_scale = out8_scale, p.out8_mt = (int)cdiv(M, 128);
-        gemm_fp8_launch(p, EPI_STORE, ctx->stream);
-    } else {
-        p.out16 = out16;
-        gemm_fp8_launch(p, EPI_STORE, ctx->stream);
-    }
+    if (x32) ME_CHECK(gamma && bias, ME_ERR_BAD_ARG, "me_op_linear_fp8: the residual form takes bias and gamma");
+    const GemmParams p = linear_fp8_params(M, N, K, A8, a_scale, W8, w_scale, bias, gamma, out16, out8, out8_scale, x32);
+    gemm_fp8_launch(p, x32 ? EPI_RESID_SCALE : EPI_STORE, ctx->stream);
     ME_API_END(ctx)
 }
 
@@ -1491,24 +1457,10 @@ int32_t me_op_linear_fp8_segments(me_ctx* ctx, int32_t M, int32_t N, int32_t K, 
                                   uint8_t* out8_scale, float* x32) {
     ME_API_BEGIN(ctx)
     ME_CHECK(A8 && a_scale && W8 && w_scale && bias, ME_ERR_BAD_ARG, "me_op_linear_fp8_segments: null pointer");
-    GemmParams p = GemmParams();
-    p.M = M, p.N = N, p.K = K, p.A = A8, p.lda = K, p.a_scale = a_scale, p.a_mt = (int)cdiv(M, 128);
-    p.W = W8[0], p.w_scale = w_scale[0], p.bias = bias[0], p.ldc = N;
-    p.seg1 = seg1, p.seg2 = seg2;
-    p.W_s1 = W8[1], p.w_scale_s1 = w_scale[1], p.bias_s1 = bias[1];
-    p.W_s2 = W8[2], p.w_scale_s2 = w_scale[2], p.bias_s2 = bias[2];
-    p.clamp_lo = -INFINITY, p.clamp_hi = INFINITY;
-    if (x32) {
-        ME_CHECK(gamma, ME_ERR_BAD_ARG, "me_op_linear_fp8_segments: the residual form takes gamma");
-        p.gamma = gamma[0], p.gamma_s1 = gamma[1], p.gamma_s2 = gamma[2], p.res32 = x32, p.out32 = x32;
-        gemm_fp8_launch(p, EPI_RESID_SCALE, ctx->stream);
-    } else if (out8) {
-        p.act = ACT_GELU, p.out8 = out8, p.out8_scale = out8_scale, p.out8_mt = (int)cdiv(M, 128);
-        gemm_fp8_launch(p, EPI_STORE, ctx->stream);
-    } else {
-        p.out16 = out16;
-        gemm_fp8_launch(p, EPI_STORE, ctx->stream);
-    }
+    if (x32) ME_CHECK(gamma, ME_ERR_BAD_ARG, "me_op_linear_fp8_segments: the residual form takes gamma");
+    GemmParams p = linear_fp8_params(M, N, K, A8, a_scale, nullptr, nullptr, nullptr, nullptr, out16, out8, out8_scale, x32);
+    set_segments(p, seg1, seg2, seg_weights(W8, w_scale, bias, x32 ? gamma : nullptr));
+    gemm_fp8_launch(p, x32 ? EPI_RESID_SCALE : EPI_STORE, ctx->stream);
     ME_API_END(ctx)
 }
 
@@ -1523,19 +1475,10 @@ int32_t me_op_linear_fp8_residual_layernorm(me_ctx* ctx, int32_t M, int32_t N, i
     for (int i = 0; i < nseg; ++i)
         ME_CHECK(W8[i] && w_scale[i] && bias[i] && gamma[i] && ln_w[i] && ln_b[i], ME_ERR_BAD_ARG,
                  "me_op_linear_fp8_residual_layernorm: row segment %d without weights", i);
-    GemmParams p = GemmParams();
-    p.M = M, p.N = N, p.K = K, p.A = A8, p.lda = K, p.a_scale = a_scale, p.a_mt = (int)cdiv(M, 128);
-    p.W = W8[0], p.w_scale = w_scale[0], p.bias = bias[0], p.ldc = N;
-    p.seg1 = seg1, p.seg2 = seg2;
-    p.W_s1 = W8[1], p.w_scale_s1 = w_scale[1], p.bias_s1 = bias[1];
-    p.W_s2 = W8[2], p.w_scale_s2 = w_scale[2], p.bias_s2 = bias[2];
-    p.clamp_lo = -INFINITY, p.clamp_hi = INFINITY;
-    p.gamma = gamma[0], p.gamma_s1 = gamma[1], p.gamma_s2 = gamma[2], p.res32 = x32, p.out32 = x32;
-    p.ln_out16 = xn8, p.ln_eps = eps, p.out8 = xn8, p.out8_scale = xn_scale, p.out8_mt = (int32_t)cdiv(M, 128);
-    p.ln_w = ln_w[0], p.ln_b = ln_b[0], p.ln_w_s1 = ln_w[1], p.ln_b_s1 = ln_b[1], p.ln_w_s2 = ln_w[2], p.ln_b_s2 = ln_b[2];
-    const size_t row_tiles = (size_t)seg_row_tiles<352>(M, seg1, seg2);
-    p.ln_stats = (unsigned long long*)site_buf(ctx, "op.ln.stats", row_tiles * (size_t)(N / 256) * 352 * 8);
-    p.ln_count = (unsigned*)site_buf(ctx, "op.ln.count." + std::to_string(N), row_tiles * 64);
+    GemmParams p = linear_fp8_params(M, N, K, A8, a_scale, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, x32);
+    set_segments(p, seg1, seg2, seg_weights(W8, w_scale, bias, gamma));
+    set_fused_layernorm(ctx, p, "op.ln.stats", "op.ln.count." + std::to_string(N), LnSet{ln_w[0], ln_b[0], ln_w[1], ln_b[1], ln_w[2], ln_b[2]},
+                        eps, nullptr, xn8, xn_scale);
     gemm_fp8_launch(p, EPI_RESID_SCALE, ctx->stream);
     ME_API_END(ctx)
 }
@@ -1549,19 +1492,13 @@ int32_t me_op_linear_segments(me_ctx* ctx, int32_t M, int32_t N, int32_t K, cons
              "me_op_linear_segments: a row segment without weights");
     ME_CHECK(seg1 >= 0 && seg2 >= 0 && seg1 <= M && seg2 <= M && (seg2 == 0 || (seg1 > 0 && seg2 > seg1)), ME_ERR_BAD_ARG,
              "me_op_linear_segments: segments %d / %d of %d rows", seg1, seg2, M);
-    GemmParams p = GemmParams();
-    p.M = M, p.N = N, p.K = K, p.A = A16, p.lda = K, p.W = W16[0], p.bias = bias[0], p.ldc = N;
-    p.seg1 = seg1, p.seg2 = seg2, p.W_s1 = W16[1], p.bias_s1 = bias[1], p.W_s2 = W16[2], p.bias_s2 = bias[2];
-    p.clamp_lo = -INFINITY, p.clamp_hi = INFINITY;
-    if (x32) {
+    if (x32)
         ME_CHECK(gamma && gamma[0] && (seg1 == 0 || gamma[1]) && (seg2 == 0 || gamma[2]), ME_ERR_BAD_ARG,
                  "me_op_linear_segments: the residual form takes gamma for every segment");
-        p.gamma = gamma[0], p.gamma_s1 = gamma[1], p.gamma_s2 = gamma[2], p.res32 = x32, p.out32 = x32;
-        gemm_launch(p, A_PLAIN, EPI_RESID_SCALE, ctx->dtype, ctx->stream, tile_cfg);
-    } else {
-        p.out16 = out16, p.act = act;
-        gemm_launch(p, A_PLAIN, EPI_STORE, ctx->dtype, ctx->stream, tile_cfg);
-    }
+    GemmParams p = x32 ? resid_params(M, N, K, A16, nullptr, nullptr, nullptr, x32)
+                       : linear_params(M, N, K, A16, nullptr, nullptr, out16, nullptr, act);
+    set_segments(p, seg1, seg2, seg_weights(W16, nullptr, bias, x32 ? gamma : nullptr));
+    gemm_launch(p, A_PLAIN, x32 ? EPI_RESID_SCALE : EPI_STORE, ctx->dtype, ctx->stream, tile_cfg);
     ME_API_END(ctx)
 }
 
@@ -1578,19 +1515,12 @@ void linear_residual_layernorm_impl(me_ctx* ctx, const char* who, int32_t M, int
     for (int i = 0; i < nseg; ++i)
         ME_CHECK(W16[i] && bias[i] && gamma[i] && ln_w[i] && ln_b[i], ME_ERR_BAD_ARG, "%s: row segment %d without weights", who, i);
     ME_CHECK(N == 256 || N == 512 || N == 1024, ME_ERR_BAD_SHAPE, "%s: N = %d not in {256, 512, 1024}", who, N);
-    GemmParams p = GemmParams();
-    p.M = M, p.N = N, p.K = K, p.A = A16, p.lda = K, p.W = W16[0], p.bias = bias[0], p.ldc = N;
-    p.seg1 = seg1, p.seg2 = seg2, p.W_s1 = W16[1], p.bias_s1 = bias[1], p.W_s2 = W16[2], p.bias_s2 = bias[2];
-    p.clamp_lo = -INFINITY, p.clamp_hi = INFINITY;
-    p.gamma = gamma[0], p.gamma_s1 = gamma[1], p.gamma_s2 = gamma[2], p.res32 = x32, p.out32 = x32;
-    p.ln_out16 = xn8 ? (void*)xn8 : xn16, p.ln_eps = eps;
-    if (xn8) p.out8 = xn8, p.out8_scale = xn_scale, p.out8_mt = (int32_t)cdiv(M, 128);
-    p.ln_w = ln_w[0], p.ln_b = ln_b[0], p.ln_w_s1 = ln_w[1], p.ln_b_s1 = ln_b[1], p.ln_w_s2 = ln_w[2], p.ln_b_s2 = ln_b[2];
-    const size_t row_tiles = (size_t)seg_row_tiles<352>(M, seg1, seg2);
+    GemmParams p = resid_params(M, N, K, A16, nullptr, nullptr, nullptr, x32);
+    set_segments(p, seg1, seg2, seg_weights(W16, nullptr, bias, gamma));
     // (an arrival counter advances by N / 256 per launch and must start a launch at a multiple of that: one per N)
-    p.ln_stats = (unsigned long long*)site_buf(ctx, "op.ln.stats", row_tiles * (size_t)(N / 256) * 352 * 8);
-    p.ln_count = (unsigned*)site_buf(ctx, "op.ln.count." + std::to_string(N), row_tiles * 64);
-    gemm_launch(p, A_PLAIN, EPI_RESID_SCALE, ctx->dtype, ctx->stream, 10);
+    set_fused_layernorm(ctx, p, "op.ln.stats", "op.ln.count." + std::to_string(N), LnSet{ln_w[0], ln_b[0], ln_w[1], ln_b[1], ln_w[2], ln_b[2]},
+                        eps, xn16, xn8, xn_scale);
+    gemm_launch(p, A_PLAIN, EPI_RESID_SCALE, ctx->dtype, ctx->stream, CFG_PP352);
 }
 }  // namespace
 

@@ -293,7 +293,10 @@ __host__ __device__ __forceinline__ int seg_row_tiles(int M, int seg1, int seg2)
 }
 
 
-// dtype: ME_DTYPE_F16 / ME_DTYPE_BF16.  Picks a tile configuration from (M, N, K).
+// Tile configurations of gemm_launch (gemm.hip kCfgNames has their shapes).  The ids are what me_op_* take as tile_cfg.
+enum { CFG_PP256 = 0, CFG_128 = 1, CFG_64 = 2, CFG_160 = 3, CFG_RING64 = 4, CFG_PP192 = 5, CFG_8PH = 6, CFG_PP96 = 7,
+       CFG_RING128 = 8, CFG_HALO = 9, CFG_PP352 = 10, CFG_HALO12 = 11, CFG_HALO_N128 = 12, CFG_COUNT = 13 };
+// dtype: ME_DTYPE_F16 / ME_DTYPE_BF16.  Picks a tile configuration from (M, N, K) unless force_cfg names one.
 void gemm_launch(const GemmParams& p, AMode amode, EpiKind epi, int32_t dtype, hipStream_t stream,
                  int32_t force_cfg = -1);
 // The depth head's final 3x3 (128 -> 32) + 1x1 (32 -> 1) on a pixel halo tile with the weights held in registers
@@ -339,8 +342,8 @@ struct RowSegs {
 void attention_launch(const void* qkv, void* out, int32_t windows, int32_t tokens, int32_t heads,
                       int32_t dtype, hipStream_t stream, const RowSegs* segs = nullptr, uint8_t* out8 = nullptr,
                       uint8_t* out8_scale = nullptr, int64_t out8_mt = 0, bool q_prescaled = false);
-// attention3.hip: the kernel attention_launch runs for a pre-scaled Q (48 queries per wave on 16x16x32 MFMAs, the query beyond
-// whole wave units on the vector pipe)
+// attention3.hip: a development re-cut (48 queries per wave on 16x16x32 MFMAs, the query beyond whole wave units on the vector
+// pipe) that attention_launch reaches only with ME_ATT_V=3; for a pre-scaled Q it runs attention.hip's attention2_kernel
 void attention3_launch(const void* qkv, void* out, int32_t windows, int32_t tokens, int32_t heads, int32_t dtype, hipStream_t stream,
                        const RowSegs& segs, uint8_t* out8, uint8_t* out8_scale, int64_t out8_mt, float defer_thr);
 // 1/sqrt(head_dim) (vit.rs:47) times log2(e): the factor a pre-scaled Q carries (GemmParams::qscale of the qkv launch)

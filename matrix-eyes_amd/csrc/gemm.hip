@@ -59,12 +59,10 @@ ProfScope::~ProfScope() {
     if (index >= 0) (void)hipEventRecord(profiler().entries[index].e1, stream);
 }
 
-// Tile configurations (the ids are what me_op_* take as tile_cfg)
+// Tile configurations by id (common.h CFG_*)
 static const char* kCfgNames[] = {"256x256x64/8w-pp", "128x128x64/4w", "64x64x64/4w", "160x128x64/4w",
                                   "64x64x64/4w-ring6", "192x256x64/8w-pp", "256x256x64/8w-8ph", "96x256x64/8w-pp",
                                   "128x256x64/8w-ring3", "16x16px-x256x64/8w-halo", "352x256x64/8w-pp", "12x16px-x256x64/8w-halo", "16x16px-x128x64/8w-halo"};
-enum { CFG_PP256 = 0, CFG_128 = 1, CFG_64 = 2, CFG_160 = 3, CFG_RING64 = 4, CFG_PP192 = 5, CFG_8PH = 6, CFG_PP96 = 7,
-       CFG_RING128 = 8, CFG_HALO = 9, CFG_PP352 = 10, CFG_HALO12 = 11, CFG_HALO_N128 = 12, CFG_COUNT = 13 };
 int gemm_num_configs() { return CFG_COUNT; }
 const char* gemm_config_name(int cfg) { return cfg >= 0 && cfg < CFG_COUNT ? kCfgNames[cfg] : "?"; }
 

@@ -8,7 +8,7 @@
 #include <algorithm>
 #include <memory>
 
-#include "model.h"
+#include "gemm_params.h"
 
 namespace me {
 
@@ -63,17 +63,7 @@ void from_device(me_ctx* ctx, void* dst, const void* src_dev, size_t bytes) {
 
 namespace {
 
-// ---- thin launch helpers ---------------------------------------------------------------
-GemmParams base_params() {
-    GemmParams p = GemmParams();  // value-initialised: every pointer null, every int 0
-    p.clamp_lo = -INFINITY, p.clamp_hi = INFINITY;
-    return p;
-}
-
-// Split operands (model.h SplitStage): a_split: A holds [hi | lo] rows of 2K and W is stored [W | W];
-// out_split: the 16-bit output is written as [hi | lo] rows of 2N.
-void set_out16_split(GemmParams& p, int64_t C) { p.ldc16 = 2 * C, p.lo_off16 = (int32_t)C; }
-
+// ---- thin launch helpers: the descriptors come from gemm_params.h, the launch decisions are made here ----
 // Deterministic split-K for the small deep launches of the tail (gemm_core.h gemm_kernel<..., SPLITK>; VERDICT r4
 // "missing" 6): a launch whose image has fewer than 200 tiles of 128 x 128 and K >= ME_SPLIT_K_MINK (4096) runs on that tile with
 // S work items per tile, S the largest power of two that keeps the launch within 640 work items and a K range of at least 512.
@@ -101,74 +91,35 @@ int maybe_split_k(me_ctx* ctx, GemmParams& p, int64_t rows_per_image, hipStream_
     return 1;
 }
 
-// out = act(A[M][K] . W[N][K]^T + bias) as 16-bit and/or f32 rows of stride ldc
+// out = act(A[M][K] . W[N][K]^T + bias) as 16-bit and/or f32 rows of N (split operands, model.h SplitStage: a_split: A holds
+// [hi | lo] rows of 2K and W is stored [W | W]; out_split: the 16-bit output is written as [hi | lo] rows of 2N)
 // rows_per_image > 0: the launch may take the split-K form (maybe_split_k)
 void linear(me_ctx* ctx, const void* A, int64_t M, int K, const void* W, int N, const float* bias,
-            void* out16, float* out32, int64_t ldc, int act, hipStream_t s, bool a_split = false,
+            void* out16, float* out32, int act, hipStream_t s, bool a_split = false,
             bool out_split = false, int qcols = 0, int64_t rows_per_image = 0) {
-    GemmParams p = base_params();
-    const int Kx = a_split ? 2 * K : K;
-    p.M = (int)M, p.N = N, p.K = Kx, p.flop_k = K, p.A = A, p.lda = Kx, p.W = W, p.bias = bias;
-    p.out16 = out16, p.out32 = out32, p.ldc = ldc, p.act = act;
-    p.qcols = qcols, p.qscale = kAttnQScale;  // the qkv linear: Q leaves scaled for the attention kernel
+    GemmParams p = linear_params(M, N, K, A, W, bias, out16, out32, act);
+    set_a_parts(p, a_split ? 2 : 1);
+    set_out16_parts(p, N, out_split ? 2 : 1);
+    set_scaled_cols(p, qcols, kAttnQScale);  // the qkv linear: Q leaves scaled for the attention kernel
     p.grid_cap = ctx->grid_cap;
-    if (out_split) set_out16_split(p, N);
     gemm_launch(p, A_PLAIN, EPI_STORE, ctx->dtype, s, maybe_split_k(ctx, p, rows_per_image, s));
 }
-
-struct ConvOut {
-    float* out32 = nullptr;   // [B*H*W][Cout]
-    void* out16 = nullptr;    // 16-bit copy
-    bool border16 = false;    // out16 is [B][H+2][W+2][Cout]
-    bool split16 = false;     // out16 pixels are [hi | lo] of 2*Cout
-    bool triple16 = false;    // ... [hi | lo | hi] of 3*Cout (with split16)
-    int act = ACT_NONE;       // applied to out16 (and out32 unless act16_only)
-    bool act16_only = true;
-    const float* res32 = nullptr;
-    const float* res32b = nullptr;
-    const float* tap_bias = nullptr;  // GemmParams::tap_bias ([9][Cout]; needs border16)
-};
 
 // Conv2d k x k (k = 1 or 3, pad (k-1)/2, stride 1 or 2) on a zero-bordered NHWC operand
 void conv(me_ctx* ctx, const void* in16b, int B, int Hin, int Win, int Cin, const void* W, int Cout,
           int k, int stride, const float* bias, const ConvOut& o, hipStream_t s, bool a_split = false) {
-    GemmParams p = base_params();
-    const int Ho = Hin / stride, Wo = Win / stride;
-    p.flop_k = k * k * Cin;
-    if (a_split) Cin *= 2;  // pixels of [hi | lo]; the packed weights repeat each tap's Cin values
-    p.M = B * Ho * Wo, p.N = Cout, p.K = k * k * Cin;
-    p.A = in16b, p.in_Hp = Hin + 2, p.in_Wp = Win + 2, p.Cin = Cin;
-    p.out_H = Ho, p.out_W = Wo, p.KH = k, p.KW = k, p.stride = stride;
-    p.W = W, p.bias = bias, p.res32 = o.res32, p.res32b = o.res32b, p.tap_bias = o.tap_bias;
-    p.out32 = o.out32, p.out16 = o.out16, p.ldc = Cout, p.out16_border = o.border16 ? 1 : 0;
-    p.act = o.act, p.act16_only = o.act16_only ? 1 : 0;
-    if (o.split16) set_out16_split(p, Cout);
-    if (o.triple16) p.ldc16 = 3 * Cout, p.hi2_off16 = 2 * Cout;
+    GemmParams p = conv_params(in16b, B, Hin, Win, Cin, W, Cout, k, stride, bias, o, a_split);
     p.grid_cap = ctx->grid_cap;
-    gemm_launch(p, A_CONV, EPI_STORE, ctx->dtype, s, o.tap_bias ? -1 : maybe_split_k(ctx, p, (int64_t)Ho * Wo, s));
+    gemm_launch(p, A_CONV, EPI_STORE, ctx->dtype, s, o.tap_bias ? -1 : maybe_split_k(ctx, p, (int64_t)p.out_H * p.out_W, s));
 }
 
-// ConvTranspose2d(2,2,stride 2) of an unbordered NHWC operand [B*H*W][Cin] -> [B][2H][2W][Cout]
-// pixel_stride: channels per pixel of out16 when it is a slice of a wider map (0: Cout, or 2 Cout when split);
-// out_split: out16 pixels are [hi | lo], the lo part lo_off channels after the hi part (0: Cout)
+// ConvTranspose2d(2,2,stride 2) of an unbordered NHWC operand [B*H*W][Cin] -> [B][2H][2W][Cout]: the arguments of convt_params
 void convt(me_ctx* ctx, const void* in16, int B, int H, int W_, int Cin, const void* W, int Cout,
            const float* bias, float* out32, void* out16, bool border16, int64_t pixel_stride,
            int act16, hipStream_t s, bool a_split = false, bool out_split = false, int64_t lo_off = 0,
-           int k_copies = 0 /* > 0: A rows hold this many Cin-wide parts ([hi | lo | hi] = 3) */) {
-    GemmParams p = base_params();
-    const int Kx = k_copies > 0 ? k_copies * Cin : (a_split ? 2 * Cin : Cin);
-    p.M = B * H * W_, p.N = 4 * Cout, p.K = Kx, p.A = in16, p.lda = Kx, p.W = W, p.bias = bias;
-    // the composed deconv o out_conv (k_copies == 3) stands for two layers of SURVEY App. B: ConvT (Cin x 4 Cout per
-    // input pixel) and the 1x1 conv at 4x the pixels (Cout x Cout each) -- twice the ConvT's FLOPs when Cin == Cout
-    p.flop_k = k_copies == 3 ? 2 * Cin : Cin;
-    p.out_H = H, p.out_W = W_, p.Cout = Cout, p.out32 = out32, p.out16 = out16;
-    p.out16_border = border16 ? 1 : 0, p.ldc = Cout, p.act = act16;
-    if (out_split) {
-        p.lo_off16 = (int32_t)(lo_off ? lo_off : Cout);
-        p.ldc16 = pixel_stride ? pixel_stride : 2 * Cout;
-    } else if (pixel_stride) {
-        p.ldc16 = pixel_stride;
-    }
+           int k_copies = 0) {
+    GemmParams p = convt_params(in16, B, H, W_, Cin, W, Cout, bias, out32, out16, border16, pixel_stride, act16, a_split,
+                                out_split, lo_off, k_copies);
     p.grid_cap = ctx->grid_cap;
     gemm_launch(p, A_PLAIN, EPI_CONVT, ctx->dtype, s);
 }
@@ -187,7 +138,7 @@ void run_upsample(me_ctx* ctx, const std::string& tag, const void* in16, int B, 
     const int64_t M = (int64_t)B * H * H;
     const size_t wide = sp ? 2 : 1;
     void* a = site_buf(ctx, tag + ".proj", (size_t)M * u.dim_int * 2 * wide);
-    linear(ctx, in16, M, C, u.conv, u.dim_int, nullptr, a, nullptr, u.dim_int, ACT_NONE, s, sp, sp, 0, (int64_t)H * H);
+    linear(ctx, in16, M, C, u.conv, u.dim_int, nullptr, a, nullptr, ACT_NONE, s, sp, sp, 0, (int64_t)H * H);
     const void* cur = a;
     int h = H;
     const int n = (int)u.convt.size();
@@ -254,10 +205,7 @@ struct VitRun {
         att = site_buf(ctx, tag + ".att", (size_t)rows * C * 2);
         hid = site_buf(ctx, tag + ".hid", (size_t)rows * 4 * C * 2);
         cls_rows_launch(tok, v.cls, v.pos, W, T, C, s);
-        GemmParams p = base_params();
-        p.M = W * P, p.N = C, p.K = 768, p.A = patches16, p.lda = 768, p.W = v.patch_w;
-        p.bias = v.patch_b, p.pos = v.pos, p.out32 = tok, p.ldc = C, p.tokens_per_window = P;
-        gemm_launch(p, A_PLAIN, EPI_PATCH_EMBED, ctx->dtype, s);
+        gemm_launch(patch_embed_params(W, P, C, patches16, v.patch_w, v.patch_b, v.pos, tok), A_PLAIN, EPI_PATCH_EMBED, ctx->dtype, s);
     }
 
     // vit.rs:163-170 Block::forward
@@ -265,22 +213,12 @@ struct VitRun {
         const VitBlockW& b = v.blocks[i];
         const int C = ctx->C(), T = ctx->T(), heads = ctx->cfg.num_heads;
         layernorm_launch(tok, b.ln1_w, b.ln1_b, xn, nullptr, rows, C, ctx->cfg.ln_eps, ctx->dtype, s);
-        linear(ctx, xn, rows, C, b.qkv_w, 3 * C, b.qkv_b, qkv, nullptr, 3 * C, ACT_NONE, s, false, false, C);
+        linear(ctx, xn, rows, C, b.qkv_w, 3 * C, b.qkv_b, qkv, nullptr, ACT_NONE, s, false, false, C);
         attention_launch(qkv, att, W, T, heads, ctx->dtype, s, nullptr, nullptr, nullptr, 0, true);
-        {
-            GemmParams p = base_params();
-            p.M = (int)rows, p.N = C, p.K = C, p.A = att, p.lda = C, p.W = b.proj_w;
-            p.bias = b.proj_b, p.gamma = b.ls1, p.res32 = tok, p.out32 = tok, p.ldc = C;
-            gemm_launch(p, A_PLAIN, EPI_RESID_SCALE, ctx->dtype, s);
-        }
+        gemm_launch(resid_params(rows, C, C, att, b.proj_w, b.proj_b, b.ls1, tok), A_PLAIN, EPI_RESID_SCALE, ctx->dtype, s);
         layernorm_launch(tok, b.ln2_w, b.ln2_b, xn, nullptr, rows, C, ctx->cfg.ln_eps, ctx->dtype, s);
-        linear(ctx, xn, rows, C, b.fc1_w, 4 * C, b.fc1_b, hid, nullptr, 4 * C, ACT_GELU, s);
-        {
-            GemmParams p = base_params();
-            p.M = (int)rows, p.N = C, p.K = 4 * C, p.A = hid, p.lda = 4 * C, p.W = b.fc2_w;
-            p.bias = b.fc2_b, p.gamma = b.ls2, p.res32 = tok, p.out32 = tok, p.ldc = C;
-            gemm_launch(p, A_PLAIN, EPI_RESID_SCALE, ctx->dtype, s);
-        }
+        linear(ctx, xn, rows, C, b.fc1_w, 4 * C, b.fc1_b, hid, nullptr, ACT_GELU, s);
+        gemm_launch(resid_params(rows, C, 4 * C, hid, b.fc2_w, b.fc2_b, b.ls2, tok), A_PLAIN, EPI_RESID_SCALE, ctx->dtype, s);
         if (taps.fn) taps.fn(taps.user, i, tok);
     }
 
@@ -374,10 +312,8 @@ struct MergedVit {
     void embed(const VitW& v, const void* patches16, int W, int64_t row) {
         const int C = ctx->C(), T = ctx->T(), P = ctx->P();
         cls_rows_launch(tok + row * C, v.cls, v.pos, W, T, C, s);
-        GemmParams p = base_params();
-        p.M = W * P, p.N = C, p.K = 768, p.A = patches16, p.lda = 768, p.W = v.patch_w;
-        p.bias = v.patch_b, p.pos = v.pos, p.out32 = tok + row * C, p.ldc = C, p.tokens_per_window = P;
-        gemm_launch(p, A_PLAIN, EPI_PATCH_EMBED, ctx->dtype, s);
+        gemm_launch(patch_embed_params(W, P, C, patches16, v.patch_w, v.patch_b, v.pos, tok + row * C), A_PLAIN, EPI_PATCH_EMBED,
+                    ctx->dtype, s);
     }
 
     void set_ln(const float* w1, const float* b1, const float* w2, const float* b2) {
@@ -393,8 +329,7 @@ struct MergedVit {
     // last row segment.  Results are bit-identical (same K order per output element).  Measured at one image, FOV head:
     // proj 93.7 -> 82.7 us, fc2 211.7 -> 207.7 us stand-alone (profiles/r03_tail_tile_ab.txt); in the step, same box,
     // alternating runs: 25.17 ms (off) -> 24.90 (proj / fc2 split) -> 24.70 (fc1 too).  ME_GEMM_TAIL96=0 turns it off.
-    bool launch_with_short_tail(const GemmParams& p, EpiKind epi, const void* w1, const float* b1, const float* g1,
-                                const void* w2, const float* b2, const float* g2) {
+    bool launch_with_short_tail(const GemmParams& p, EpiKind epi) {
         static const bool enabled = !(getenv("ME_GEMM_TAIL96") && atoi(getenv("ME_GEMM_TAIL96")) == 0);
         if (!enabled || p.N % 256 || p.M % 256 || p.K < 128) return false;
         const int64_t nbn = p.N / 256;
@@ -414,10 +349,10 @@ struct MergedVit {
         if (p.out32) b.out32 = p.out32 + rows1 * p.ldc;
         if (p.res32) b.res32 = p.res32 + rows1 * p.ldc;
         b.seg1 = b.seg2 = 0;  // one weight set: the last segment's
-        if (p.seg2) b.W = w2, b.bias = b2, b.gamma = g2;
-        else if (p.seg1) b.W = w1, b.bias = b1, b.gamma = g1;
-        gemm_launch(a, A_PLAIN, epi, ctx->dtype, s, 0);
-        gemm_launch(b, A_PLAIN, epi, ctx->dtype, s, 7);
+        if (p.seg2) b.W = p.W_s2, b.bias = p.bias_s2, b.gamma = p.gamma_s2;
+        else if (p.seg1) b.W = p.W_s1, b.bias = p.bias_s1, b.gamma = p.gamma_s1;
+        gemm_launch(a, A_PLAIN, epi, ctx->dtype, s, CFG_PP256);
+        gemm_launch(b, A_PLAIN, epi, ctx->dtype, s, CFG_PP96);
         return true;
     }
 
@@ -443,31 +378,36 @@ struct MergedVit {
         return cost352 * bias < cost256;
     }
 
+    // the weights of block i's three physical segments: one linear's members of VitBlockW (gamma: the residual forms)
+    template <class Wt>
+    SegWeights weights(int i, Wt VitBlockW::*w, const float* VitBlockW::*bias, const float* VitBlockW::*gamma = nullptr,
+                       const uint8_t* VitBlockW::*w_scale = nullptr) const {
+        const VitBlockW* b[3] = {&p0.blocks[i], &p1.blocks[i], &p2.blocks[i]};
+        SegWeights sw;
+        for (int k = 0; k < 3; ++k)
+            sw.W[k] = b[k]->*w, sw.bias[k] = b[k]->*bias, sw.gamma[k] = gamma ? b[k]->*gamma : nullptr,
+            sw.w_scale[k] = w_scale ? b[k]->*w_scale : nullptr;
+        return sw;
+    }
+
     // one GEMM over all segments (three weight sets): 16-bit output (qkv, fc1) ...
-    void gemm_all(const void* A, int K, const void* w0, const void* w1, const void* w2, const float* b0,
-                  const float* b1, const float* b2, int N, void* out16, int act, int qcols = 0) {
-        GemmParams p = base_params();
-        p.M = (int)Rtot, p.N = N, p.K = K, p.A = A, p.lda = K, p.W = w0, p.bias = b0;
-        p.qcols = qcols, p.qscale = kAttnQScale;  // qkv: Q leaves scaled for the attention kernel
+    void gemm_all(const void* A, int K, const SegWeights& w, int N, void* out16, int act, int qcols = 0) {
+        GemmParams p = linear_params(Rtot, N, K, A, nullptr, nullptr, out16, nullptr, act);
+        set_segments(p, seg1, seg2, w);
+        set_scaled_cols(p, qcols, kAttnQScale);  // qkv: Q leaves scaled for the attention kernel
         p.flop_rows = (int)real_rows();
-        p.out16 = out16, p.ldc = N, p.act = act;
-        p.seg1 = (int)seg1, p.seg2 = (int)seg2, p.W_s1 = w1, p.bias_s1 = b1, p.W_s2 = w2, p.bias_s2 = b2;
         // fc1 at one image: five whole rounds + 224 short tiles instead of a sixth round a third full (qkv's 1020 tiles
         // are 3.98 rounds and N = 3072 does not divide the round: launch_with_short_tail declines)
         if (tall_tile_wins(p)) {
-            gemm_launch(p, A_PLAIN, EPI_STORE, ctx->dtype, s, 10);
+            gemm_launch(p, A_PLAIN, EPI_STORE, ctx->dtype, s, CFG_PP352);
             return;
         }
-        if (ctx->C() >= 256 && launch_with_short_tail(p, EPI_STORE, w1, b1, nullptr, w2, b2, nullptr)) return;
+        if (ctx->C() >= 256 && launch_with_short_tail(p, EPI_STORE)) return;
         gemm_launch(p, A_PLAIN, EPI_STORE, ctx->dtype, s);
     }
     // ... or the residual update x += gamma * (A W^T + b) (proj, fc2).  On the two-group 256x256 tile: the
     // patch encoder's rows alone take 160x128 (two exact rounds), but with the small segments' 24 tiles more
     // the 340 tiles of 256x256 (two rounds) win: 25.5 vs 26.0 ms per step against separate launches.
-    // LayerNorm weights of the three physical segments for a launch that normalises the rows it updates
-    struct LnSet {
-        const float *w0 = nullptr, *b0 = nullptr, *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;
-    };
     // The residual update and the LayerNorm behind it in one launch (gemm_core.h resid_ln_epilogue): 16-bit contexts, the
     // 352-row tile, C in {256, 512, 1024}.  When it applies it applies at EVERY batch size (the tall tile is then taken
     // whatever tall_tile_wins says), so that a row's statistics are summed in the same order whatever batch the row is
@@ -485,16 +425,12 @@ struct MergedVit {
         return gemm_lnf_resident(ctx->dtype, s) >= 8 * (C / 256);
     }
     // returns true when xn holds LayerNorm(ln) of the updated rows
-    bool resid_all(const char* A, int K, const void* w0, const float* bb0, const float* g0, const void* w1,
-                   const float* bb1, const float* g1, const void* w2, const float* bb2, const float* g2,
-                   const LnSet* ln = nullptr, bool ln_fp8 = false /* xn / xn_s as the MX fp8 operand of the next GEMM */) {
+    bool resid_all(const char* A, int K, const SegWeights& w, const LnSet* ln = nullptr,
+                   bool ln_fp8 = false /* xn / xn_s as the MX fp8 operand of the next GEMM */) {
         const int C = ctx->C();
-        GemmParams p = base_params();
-        p.M = (int)Rtot, p.N = C, p.K = K, p.A = A, p.lda = K, p.W = w0, p.bias = bb0, p.gamma = g0;
+        GemmParams p = resid_params(Rtot, C, K, A, nullptr, nullptr, nullptr, tok);
+        set_segments(p, seg1, seg2, w);
         p.flop_rows = (int)real_rows();
-        p.res32 = tok, p.out32 = tok, p.ldc = C;
-        p.seg1 = (int)seg1, p.seg2 = (int)seg2, p.W_s1 = w1, p.bias_s1 = bb1, p.gamma_s1 = g1;
-        p.W_s2 = w2, p.bias_s2 = bb2, p.gamma_s2 = g2;
         // the two-group 256x256 kernel (the cost model rates 128x128 a hair cheaper here; measured it is not).  Its
         // 192-row form (tile config 5; the segment order above makes every boundary a multiple of 192 at one image)
         // wins for proj stand-alone (94.7 -> 80.3 us) and loses in the step (90 -> 95.6 us per launch, same box,
@@ -503,64 +439,44 @@ struct MergedVit {
         const bool pp = C >= 256 && K >= 128;
         const bool pp192 = pp && K <= 1024 && use_pp192 && seg1 % 192 == 0 && seg2 % 192 == 0;
         if (ln && pp && ln_fusable() && (ln_fp8 || !ctx->fp8)) {
-            const size_t row_tiles = (size_t)seg_row_tiles<352>((int)Rtot, (int)seg1, (int)seg2);
-            p.ln_out16 = xn, p.ln_eps = ctx->cfg.ln_eps;
-            if (ln_fp8) p.out8 = (uint8_t*)xn, p.out8_scale = xn_s, p.out8_mt = (int)(Rtot / 128);
-            p.ln_w = ln->w0, p.ln_b = ln->b0, p.ln_w_s1 = ln->w1, p.ln_b_s1 = ln->b1, p.ln_w_s2 = ln->w2, p.ln_b_s2 = ln->b2;
-            p.ln_stats = (unsigned long long*)site_buf(ctx, "vitm.ln.stats", row_tiles * (size_t)(C / 256) * 352 * 8);
-            p.ln_count = (unsigned*)site_buf(ctx, "vitm.ln.count", row_tiles * 64);   // zero when allocated, never reset
-            gemm_launch(p, A_PLAIN, EPI_RESID_SCALE, ctx->dtype, s, 10);
+            set_fused_layernorm(ctx, p, "vitm.ln.stats", "vitm.ln.count", *ln, ctx->cfg.ln_eps, xn, ln_fp8 ? (uint8_t*)xn : nullptr, xn_s);
+            gemm_launch(p, A_PLAIN, EPI_RESID_SCALE, ctx->dtype, s, CFG_PP352);
             return true;
         }
         if (pp && !pp192 && tall_tile_wins(p)) {
-            gemm_launch(p, A_PLAIN, EPI_RESID_SCALE, ctx->dtype, s, 10);
+            gemm_launch(p, A_PLAIN, EPI_RESID_SCALE, ctx->dtype, s, CFG_PP352);
             return false;
         }
-        if (pp && !pp192 && launch_with_short_tail(p, EPI_RESID_SCALE, w1, bb1, g1, w2, bb2, g2)) return false;
-        gemm_launch(p, A_PLAIN, EPI_RESID_SCALE, ctx->dtype, s, pp192 ? 5 : (pp ? 0 : -1));
+        if (pp && !pp192 && launch_with_short_tail(p, EPI_RESID_SCALE)) return false;
+        gemm_launch(p, A_PLAIN, EPI_RESID_SCALE, ctx->dtype, s, pp192 ? CFG_PP192 : (pp ? CFG_PP256 : -1));
         return false;
     }
 
     // the MX fp8 form of gemm_all / resid_all (gemm_fp8.hip): A = xn or hid as e4m3 + block scales
     // ln (fc2 / proj only): also write LayerNorm(ln) of the updated rows into xn / xn_s as MX fp8 -- the tall tile's residual
     // epilogue; returns true when it did
-    bool gemm8(const void* A8, const uint8_t* As, int K, int N, const VitBlockW& b0, const VitBlockW& b1,
-               const VitBlockW& b2, int which /*0 qkv, 1 fc1, 2 fc2, 3 proj*/, bool hid16_out = false, const LnSet* ln = nullptr) {
-        GemmParams p = base_params();
-        auto w8 = [&](const VitBlockW& b) { return which == 0 ? b.qkv_w8 : (which == 1 ? b.fc1_w8 : (which == 2 ? b.fc2_w8 : b.proj_w8)); };
-        auto ws = [&](const VitBlockW& b) { return which == 0 ? b.qkv_ws : (which == 1 ? b.fc1_ws : (which == 2 ? b.fc2_ws : b.proj_ws)); };
-        auto bias = [&](const VitBlockW& b) { return which == 0 ? b.qkv_b : (which == 1 ? b.fc1_b : (which == 2 ? b.fc2_b : b.proj_b)); };
-        auto gamma = [&](const VitBlockW& b) { return which == 3 ? b.ls1 : b.ls2; };
-        p.M = (int)Rtot, p.N = N, p.K = K, p.A = A8, p.lda = K, p.a_scale = As, p.a_mt = (int)(Rtot / 128);
+    bool gemm8(const void* A8, const uint8_t* As, int K, int N, const SegWeights& w, int which /*0 qkv, 1 fc1, 2 fc2, 3 proj*/,
+               bool hid16_out = false, const LnSet* ln = nullptr) {
+        GemmParams p = which >= 2 ? resid_params(Rtot, N, K, A8, nullptr, nullptr, nullptr, tok)
+                                  : linear_params(Rtot, N, K, A8, nullptr, nullptr, nullptr, nullptr);
+        set_segments(p, seg1, seg2, w);
+        set_fp8_operands(p, As, w.w_scale[0]);
         p.flop_rows = (int)real_rows();
-        p.W = w8(b0), p.w_scale = ws(b0), p.bias = bias(b0), p.ldc = N;
-        p.seg1 = (int)seg1, p.seg2 = (int)seg2;
-        p.W_s1 = w8(b1), p.w_scale_s1 = ws(b1), p.bias_s1 = bias(b1);
-        p.W_s2 = w8(b2), p.w_scale_s2 = ws(b2), p.bias_s2 = bias(b2);
         if (which == 0) {
             p.out16 = qkv;
-            p.qcols = ctx->C(), p.qscale = kAttnQScale;
+            set_scaled_cols(p, ctx->C(), kAttnQScale);
             gemm_fp8_launch(p, EPI_STORE, s);
         } else if (which == 1) {
             p.act = ACT_GELU;
             if (hid16_out) p.out16 = hid;  // fc2 stays 16-bit: the hidden layer leaves as f16
-            else p.out8 = (uint8_t*)hid, p.out8_scale = hid_s, p.out8_mt = (int)(Rtot / 128);
+            else set_out8(p, (uint8_t*)hid, hid_s);
             gemm_fp8_launch(p, EPI_STORE, s);
         } else {
-            p.gamma = gamma(b0), p.gamma_s1 = gamma(b1), p.gamma_s2 = gamma(b2), p.res32 = tok, p.out32 = tok;
             static const bool fp8_lnf = !(getenv("ME_FP8_LN_FUSE") && atoi(getenv("ME_FP8_LN_FUSE")) == 0);
-            if (ln && fp8_lnf && ln_fusable()) {
-                const int C = ctx->C();
-                const size_t row_tiles = (size_t)seg_row_tiles<352>((int)Rtot, (int)seg1, (int)seg2);
-                p.ln_out16 = xn, p.ln_eps = ctx->cfg.ln_eps;
-                p.out8 = (uint8_t*)xn, p.out8_scale = xn_s, p.out8_mt = (int)(Rtot / 128);
-                p.ln_w = ln->w0, p.ln_b = ln->b0, p.ln_w_s1 = ln->w1, p.ln_b_s1 = ln->b1, p.ln_w_s2 = ln->w2, p.ln_b_s2 = ln->b2;
-                p.ln_stats = (unsigned long long*)site_buf(ctx, "vitm.ln.stats", row_tiles * (size_t)(C / 256) * 352 * 8);
-                p.ln_count = (unsigned*)site_buf(ctx, "vitm.ln.count", row_tiles * 64);   // zero when allocated, never reset
-                gemm_fp8_launch(p, EPI_RESID_SCALE, s);
-                return true;
-            }
+            const bool fuse = ln && fp8_lnf && ln_fusable();
+            if (fuse) set_fused_layernorm(ctx, p, "vitm.ln.stats", "vitm.ln.count", *ln, ctx->cfg.ln_eps, xn, (uint8_t*)xn, xn_s);
             gemm_fp8_launch(p, EPI_RESID_SCALE, s);
+            return fuse;
         }
         return false;
     }
@@ -569,6 +485,14 @@ struct MergedVit {
     void block(int i) {
         const VitBlockW &b0 = p0.blocks[i], &b1 = p1.blocks[i], &b2 = p2.blocks[i];  // by physical segment
         const int C = ctx->C(), T = ctx->T(), heads = ctx->cfg.num_heads;
+        // norm2 of this block and norm1 of the next, for the residual launches that write them (resid_all, gemm8)
+        const LnSet ln2{b0.ln2_w, b0.ln2_b, b1.ln2_w, b1.ln2_b, b2.ln2_w, b2.ln2_b};
+        LnSet next;
+        const bool has_next = i + 1 < ctx->cfg.depth;
+        if (has_next) {
+            const VitBlockW &n0 = p0.blocks[i + 1], &n1 = p1.blocks[i + 1], &n2 = p2.blocks[i + 1];
+            next = LnSet{n0.ln1_w, n0.ln1_b, n1.ln1_w, n1.ln1_b, n2.ln1_w, n2.ln1_b};
+        }
         if (ctx->fp8) {
             // BASELINE configs[3]: the linears named by me_model_config.fp8_linears (default: all four) run on the scaled
             // fp8 MFMA, each fed by a producer that writes MX fp8 -- LayerNorm (qkv, fc1), the attention kernel's own
@@ -582,10 +506,10 @@ struct MergedVit {
                 if (!xn_is_norm1_fp8)
                     layernorm_fp8_launch(tok, b0.ln1_w, b0.ln1_b, (uint8_t*)xn, xn_s, Rtot, C, ctx->cfg.ln_eps, s, &segs);
                 xn_is_norm1_fp8 = false;
-                gemm8(xn, xn_s, C, 3 * C, b0, b1, b2, 0);
+                gemm8(xn, xn_s, C, 3 * C, weights(i, &VitBlockW::qkv_w8, &VitBlockW::qkv_b, nullptr, &VitBlockW::qkv_ws), 0);
             } else {
                 layernorm_launch(tok, b0.ln1_w, b0.ln1_b, xn, nullptr, Rtot, C, ctx->cfg.ln_eps, ctx->dtype, s, &segs);
-                gemm_all(xn, C, b0.qkv_w, b1.qkv_w, b2.qkv_w, b0.qkv_b, b1.qkv_b, b2.qkv_b, 3 * C, qkv, ACT_NONE, C);
+                gemm_all(xn, C, weights(i, &VitBlockW::qkv_w, &VitBlockW::qkv_b), 3 * C, qkv, ACT_NONE, C);
             }
             if (p8) {
                 // the attention kernel writes the projection's fp8 operand itself (the bytes a separate
@@ -599,24 +523,22 @@ struct MergedVit {
                     attention_launch(qkv, att, windows, T, heads, ctx->dtype, s, &segs, att8, att_s, Rtot / 128, true);
                 }
                 // ... and its residual epilogue norm2 as fc1's fp8 operand (the tall fp8 tile)
-                const LnSet ln2{b0.ln2_w, b0.ln2_b, b1.ln2_w, b1.ln2_b, b2.ln2_w, b2.ln2_b};
-                xn_is_norm2_fp8 = gemm8(att8, att_s, C, C, b0, b1, b2, 3, false, f18 ? &ln2 : nullptr);
+                const SegWeights w8 = weights(i, &VitBlockW::proj_w8, &VitBlockW::proj_b, &VitBlockW::ls1, &VitBlockW::proj_ws);
+                xn_is_norm2_fp8 = gemm8(att8, att_s, C, C, w8, 3, false, f18 ? &ln2 : nullptr);
             } else {
                 attention_launch(qkv, att, windows, T, heads, ctx->dtype, s, &segs, nullptr, nullptr, 0, true);
                 // the 16-bit projection's residual epilogue writes norm2 as fc1's MX fp8 operand (gemm_core.h resid_ln_epilogue)
-                const LnSet ln2{b0.ln2_w, b0.ln2_b, b1.ln2_w, b1.ln2_b, b2.ln2_w, b2.ln2_b};
-                xn_is_norm2_fp8 = resid_all(att, C, b0.proj_w, b0.proj_b, b0.ls1, b1.proj_w, b1.proj_b, b1.ls1, b2.proj_w, b2.proj_b,
-                                            b2.ls1, f18 ? &ln2 : nullptr, true);
+                xn_is_norm2_fp8 = resid_all(att, C, weights(i, &VitBlockW::proj_w, &VitBlockW::proj_b, &VitBlockW::ls1), f18 ? &ln2 : nullptr, true);
             }
             set_ln(b1.ln2_w, b1.ln2_b, b2.ln2_w, b2.ln2_b);
             if (f18) {
                 if (!xn_is_norm2_fp8)
                     layernorm_fp8_launch(tok, b0.ln2_w, b0.ln2_b, (uint8_t*)xn, xn_s, Rtot, C, ctx->cfg.ln_eps, s, &segs);
                 xn_is_norm2_fp8 = false;
-                gemm8(xn, xn_s, C, 4 * C, b0, b1, b2, 1, !f28);
+                gemm8(xn, xn_s, C, 4 * C, weights(i, &VitBlockW::fc1_w8, &VitBlockW::fc1_b, nullptr, &VitBlockW::fc1_ws), 1, !f28);
             } else {
                 layernorm_launch(tok, b0.ln2_w, b0.ln2_b, xn, nullptr, Rtot, C, ctx->cfg.ln_eps, ctx->dtype, s, &segs);
-                gemm_all(xn, C, b0.fc1_w, b1.fc1_w, b2.fc1_w, b0.fc1_b, b1.fc1_b, b2.fc1_b, 4 * C, hid, ACT_GELU);
+                gemm_all(xn, C, weights(i, &VitBlockW::fc1_w, &VitBlockW::fc1_b), 4 * C, hid, ACT_GELU);
             }
             if (f28) {
                 const uint8_t* h8 = (const uint8_t*)hid;
@@ -625,15 +547,11 @@ struct MergedVit {
                     quantize_f16_to_fp8_launch(hid, q, hid_s, Rtot, 4 * C, 0, s);
                     h8 = q;
                 }
-                LnSet next;
-                const bool fuse_next = q8 && i + 1 < ctx->cfg.depth;  // the next block's qkv reads norm1 as fp8
-                if (fuse_next) {
-                    const VitBlockW &n0 = p0.blocks[i + 1], &n1 = p1.blocks[i + 1], &n2 = p2.blocks[i + 1];
-                    next = LnSet{n0.ln1_w, n0.ln1_b, n1.ln1_w, n1.ln1_b, n2.ln1_w, n2.ln1_b};
-                }
-                xn_is_norm1_fp8 = gemm8(h8, hid_s, 4 * C, C, b0, b1, b2, 2, false, fuse_next ? &next : nullptr);
+                const bool fuse_next = q8 && has_next;  // the next block's qkv reads norm1 as fp8
+                const SegWeights w8 = weights(i, &VitBlockW::fc2_w8, &VitBlockW::fc2_b, &VitBlockW::ls2, &VitBlockW::fc2_ws);
+                xn_is_norm1_fp8 = gemm8(h8, hid_s, 4 * C, C, w8, 2, false, fuse_next ? &next : nullptr);
             } else {
-                resid_all(hid, 4 * C, b0.fc2_w, b0.fc2_b, b0.ls2, b1.fc2_w, b1.fc2_b, b1.ls2, b2.fc2_w, b2.fc2_b, b2.ls2);
+                resid_all(hid, 4 * C, weights(i, &VitBlockW::fc2_w, &VitBlockW::fc2_b, &VitBlockW::ls2));
             }
             if (taps.fn) taps.fn(taps.user, i, tok + row_main * C);
             return;
@@ -644,22 +562,14 @@ struct MergedVit {
             layernorm_launch(tok, b0.ln1_w, b0.ln1_b, xn, nullptr, Rtot, C, ctx->cfg.ln_eps, ctx->dtype, s, &segs);
         }
         xn_is_norm1 = false;
-        gemm_all(xn, C, b0.qkv_w, b1.qkv_w, b2.qkv_w, b0.qkv_b, b1.qkv_b, b2.qkv_b, 3 * C, qkv, ACT_NONE, C);
+        gemm_all(xn, C, weights(i, &VitBlockW::qkv_w, &VitBlockW::qkv_b), 3 * C, qkv, ACT_NONE, C);
         attention_launch(qkv, att, W0 + W1 * (fov ? 2 : 1), T, heads, ctx->dtype, s, &segs, nullptr, nullptr, 0, true);
-        const LnSet ln2{b0.ln2_w, b0.ln2_b, b1.ln2_w, b1.ln2_b, b2.ln2_w, b2.ln2_b};
-        if (!resid_all(att, C, b0.proj_w, b0.proj_b, b0.ls1, b1.proj_w, b1.proj_b, b1.ls1, b2.proj_w, b2.proj_b, b2.ls1, &ln2)) {
+        if (!resid_all(att, C, weights(i, &VitBlockW::proj_w, &VitBlockW::proj_b, &VitBlockW::ls1), &ln2)) {
             set_ln(b1.ln2_w, b1.ln2_b, b2.ln2_w, b2.ln2_b);
             layernorm_launch(tok, b0.ln2_w, b0.ln2_b, xn, nullptr, Rtot, C, ctx->cfg.ln_eps, ctx->dtype, s, &segs);
         }
-        gemm_all(xn, C, b0.fc1_w, b1.fc1_w, b2.fc1_w, b0.fc1_b, b1.fc1_b, b2.fc1_b, 4 * C, hid, ACT_GELU);
-        LnSet next;
-        const bool has_next = i + 1 < ctx->cfg.depth;
-        if (has_next) {
-            const VitBlockW &n0 = p0.blocks[i + 1], &n1 = p1.blocks[i + 1], &n2 = p2.blocks[i + 1];
-            next = LnSet{n0.ln1_w, n0.ln1_b, n1.ln1_w, n1.ln1_b, n2.ln1_w, n2.ln1_b};
-        }
-        xn_is_norm1 = resid_all(hid, 4 * C, b0.fc2_w, b0.fc2_b, b0.ls2, b1.fc2_w, b1.fc2_b, b1.ls2, b2.fc2_w, b2.fc2_b, b2.ls2,
-                                has_next ? &next : nullptr);
+        gemm_all(xn, C, weights(i, &VitBlockW::fc1_w, &VitBlockW::fc1_b), 4 * C, hid, ACT_GELU);
+        xn_is_norm1 = resid_all(hid, 4 * C, weights(i, &VitBlockW::fc2_w, &VitBlockW::fc2_b, &VitBlockW::ls2), has_next ? &next : nullptr);
         if (taps.fn) taps.fn(taps.user, i, tok + row_main * C);
     }
 
@@ -756,8 +666,7 @@ void stage_encoder_trunk(me_ctx* ctx, const float* img32, int B, bool fov_async 
                  s, sp);
     if (fov_async) {
         float* lin32 = (float*)site_buf(ctx, "fov.lin", (size_t)B * T * (dec / 2) * 4);
-        linear(ctx, run.final16(2), (int64_t)B * T, C, ctx->w.fov_lin_w, dec / 2, ctx->w.fov_lin_b, nullptr, lin32,
-               dec / 2, ACT_NONE, s);
+        linear(ctx, run.final16(2), (int64_t)B * T, C, ctx->w.fov_lin_w, dec / 2, ctx->w.fov_lin_b, nullptr, lin32, ACT_NONE, s);
     }
     report(ctx, 0.55f, "reshaping patch encodings");
     // encoder.rs:263,285-294: split_with_sizes + merge
@@ -785,15 +694,11 @@ void stage_encoder_trunk(me_ctx* ctx, const float* img32, int B, bool fov_async 
           false, cat_stride, ACT_NONE, s, sp, sp, 2 * e3);
     report(ctx, 0.95f, "fusing lowres");
     void* enc4 = site_buf(ctx, "enc4.16b", bordered_bytes(B, H4, H4, e3) * wide_dec);
-    {
-        GemmParams p = base_params();
-        const int K = 2 * e3 * (int)wide;
-        p.M = B * H4 * H4, p.N = e3, p.K = K, p.flop_k = 2 * e3, p.A = cat, p.lda = K, p.W = ctx->w.fuse_w;
-        p.bias = ctx->w.fuse_b, p.out16 = enc4, p.out16_border = 1, p.ldc = e3;
-        p.out_H = H4, p.out_W = H4;
-        if (sp_dec) set_out16_split(p, e3);
-        gemm_launch(p, A_PLAIN, EPI_STORE, ctx->dtype, s);
-    }
+    GemmParams p = linear_params((int64_t)B * H4 * H4, e3, 2 * e3, cat, ctx->w.fuse_w, ctx->w.fuse_b, enc4, nullptr);
+    set_a_parts(p, (int)wide);
+    set_out16_bordered(p, H4, H4);
+    set_out16_parts(p, e3, (int)wide_dec);
+    gemm_launch(p, A_PLAIN, EPI_STORE, ctx->dtype, s);
 }
 
 // the head behind head[0] as one launch on the half-resolution map (stage_head): needs the un-split chain and the 128-channel
@@ -887,7 +792,7 @@ void stage_decoder_levels(me_ctx* ctx, int B, bool want_features32, int first, i
         }
         void* v16 = site_buf(ctx, L + ".v16", (size_t)B * h * h * dec * 2 * wf);
         ConvOut o4;
-        o4.out16 = v16, o4.res32 = out32, o4.split16 = spf, o4.triple16 = fused;
+        o4.out16 = v16, o4.res32 = out32, o4.parts16 = (int)wf;
         conv(ctx, t2_r16, B, h, h, dec, fw.resnet2.w[1], dec, 3, 1, fw.resnet2.b[1], o4, s);
         if (fused) {
             // out_conv(deconv(v)) as ONE launch: f32 features of the next level straight from the pixel shuffle
@@ -908,18 +813,16 @@ void stage_decoder_levels(me_ctx* ctx, int B, bool want_features32, int first, i
         const int64_t Mo = (int64_t)B * ho * ho;
         if (i > 0) {
             feat32 = (float*)site_buf(ctx, L + ".feat.f32", (size_t)Mo * dec * 4);
-            linear(ctx, pre, Mo, dec, fw.out_w, dec, fw.out_b, nullptr, feat32, dec, ACT_NONE, s, spf);
+            linear(ctx, pre, Mo, dec, fw.out_w, dec, fw.out_b, nullptr, feat32, ACT_NONE, s, spf);
         } else {
             // final features: 16-bit zero-bordered operand of head[0]; f32 copy for the ABI
             float* f32 = want_features32 ? (float*)site_buf(ctx, "features.f32", (size_t)Mo * dec * 4)
                                          : nullptr;
             void* f16b = site_buf(ctx, "features.16b", bordered_bytes(B, ho, ho, dec) * (sp_head ? 2 : 1));
-            GemmParams p = base_params();
-            const int K = dec * (int)wf;
-            p.M = (int)Mo, p.N = dec, p.K = K, p.flop_k = dec, p.A = pre, p.lda = K, p.W = fw.out_w;
-            p.bias = fw.out_b, p.out16 = f16b, p.out16_border = 1, p.out32 = f32, p.ldc = dec;
-            p.out_H = ho, p.out_W = ho;
-            if (sp_head) set_out16_split(p, dec);
+            GemmParams p = linear_params(Mo, dec, dec, pre, fw.out_w, fw.out_b, f16b, f32);
+            set_a_parts(p, (int)wf);
+            set_out16_bordered(p, ho, ho);
+            set_out16_parts(p, dec, sp_head ? 2 : 1);
             gemm_launch(p, A_PLAIN, EPI_STORE, ctx->dtype, s);
         }
     }
@@ -936,6 +839,7 @@ void stage_head(me_ctx* ctx, int B, const float* f_norm_dev, bool clamp, float* 
     const bool sp = ctx->split(SPLIT_HEAD);
     const size_t wide = sp ? 2 : 1;
     const void* f16b = ctx->bufs.at("features.16b").p;
+    const float clamp_lo = clamp ? 1e-4f : -INFINITY, clamp_hi = clamp ? 1e4f : INFINITY;  // mod.rs:362
     // mod.rs:326-333 behind head[0]: ConvTranspose -> conv3x3 -> ReLU -> conv1x1 -> ReLU as ONE launch on the half-resolution map,
     // the two linear layers composed at load time (weights.hip compose_head): the [B, 128, 1536, 1536] tensor between them (605 MB
     // written and read back) never exists.  Needs the un-split chain and the 128-channel halo tile's shapes; ME_HEAD_COMPOSED=0:
@@ -951,34 +855,24 @@ void stage_head(me_ctx* ctx, int B, const float* f_norm_dev, bool clamp, float* 
         } else {
             conv(ctx, f16b, B, Hh, Hh, dec, ctx->w.head0_w, dec / 2, 3, 1, ctx->w.head0_b, o, s, false);
         }
-        GemmParams p = base_params();
-        p.M = B * Hh * Hh, p.N = 128, p.K = 9 * (dec / 2);
-        p.A = h0b, p.in_Hp = Hh + 2, p.in_Wp = Hh + 2, p.Cin = dec / 2, p.out_H = Hh, p.out_W = Hh;
-        p.KH = 3, p.KW = 3, p.stride = 1, p.W = ctx->w.head_fused_w, p.bias = ctx->w.head_fused_b;
-        p.tap_bias = ctx->w.head_fused_b + 32;
-        // head.4.weight as the 32 floats the epilogue reads (compose_head pads the head_dims[0] of the checkpoint with zeros)
-        p.w2 = ctx->w.head_fused_b + 32 + 9 * 32, p.b2 = ctx->w.head4_b, p.f_norm = f_norm_dev;
-        p.pixels_per_image = S * S, p.out32 = depth_dev;
-        p.clamp_lo = clamp ? 1e-4f : -INFINITY, p.clamp_hi = clamp ? 1e4f : INFINITY;
-        head_composed_launch(p, ctx->dtype, s);
+        // head_fused_b: the bias [32], its per-tap shares [9][32], and head.4.weight as the 32 floats the epilogue reads
+        // (compose_head pads the head_dims[0] of the checkpoint with zeros)
+        const float* fb = ctx->w.head_fused_b;
+        head_composed_launch(head_composed_params(h0b, B, Hh, Hh, dec / 2, ctx->w.head_fused_w, fb, fb + 32, fb + 32 + 9 * 32,
+                                                  ctx->w.head4_b, f_norm_dev, clamp_lo, clamp_hi, depth_dev),
+                             ctx->dtype, s);
         return;
     }
     void* h0 = site_buf(ctx, "head.h0", (size_t)B * Hh * Hh * (dec / 2) * 2 * wide);
     ConvOut o;
-    o.out16 = h0, o.split16 = sp;
+    o.out16 = h0, o.parts16 = (int)wide;
     conv(ctx, f16b, B, Hh, Hh, dec, ctx->w.head0_w, dec / 2, 3, 1, ctx->w.head0_b, o, s, sp);
     void* h1 = site_buf(ctx, "head.h1b", bordered_bytes(B, S, S, dec / 2) * wide);
     convt(ctx, h0, B, Hh, Hh, dec / 2, ctx->w.head1_w, dec / 2, ctx->w.head1_b, nullptr, h1, true, 0,
           ACT_NONE, s, sp, sp);
-    GemmParams p = base_params();
-    const int hc = (dec / 2) * (int)wide;
-    p.M = B * S * S, p.N = c.head_dims[0], p.K = 9 * hc, p.flop_k = 9 * (dec / 2);
-    p.A = h1, p.in_Hp = S + 2, p.in_Wp = S + 2, p.Cin = hc, p.out_H = S, p.out_W = S;
-    p.KH = 3, p.KW = 3, p.stride = 1, p.W = ctx->w.head2_w, p.bias = ctx->w.head2_b;
-    p.w2 = ctx->w.head4_w, p.b2 = ctx->w.head4_b, p.f_norm = f_norm_dev;
-    p.pixels_per_image = S * S, p.out32 = depth_dev;
-    if (clamp) p.clamp_lo = 1e-4f, p.clamp_hi = 1e4f;
-    gemm_launch(p, A_CONV, EPI_HEAD_FINAL, ctx->dtype, s);
+    gemm_launch(head_final_params(h1, B, S, S, dec / 2, ctx->w.head2_w, c.head_dims[0], ctx->w.head2_b, ctx->w.head4_w, ctx->w.head4_b,
+                                  f_norm_dev, clamp_lo, clamp_hi, depth_dev, sp),
+                A_CONV, EPI_HEAD_FINAL, ctx->dtype, s);
 }
 
 // fov.rs:40-63: the FOV encoder (third ViT-L on "enc.x2", the 1/4 image) and its Linear
@@ -991,8 +885,7 @@ void stage_fov_vit(me_ctx* ctx, int B, hipStream_t s) {
     void* tok16 = site_buf(ctx, "fov.tok16", (size_t)B * T * C * 2);
     vit_forward(ctx, ME_VIT_FOV_ENCODER, patches, B, VitTaps(), tok16, nullptr, "vit.fov", s);
     float* lin32 = (float*)site_buf(ctx, "fov.lin", (size_t)B * T * (dec / 2) * 4);
-    linear(ctx, tok16, (int64_t)B * T, C, ctx->w.fov_lin_w, dec / 2, ctx->w.fov_lin_b, nullptr, lin32,
-           dec / 2, ACT_NONE, s);
+    linear(ctx, tok16, (int64_t)B * T, C, ctx->w.fov_lin_w, dec / 2, ctx->w.fov_lin_b, nullptr, lin32, ACT_NONE, s);
 }
 
 // fov.rs:66-88: the convolutional tail; needs "fov.lin" (stage_fov_vit) and "lowres.f32" (decoder)

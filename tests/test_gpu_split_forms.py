@@ -1,6 +1,7 @@
 """Kernel-level tests (-m gpu) of the split-operand forms of the GEMM / conv / ConvTranspose epilogues (gemm_core.h
 store_16bit_lo, GemmParams::ldc16 / lo_off16 / hi2_off16) through me_op_conv2d_forms, me_op_linear_split and
-me_op_conv_transpose2x2_forms, which fill GemmParams as pipeline.hip's conv / linear / convt helpers do.
+me_op_conv_transpose2x2_forms, which build GemmParams with the code pipeline.hip's conv / linear / convt helpers use
+(csrc/gemm_params.h).
 
 A split value is the pair hi = T(v), lo = T(v - hi).  On the INPUT side the kernel only sees K (or Cin) doubled or
 tripled against weights that repeat themselves (weights.hip); the tests build those operands.  Every check is one of
