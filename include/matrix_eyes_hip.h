@@ -404,6 +404,39 @@ int32_t me_ctx_set_jpeg_entropy(me_ctx* ctx, int32_t mode);
    [2] entropy kernels with the looks at their changed counts (HIP events). */
 int32_t me_last_jpeg_entropy(me_ctx* ctx, int64_t report[8], double ms[3]);
 
+/* ---- PNG decoding on the device (reconstruction.rs:95-113 for the photo, output.rs:206-218 for vertex colours) ---------- */
+
+/* Size and EXIF span of a PNG file in memory: width / height of IHDR (before any orientation), and the offset and length
+   inside `file` of the body of the last eXIf chunk (the TIFF-structured block; 0, 0: none), which the caller parses with
+   what it has.  Needs neither a GPU nor a context (ctx-less errors: me_last_error(NULL)).  A null pointer is
+   ME_ERR_BAD_ARG, and so is a file whose chunks or header the decoder refuses, with the decoder's message. */
+int32_t me_png_info(const uint8_t* file, int64_t nbytes, int32_t* width, int32_t* height,
+                    int64_t* exif_offset, int64_t* exif_nbytes);
+/* The picture of a PNG file (every colour type and bit depth of the specification's table 11.1, interlaced or not; alpha
+   dropped, 16-bit samples rounded to 8, as DynamicImage::into_rgb8 does), byte for byte what the C++ host layer's decoder
+   writes (host/png_decoder.cpp decode_png) followed by apply_orientation(orientation).  The host inflates the IDAT data
+   into pinned memory band by band; every finished band of rows is copied up and its unfilter launch queued behind it, so
+   the GPU works under the inflate; the conversion to RGB, the de-interlacing and the orientation are one more kernel.
+   rgb [h,w,3] is the ORIENTED size (w and h swap for orientations 5..8), a host or device pointer; enqueued on the
+   context's stream: a device rgb is not synchronised (except for a palette file, whose index check comes back from the
+   device), a host rgb is.  A null pointer or an orientation outside 1..8 is ME_ERR_BAD_ARG; a size that does not match the
+   file ME_ERR_BAD_SHAPE; a file the decoder refuses ME_ERR_BAD_ARG with the host decoder's own message ("<png>: ..." in
+   place of a path): when the device path meets a defect the host decoder runs whole and its words stand.  On an error
+   the destination's contents are unspecified and the context stays usable.  Needs a context, not finalised weights.
+   Scratch belongs to the context and grows to the high-water mark. */
+int32_t me_png_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t orientation,
+                           uint8_t* rgb, int32_t w, int32_t h);
+/* reconstruction.rs:95-113 in one call: me_png_decode_rgb8 into context-owned device memory, then
+   me_resize_lanczos3_rgb8 to dst [nh,nw,3] (host or device): only the resized picture can cross to the host.  Errors as
+   the two calls; the picture's sides are bound by ME_RESIZE_MAX_DIM. */
+int32_t me_png_decode_resized_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t orientation,
+                                   uint8_t* dst, int32_t nw, int32_t nh);
+/* Legs of the context's last PNG decode in milliseconds: [0] inflate on the host (wall clock; the uploads and launches
+   are queued from inside it), [1] uploads of the bands, [2] png_unfilter_kernel launches, [3] png_finish_kernel,
+   [4] download to a host rgb (0 for a device one); [1]..[4] are HIP event times, summed over the bands.  Synchronises the
+   context's stream. */
+int32_t me_last_png_timing(me_ctx* ctx, double ms_out[5]);
+
 /* output.rs:264-363 IndexedMesh::new + for_each_face + remap_face.
    depth [height,width] (DepthMap.data, stride `width`).  vertex_index [height*width]: the
    first-use vertex id or -1.  faces [nfaces,3] remapped vertex ids in the reference's

@@ -226,6 +226,19 @@ int64_t me_op_lanczos3_table(int32_t len_in, int32_t len_out, int32_t* left, int
    yardstick me_jpeg_decode_rgb8 is measured against in the same process (tools/bench_jpeg.py).  HOST arrays only, no
    context, no GPU; rgb [h,w,3].  0, or < 0 on a null pointer, a size that does not match or a file the decoder refuses. */
 int32_t me_op_jpeg_decode_host(const uint8_t* file, int64_t nbytes, uint8_t* rgb, int32_t w, int32_t h);
+/* The C++ host layer's PNG decoder (host/png_decoder.cpp decode_png, no orientation) from inside the library: the
+   yardstick me_png_decode_rgb8 is measured against in the same process (tools/bench_png_decode.py).  HOST arrays only, no
+   context, no GPU; rgb [h,w,3].  0, or < 0 on a null pointer (-1), a size that does not match (-2) or a file the decoder
+   refuses (-3: its message is me_last_error(NULL)). */
+int32_t me_op_png_decode_host(const uint8_t* file, int64_t nbytes, uint8_t* rgb, int32_t w, int32_t h);
+/* The unfilter leg of me_png_decode_rgb8 alone: `stream` is the filtered stream of a picture of the given IHDR fields
+   (filter byte plus row, pass after pass: what zlib inflates the IDAT data to), nbytes its length; `out` receives the
+   reconstructed stream in the same layout (filter bytes kept).  Host or device pointers, out == stream allowed for device
+   memory.  band_rows: picture rows per launch (0: the default; a small value makes a small picture span many launches).
+   A host stream with a filter byte above 4 is ME_ERR_BAD_ARG ("bad PNG filter"); in device memory such a row is taken as
+   filter 0.  A length that does not match the fields is ME_ERR_BAD_SHAPE. */
+int32_t me_op_png_unfilter(me_ctx* ctx, const uint8_t* stream, int64_t nbytes, int32_t width, int32_t height,
+                           int32_t bit_depth, int32_t colour_type, int32_t interlace, int32_t band_rows, uint8_t* out);
 /* The quantised DCT coefficients of a JPEG file as the host decoder makes them (decode_jpeg_coefficients): all components
    one after the other, natural order, `count` int16_t in all (the layout jpeg_idct_kernel reads).  HOST arrays only, no
    context, no GPU.  0, or < 0 on a null pointer (-1), a count that does not match (-2) or a file the decoder refuses (-3). */

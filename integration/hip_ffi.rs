@@ -116,6 +116,10 @@ extern "C" {
     pub fn me_last_jpeg_timing(ctx: *mut MeCtx, ms_out: *mut f64) -> i32;
     pub fn me_ctx_set_jpeg_entropy(ctx: *mut MeCtx, mode: i32) -> i32;
     pub fn me_last_jpeg_entropy(ctx: *mut MeCtx, report: *mut i64, ms: *mut f64) -> i32;
+    pub fn me_png_info(file: *const u8, nbytes: i64, width: *mut i32, height: *mut i32, exif_offset: *mut i64, exif_nbytes: *mut i64) -> i32;
+    pub fn me_png_decode_rgb8(ctx: *mut MeCtx, file: *const u8, nbytes: i64, orientation: i32, rgb: *mut u8, w: i32, h: i32) -> i32;
+    pub fn me_png_decode_resized_rgb8(ctx: *mut MeCtx, file: *const u8, nbytes: i64, orientation: i32, dst: *mut u8, nw: i32, nh: i32) -> i32;
+    pub fn me_last_png_timing(ctx: *mut MeCtx, ms_out: *mut f64) -> i32;
     pub fn me_png_encode_rgb8(ctx: *mut MeCtx, rgb: *const u8, w: i32, h: i32, png_dev: *mut *const u8, nbytes: *mut i64) -> i32;
     pub fn me_output_png(ctx: *mut MeCtx, rgb: *const u8, w: i32, h: i32, destination_path: *const c_char) -> i32;
     pub fn me_output_depth_map_png(ctx: *mut MeCtx, depth: *const f32, data_width: i32, data_height: i32, min_depth: f32, max_depth: f32, minmax_dev: *const f32, out_w: i32, out_h: i32, destination_path: *const c_char) -> i32;

@@ -85,6 +85,10 @@ SIGNATURES = {
     "me_jpeg_decode_resized_rgb8": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32]),
     "me_last_jpeg_timing": (_i32, [_vp, C.POINTER(C.c_double)]),
     "me_ctx_set_jpeg_entropy": (_i32, [_vp, _i32]),
+    "me_png_info": (_i32, [_vp, _i64, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64)]),
+    "me_png_decode_rgb8": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32]),
+    "me_png_decode_resized_rgb8": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32]),
+    "me_last_png_timing": (_i32, [_vp, C.POINTER(C.c_double)]),
     "me_last_jpeg_entropy": (_i32, [_vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
     "me_png_encode_rgb8": (_i32, [_vp, _vp, _i32, _i32, C.POINTER(_vp), C.POINTER(_i64)]),
     "me_output_png": (_i32, [_vp, _vp, _i32, _i32, C.c_char_p]),
@@ -158,6 +162,8 @@ SIGNATURES = {
     "me_op_lanczos3_table": (_i64, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32), _i64]),
     "me_op_jpeg_decode_host": (_i32, [_vp, _i64, _vp, _i32, _i32]),
     "me_op_jpeg_coefficients_host": (_i32, [_vp, _i64, _vp, _i64]),
+    "me_op_png_decode_host": (_i32, [_vp, _i64, _vp, _i32, _i32]),
+    "me_op_png_unfilter": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "me_op_jpeg_entropy": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64]),
     "me_op_jpeg_encode_host": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _i64, C.POINTER(_i64)]),
     "me_last_jpeg_encode": (_i32, [_vp, C.POINTER(_i64), C.POINTER(C.c_double)]),

@@ -117,7 +117,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         return int(e.code)
     from ._lib import MatrixEyesError
     from .depth_pro import (DepthProModelLoader, resolve_jpeg_decoder, resolve_jpeg_encoder, resolve_jpeg_entropy,
-                            resolve_jpeg_quality, resolve_jpeg_subsampling, resolve_png_encoder, resolve_resampler)
+                            resolve_jpeg_quality, resolve_jpeg_subsampling, resolve_png_decoder, resolve_png_encoder,
+                            resolve_resampler)
     from .reconstruction import extract_depth
     try:
         resolve_resampler()                  # MATRIX_EYES_RESAMPLER = pillow | device
@@ -128,6 +129,11 @@ def main(argv: Optional[List[str]] = None) -> int:
         resolve_png_encoder()                # MATRIX_EYES_PNG_ENCODER = pillow | device
     except MatrixEyesError as err:
         print(f"MATRIX_EYES_PNG_ENCODER: {err.message}", file=sys.stderr)
+        return 2
+    try:
+        resolve_png_decoder()                # MATRIX_EYES_PNG_DECODER = pillow | host | device
+    except MatrixEyesError as err:
+        print(f"MATRIX_EYES_PNG_DECODER: {err.message}", file=sys.stderr)
         return 2
     try:
         resolve_jpeg_decoder()               # MATRIX_EYES_JPEG_DECODER = pillow | host | device

@@ -306,6 +306,7 @@ void me_ctx_destroy(me_ctx* ctx) {
         if (kv.second.p) (void)hipFree(kv.second.p);
     me::free_resample_tables(ctx);
     me::free_jpeg_scratch(ctx);
+    me::free_png_scratch(ctx);
     if (ctx->arena) (void)hipFree(ctx->arena);
     if (ctx->arena8) (void)hipFree(ctx->arena8);
     if (ctx->status_dev) (void)hipFree(ctx->status_dev);
@@ -991,6 +992,122 @@ int32_t me_jpeg_decode_resized_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nb
     const uint8_t* full = jpeg_decode_rgb8(ctx, file, nbytes, orientation, nullptr, 0, 0, &ow, &oh);
     OutBuf o = out_buf(ctx, dst, (size_t)nw * nh * 3, "jpeg.resized");
     resize_lanczos3_rgb8(ctx, full, ow, oh, (uint8_t*)o.dev, nw, nh);
+    finish(ctx, o);
+    ME_API_END(ctx)
+}
+
+// ---- PNG decoding (png_decode.hip) ---------------------------------------------------------------------------------
+int32_t me_png_info(const uint8_t* file, int64_t nbytes, int32_t* width, int32_t* height, int64_t* exif_offset,
+                    int64_t* exif_nbytes) {
+    if (!file || nbytes < 0 || !width || !height || !exif_offset || !exif_nbytes) {
+        g_create_error = "me_png_info: null pointer";
+        return ME_ERR_BAD_ARG;
+    }
+    try {
+        const std::vector<uint8_t> bytes(file, file + nbytes);
+        const matrix_eyes::PngFrame head = matrix_eyes::parse_png_header(bytes, "<png>");
+        *width = (int32_t)head.width, *height = (int32_t)head.height;
+        *exif_offset = (int64_t)head.exif_offset, *exif_nbytes = (int64_t)head.exif_nbytes;
+    } catch (const std::exception& e) {
+        g_create_error = e.what();
+        return ME_ERR_BAD_ARG;
+    }
+    return ME_OK;
+}
+
+int32_t me_op_png_decode_host(const uint8_t* file, int64_t nbytes, uint8_t* rgb, int32_t w, int32_t h) {
+    if (!file || nbytes < 0 || !rgb) return -1;
+    try {
+        const std::vector<uint8_t> bytes(file, file + nbytes);
+        const matrix_eyes::RgbImage img = matrix_eyes::decode_png(bytes, "<png>", nullptr);
+        if ((int64_t)img.width != w || (int64_t)img.height != h) return -2;
+        std::memcpy(rgb, img.data.data(), img.data.size());
+    } catch (const std::exception& e) {
+        g_create_error = e.what();
+        return -3;
+    }
+    return 0;
+}
+
+int32_t me_png_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t orientation, uint8_t* rgb, int32_t w,
+                           int32_t h) {
+    ME_API_BEGIN(ctx)
+    check_jpeg_args("me_png_decode_rgb8", file, nbytes, orientation, rgb);
+    ME_CHECK(w > 0 && h > 0, ME_ERR_BAD_SHAPE, "me_png_decode_rgb8: %dx%d", w, h);
+    const size_t nout = (size_t)w * h * 3;
+    const bool dev = is_device_ptr(rgb);
+    int32_t ow = 0, oh = 0;
+    uint8_t* d = png_decode_rgb8(ctx, file, nbytes, orientation, dev ? rgb : nullptr, w, h, &ow, &oh);
+    if (!dev) {
+        ME_HIP(hipMemcpyAsync(rgb, d, nout, hipMemcpyDeviceToHost, ctx->stream));
+        ME_HIP(hipEventRecord(ctx->png_ev[3 * (size_t)ctx->png_timed_bands + 2], ctx->stream));
+        ctx->png_timed_download = true;
+        ME_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    ME_API_END(ctx)
+}
+
+int32_t me_png_decode_resized_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t orientation, uint8_t* dst,
+                                   int32_t nw, int32_t nh) {
+    ME_API_BEGIN(ctx)
+    check_jpeg_args("me_png_decode_resized_rgb8", file, nbytes, orientation, dst);
+    ME_CHECK(nw > 0 && nh > 0 && nw <= ME_RESIZE_MAX_DIM && nh <= ME_RESIZE_MAX_DIM, ME_ERR_BAD_SHAPE,
+             "me_png_decode_resized_rgb8: -> %dx%d", nw, nh);
+    {
+        int32_t fw = 0, fh = 0;  // the file's size before anything is inflated: the resampler's bound
+        int64_t eo = 0, en = 0;
+        if (me_png_info(file, nbytes, &fw, &fh, &eo, &en) != ME_OK) fail(ME_ERR_BAD_ARG, "%s", g_create_error.c_str());
+        check_resize_shape("me_png_decode_resized_rgb8", fw, fh, nw, nh);
+    }
+    int32_t ow = 0, oh = 0;
+    const uint8_t* full = png_decode_rgb8(ctx, file, nbytes, orientation, nullptr, 0, 0, &ow, &oh);
+    OutBuf o = out_buf(ctx, dst, (size_t)nw * nh * 3, "png.resized");
+    resize_lanczos3_rgb8(ctx, full, ow, oh, (uint8_t*)o.dev, nw, nh);
+    finish(ctx, o);
+    ME_API_END(ctx)
+}
+
+int32_t me_last_png_timing(me_ctx* ctx, double ms_out[5]) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(ms_out, ME_ERR_BAD_ARG, "me_last_png_timing: null pointer");
+    ME_CHECK(ctx->png_timed, ME_ERR_NOT_READY, "me_last_png_timing: no PNG decode has completed on this context");
+    ME_HIP(hipStreamSynchronize(ctx->stream));
+    ms_out[0] = ctx->png_inflate_ms;
+    for (int i = 1; i < 5; ++i) ms_out[i] = 0.0;
+    auto between = [&](size_t a, size_t b) {
+        float ms = 0.f;
+        ME_HIP(hipEventElapsedTime(&ms, ctx->png_ev[a], ctx->png_ev[b]));
+        return (double)ms;
+    };
+    const size_t bands = (size_t)ctx->png_timed_bands;
+    for (size_t i = 0; i < bands; ++i) ms_out[1] += between(3 * i, 3 * i + 1), ms_out[2] += between(3 * i + 1, 3 * i + 2);
+    ms_out[3] = between(3 * bands, 3 * bands + 1);
+    if (ctx->png_timed_download) ms_out[4] = between(3 * bands + 1, 3 * bands + 2);
+    ME_API_END(ctx)
+}
+
+int32_t me_op_png_unfilter(me_ctx* ctx, const uint8_t* stream, int64_t nbytes, int32_t width, int32_t height, int32_t bit_depth,
+                           int32_t colour_type, int32_t interlace, int32_t band_rows, uint8_t* out) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(stream && out && nbytes >= 0, ME_ERR_BAD_ARG, "me_op_png_unfilter: null pointer");
+    ME_CHECK(width > 0 && height > 0 && (int64_t)width * height <= matrix_eyes::kMaxPixels, ME_ERR_BAD_SHAPE, "me_op_png_unfilter: %dx%d",
+             width, height);
+    const bool depth_ok = bit_depth == 1 || bit_depth == 2 || bit_depth == 4 || bit_depth == 8 || bit_depth == 16;
+    ME_CHECK(depth_ok && me_pngdec::channels_of(colour_type) && !(bit_depth < 8 && colour_type != 0 && colour_type != 3) &&
+                 !(bit_depth == 16 && colour_type == 3) && (interlace == 0 || interlace == 1) && band_rows >= 0,
+             ME_ERR_BAD_ARG, "me_op_png_unfilter: depth %d, colour type %d, interlace %d, band_rows %d", bit_depth, colour_type, interlace,
+             band_rows);
+    const me_pngdec::Geom g = me_pngdec::make_geom(width, height, bit_depth, colour_type, interlace);
+    ME_CHECK(nbytes == g.total, ME_ERR_BAD_SHAPE, "me_op_png_unfilter: the stream of this picture has %lld bytes, not %lld",
+             (long long)g.total, (long long)nbytes);
+    if (!is_device_ptr(stream))   // a filter byte above 4 never reaches the kernel
+        for (int ps = 0; ps < g.npass; ++ps)
+            for (int32_t py = 0; g.pass[ps].pw && py < g.pass[ps].ph; ++py)
+                ME_CHECK(stream[g.pass[ps].offset + (int64_t)py * ((int64_t)g.pass[ps].stride + 1)] <= 4, ME_ERR_BAD_ARG,
+                         "me_op_png_unfilter: bad PNG filter");
+    const uint8_t* s = (const uint8_t*)to_device(ctx, stream, (size_t)nbytes, "png.op.in");
+    OutBuf o = out_buf(ctx, out, (size_t)nbytes, "png.op.out");
+    png_unfilter(ctx, s, (uint8_t*)o.dev, width, height, bit_depth, colour_type, interlace, band_rows);
     finish(ctx, o);
     ME_API_END(ctx)
 }

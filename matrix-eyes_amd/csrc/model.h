@@ -283,6 +283,20 @@ struct me_ctx {
     JpegEncodeReport jpeg_encode_report;
     bool jpeg_encode_reported = false;
     hipEvent_t jpeg_encode_ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // PNG decoding (png_decode.hip): the pinned host buffer zlib inflates into and the uploads read, grown to the high-water
+    // mark; `png_uploaded` is recorded behind the last upload of a decode, and the next decode waits for it on the host
+    // before it inflates into the buffer again.  png_status: the pinned word the finish kernel's palette status comes back
+    // in.  png_ev: the marks of the last decode (me_last_png_timing): three per band (before its upload, between upload and
+    // unfilter launch, behind the launch), then before and behind the finish kernel and behind the download.
+    uint8_t* png_pinned = nullptr;
+    size_t png_pinned_bytes = 0;
+    int32_t* png_status = nullptr;
+    hipEvent_t png_uploaded = nullptr;
+    bool png_upload_pending = false;
+    std::vector<hipEvent_t> png_ev;
+    int32_t png_timed_bands = 0;
+    bool png_timed = false, png_timed_download = false;
+    double png_inflate_ms = 0.0;
 
     // The whole extract_depth step as one hipGraph (shapes are static per batch size).  A call whose pointers
     // all live on the device and that needs no host callback is enqueued eagerly the first time it is seen,
@@ -433,6 +447,16 @@ int16_t* jpeg_pinned_buffer(me_ctx* ctx, size_t count);
 bool jpeg_entropy_decode(me_ctx* ctx, const std::vector<uint8_t>& file, int32_t subseq_bits,
                          matrix_eyes::JpegEntropyPlan& plan);
 void free_jpeg_entropy_scratch(me_ctx* ctx);
+// png_decode.hip: a PNG file in host memory -> its oriented RGB picture [oh][ow][3] in device memory, on ctx->stream;
+// arguments, result and errors as jpeg_decode_rgb8 ("png.rgb" is the context's own buffer).  The host inflates into pinned
+// memory and every finished band of rows is uploaded and unfiltered behind it.
+uint8_t* png_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t orientation, uint8_t* dst_dev,
+                         int32_t want_w, int32_t want_h, int32_t* ow, int32_t* oh);
+// the unfilter leg alone: a filtered stream -> the reconstructed stream (same layout), device pointers, src == dst allowed;
+// band_rows 0: the default
+void png_unfilter(me_ctx* ctx, const uint8_t* src_dev, uint8_t* dst_dev, int32_t width, int32_t height, int32_t depth,
+                  int32_t ctype, int32_t interlace, int32_t band_rows);
+void free_png_scratch(me_ctx* ctx);
 // png_encode.hip, jpeg_encode.hip: a finished file in the context's scratch, and the encoders that leave one there.  Both
 // synchronise (the file's size comes back to the host); the entries (output_api.hip) check the arguments first.
 struct DeviceFile {

@@ -124,6 +124,18 @@ def resolve_jpeg_decoder(jpeg_decoder=None) -> str:
     return _resolve_choice(jpeg_decoder, "MATRIX_EYES_JPEG_DECODER", "pillow", JPEG_DECODERS, "jpeg decoder", {"host": "pillow"})
 
 
+PNG_DECODERS = ("pillow", "host", "device")
+
+
+def resolve_png_decoder(png_decoder=None) -> str:
+    """Who decodes a ".png" source (reconstruction.rs:95-106 for the photo, output.rs:206-218 for the vertex colours):
+    "pillow" (the default; "host", the compiled CLI's name for its own decoder, means the same here) or "device"
+    (me_png_decode_rgb8 / me_png_decode_resized_rgb8: zlib's inflate on the host, the scanline filters, the conversion to
+    RGB, the de-interlacing and the orientation on the GPU, the compiled CLI's bytes).  None reads
+    MATRIX_EYES_PNG_DECODER; anything but these names is an argument error."""
+    return _resolve_choice(png_decoder, "MATRIX_EYES_PNG_DECODER", "pillow", PNG_DECODERS, "png decoder", {"host": "pillow"})
+
+
 JPEG_ENTROPIES = ("host", "device")
 
 
@@ -425,6 +437,62 @@ class Context:
         ms = (C.c_double * 5)()
         self._check(self.lib.me_last_jpeg_timing(self._h, ms))
         return list(ms)
+
+    @staticmethod
+    def png_info(data: bytes):
+        """(width, height, exif_offset, exif_nbytes) of a PNG file in memory (me_png_info): IHDR's size, before any
+        orientation, and the span of the last eXIf chunk's body inside `data` (0, 0: none).  No GPU."""
+        lib = L.load_library()
+        data = bytes(data)
+        w, h, off, n = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+        rc = lib.me_png_info(data, len(data), C.byref(w), C.byref(h), C.byref(off), C.byref(n))
+        if rc != L.ME_OK:
+            msg = lib.me_last_error(None)
+            raise L.MatrixEyesError(rc, msg.decode("utf-8", "replace") if msg else "")
+        return w.value, h.value, off.value, n.value
+
+    def decode_png(self, data: bytes, orientation: int = 1, out=None):
+        """The picture of a PNG file, oriented (me_png_decode_rgb8): uint8 [h, w, 3], the C++ host decoder's bytes.
+        out: a numpy array or a CUDA torch tensor of the oriented shape (a CUDA one is only queued on the context's
+        stream); None: a new numpy array."""
+        data = bytes(data)
+        w, h, _, _ = self.png_info(data)
+        if 5 <= int(orientation) <= 8:
+            w, h = h, w
+        po, out = _out(out, (h, w, 3), np.uint8)
+        self._check(self.lib.me_png_decode_rgb8(self._h, data, len(data), int(orientation), po, w, h))
+        return out
+
+    def decode_png_resized(self, data: bytes, size, orientation: int = 1, out=None):
+        """decode_png into context-owned device memory, then resize_lanczos3 to size = (nw, nh)
+        (me_png_decode_resized_rgb8, reconstruction.rs:95-113 in one call): only the resized picture leaves the device,
+        or, with a CUDA `out`, nothing does."""
+        data = bytes(data)
+        nw, nh = int(size[0]), int(size[1])
+        if nw <= 0 or nh <= 0:
+            raise L.MatrixEyesError(2, f"decode_png_resized: target size {nw}x{nh}")
+        po, out = _out(out, (nh, nw, 3), np.uint8)
+        self._check(self.lib.me_png_decode_resized_rgb8(self._h, data, len(data), int(orientation), po, nw, nh))
+        return out
+
+    def last_png_timing(self):
+        """[inflate (host), uploads, unfilter launches, finish kernel, download] of the last PNG decode, in ms"""
+        ms = (C.c_double * 5)()
+        self._check(self.lib.me_last_png_timing(self._h, ms))
+        return list(ms)
+
+    def op_png_unfilter(self, stream, width, height, bit_depth, colour_type, interlace=0, band_rows=0, out=None):
+        """me_op_png_unfilter: the filtered stream of a PNG picture (uint8 [n], numpy or a CUDA tensor) -> the
+        reconstructed stream in the same layout; band_rows 0: the default"""
+        p, keep = _in_ptr(stream, np.uint8)
+        n = int(stream.shape[0])
+        if out is None and _is_torch(stream) and stream.is_cuda:
+            import torch
+            out = torch.empty((n,), dtype=torch.uint8, device=stream.device)
+        po, out = _out(out, (n,), np.uint8)
+        self._check(self.lib.me_op_png_unfilter(self._h, p, n, int(width), int(height), int(bit_depth), int(colour_type),
+                                                int(interlace), int(band_rows), po))
+        return out
 
     @staticmethod
     def _rgb_shape(rgb, who):

@@ -1,6 +1,6 @@
 // Image file I/O and resampling for the C++ host layer (the reference uses the `image` and `kamadak-exif`
 // crates: reconstruction.rs:96-113,133-143, output.rs:133-138,192,206-218).  Decoded here: JPEG (baseline and
-// progressive Huffman, jpeg_decoder.cpp), PNG (8/16-bit, non-interlaced, zlib) and binary PPM; encoded: PNG,
+// progressive Huffman, jpeg_decoder.cpp), PNG (every colour type and depth, Adam7; png_decoder.cpp) and binary PPM; encoded: PNG,
 // baseline JPEG (jpeg_encoder.cpp) and PPM.  Anything else is an ImageError, as an unsupported format is in the reference.
 #pragma once
 #include <cstdint>
@@ -8,6 +8,8 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
+
+#include "../csrc/png_recon.h"
 
 namespace matrix_eyes {
 
@@ -40,6 +42,32 @@ RgbImage apply_orientation(const RgbImage& img, int orientation);
 // the raw TIFF-structured EXIF block (after "Exif\0\0" in a JPEG APP1 segment, or a PNG eXIf chunk)
 ImageMetadata parse_exif(const std::vector<uint8_t>& exif);
 RgbImage decode_jpeg(const std::vector<uint8_t>& file, const std::string& path, std::vector<uint8_t>* exif);
+
+// The PNG decoder (png_decoder.cpp), cut where the device decoder (csrc/png_decode.hip) takes over: the chunks, then the
+// inflate, then the reconstruction.  decode_png is the three in a row; `exif` receives the last eXIf chunk's bytes.
+struct PngSpan {
+    size_t offset = 0, nbytes = 0;   // inside the file
+};
+struct PngFrame {
+    uint32_t width = 0, height = 0;
+    int depth = 0, ctype = 0, interlace = 0;
+    std::vector<uint8_t> plte;                 // the last PLTE chunk's bytes
+    size_t exif_offset = 0, exif_nbytes = 0;   // the last eXIf chunk's body (0, 0: none)
+    std::vector<PngSpan> idat;                 // the IDAT bodies, in file order
+    size_t bits_pp = 0, bpp = 0;               // bits per pixel; the filters' byte distance
+    size_t total = 0;                          // bytes of the filtered stream: (stride + 1) * ph of every pass
+    me_pngdec::Geom geom;                         // the same and, per pass, x0, y0, dx, dy, pw, ph, stride and its offset
+};
+// every refusal of decode_png that needs no inflating, in its words and order
+PngFrame parse_png_header(const std::vector<uint8_t>& file, const std::string& path);
+// The IDAT data inflated (zlib's streaming inflate) into dst[frame.total]: the filtered stream, filter byte plus row, pass
+// after pass.  A stream that ends short, runs long, fails its Adler-32 or is damaged throws "PNG data does not inflate to
+// the image size"; bytes behind the stream's end inside IDAT are ignored.  band_cb (optional) is called with the number
+// of stream bytes complete so far, every few hundred KiB: a caller can start work on the rows that are finished.
+using PngBandCallback = void (*)(void* user, size_t complete);
+void inflate_png(const PngFrame& frame, const std::vector<uint8_t>& file, const std::string& path, uint8_t* dst,
+                 PngBandCallback band_cb = nullptr, void* band_user = nullptr);
+RgbImage decode_png(const std::vector<uint8_t>& file, const std::string& path, std::vector<uint8_t>* exif);
 
 // The JPEG decoder up to and including the entropy-coded segments (every scan type, restart intervals, interleaved or
 // not): the frame and its quantised DCT coefficients, before any reconstruction.  decode_jpeg is this plus the

@@ -75,6 +75,7 @@ Device::Device() {
     device_resampler_ = env_host_or_device("MATRIX_EYES_RESAMPLER", true);
     device_png_encoder_ = env_host_or_device("MATRIX_EYES_PNG_ENCODER", false);
     device_jpeg_decoder_ = env_host_or_device("MATRIX_EYES_JPEG_DECODER", false);
+    device_png_decoder_ = env_host_or_device("MATRIX_EYES_PNG_DECODER", false);
     device_jpeg_encoder_ = env_host_or_device("MATRIX_EYES_JPEG_ENCODER", false);
     try {  // MATRIX_EYES_JPEG_QUALITY, MATRIX_EYES_JPEG_SUBSAMPLING: refused here, not at the first ".jpg" written
         jpeg_params_ = jpeg_output_params();
@@ -124,21 +125,30 @@ RgbImage Device::resize_exact_lanczos3(const RgbImage& img, uint32_t width, uint
     return out;
 }
 
-bool Device::load_jpeg_resized(const std::string& path, bool with_orientation, uint32_t width, uint32_t height, RgbImage* out,
-                               ImageMetadata* metadata, uint32_t* original_width, uint32_t* original_height) const {
-    if (!device_jpeg_decoder_ || !(ends_with_ci(path, ".jpg") || ends_with_ci(path, ".jpeg"))) return false;
+bool Device::load_decoded_resized(const std::string& path, bool with_orientation, uint32_t width, uint32_t height, RgbImage* out,
+                                  ImageMetadata* metadata, uint32_t* original_width, uint32_t* original_height) const {
+    const bool jpeg_name = ends_with_ci(path, ".jpg") || ends_with_ci(path, ".jpeg"), png_name = ends_with_ci(path, ".png");
+    if (!(device_jpeg_decoder_ && jpeg_name) && !(device_png_decoder_ && png_name)) return false;
     std::ifstream f(path, std::ios::binary);
     if (!f) throw ImageError("cannot open " + path);
     const std::vector<uint8_t> file((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-    if (!(file.size() >= 3 && file[0] == 0xff && file[1] == 0xd8 && file[2] == 0xff)) return false;  // load_image goes by the signature
-    // the library says "<jpeg>: ..." where the host decoder says "<path>: ..."
+    // load_image goes by the signature
+    static const uint8_t kPngSig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+    const bool png = file.size() >= 8 && !std::memcmp(file.data(), kPngSig, 8);
+    const bool jpeg = !png && file.size() >= 3 && file[0] == 0xff && file[1] == 0xd8 && file[2] == 0xff;
+    if (!(jpeg && jpeg_name) && !(png && png_name)) return false;
+    // the library says "<jpeg>: ..." / "<png>: ..." where the host decoder says "<path>: ..."
+    const std::string tag = png ? "<png>" : "<jpeg>";
     auto refuse = [&](const char* message) {
         const std::string m = message ? message : "";
-        throw ImageError(m.rfind("<jpeg>", 0) == 0 ? path + m.substr(6) : m);
+        throw ImageError(m.rfind(tag, 0) == 0 ? path + m.substr(tag.size()) : m);
     };
+    const auto info = png ? me_png_info : me_jpeg_info;
+    const auto decode = png ? me_png_decode_rgb8 : me_jpeg_decode_rgb8;
+    const auto decode_resized = png ? me_png_decode_resized_rgb8 : me_jpeg_decode_resized_rgb8;
     int32_t w = 0, h = 0;
     int64_t exif_offset = 0, exif_nbytes = 0;
-    if (me_jpeg_info(file.data(), (int64_t)file.size(), &w, &h, &exif_offset, &exif_nbytes) != ME_OK) refuse(me_last_error(nullptr));
+    if (info(file.data(), (int64_t)file.size(), &w, &h, &exif_offset, &exif_nbytes) != ME_OK) refuse(me_last_error(nullptr));
     const ImageMetadata meta = parse_exif(std::vector<uint8_t>(file.begin() + exif_offset, file.begin() + exif_offset + exif_nbytes));
     if (metadata) *metadata = meta;
     // apply_orientation leaves the picture alone for a value outside 2..8
@@ -148,13 +158,13 @@ bool Device::load_jpeg_resized(const std::string& path, bool with_orientation, u
     if (original_height) *original_height = oh;
     if (device_resampler_) {  // decode, orientation and resize chained on the GPU: only the resized picture comes back
         *out = RgbImage(width, height);
-        const int32_t rc = me_jpeg_decode_resized_rgb8(ctx_, file.data(), (int64_t)file.size(), orientation, out->data.data(),
-                                                       (int32_t)width, (int32_t)height);
+        const int32_t rc = decode_resized(ctx_, file.data(), (int64_t)file.size(), orientation, out->data.data(), (int32_t)width,
+                                          (int32_t)height);
         if (rc != ME_OK) refuse(me_last_error(ctx_));
         return true;
     }
     RgbImage full(ow, oh);
-    const int32_t rc = me_jpeg_decode_rgb8(ctx_, file.data(), (int64_t)file.size(), orientation, full.data.data(), (int32_t)ow, (int32_t)oh);
+    const int32_t rc = decode(ctx_, file.data(), (int64_t)file.size(), orientation, full.data.data(), (int32_t)ow, (int32_t)oh);
     if (rc != ME_OK) refuse(me_last_error(ctx_));
     *out = matrix_eyes::resize_exact_lanczos3(full, width, height);
     return true;
@@ -279,8 +289,8 @@ void DepthMap::output_mesh(const std::string& destination_path, const std::strin
     if (mode == VertexMode::Color) {  // output.rs:206-218
         try {
             RgbImage resized;  // the source as decoded (no orientation), resized to the depth map
-            if (!device_.load_jpeg_resized(source_path, false, (uint32_t)data_width_, (uint32_t)data_height_, &resized, nullptr, nullptr,
-                                           nullptr))
+            if (!device_.load_decoded_resized(source_path, false, (uint32_t)data_width_, (uint32_t)data_height_, &resized, nullptr,
+                                              nullptr, nullptr))
                 resized = device_.resize_exact_lanczos3(load_image(source_path), (uint32_t)data_width_, (uint32_t)data_height_);
             colors = std::move(resized.data);
         } catch (const ImageError& err) {
@@ -327,9 +337,9 @@ SourceImage SourceImage::load_with(const Device* device, const std::string& path
     RgbImage img;
     ImageMetadata meta;
     try {
-        // a JPEG photo with MATRIX_EYES_JPEG_DECODER=device: reconstruction, orientation (:104-106) and the resize (:107-113) on the GPU
+        // a JPEG / PNG photo with MATRIX_EYES_JPEG_DECODER / _PNG_DECODER=device: reconstruction, orientation (:104-106) and the resize (:107-113) on the GPU
         uint32_t ow = 0, oh = 0;
-        if (device && device->load_jpeg_resized(path, true, (uint32_t)size, (uint32_t)size, &s.img, &meta, &ow, &oh)) {
+        if (device && device->load_decoded_resized(path, true, (uint32_t)size, (uint32_t)size, &s.img, &meta, &ow, &oh)) {
             s.focal_length_35mm = focal_length_35mm;
             if (!s.focal_length_35mm && meta.focal_length_35mm) s.focal_length_35mm = (float)*meta.focal_length_35mm;
             s.original_width = ow, s.original_height = oh;

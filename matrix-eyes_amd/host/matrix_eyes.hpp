@@ -76,10 +76,17 @@ public:
     // the full-size picture never exists on the host); "host" (the default) is jpeg_decoder.cpp.  Both write the same
     // bytes; any other value fails the constructor.
     bool device_jpeg_decoder() const { return device_jpeg_decoder_; }
+    // ImageReader::open(..).decode() of a PNG photo or vertex-colour source (reconstruction.rs:95-106, output.rs:206-218):
+    // with MATRIX_EYES_PNG_DECODER=device zlib's inflate stays on the host and the scanline filters, the conversion to RGB,
+    // the de-interlacing and the orientation run on the GPU (me_png_decode_rgb8), chained there with the resize when the
+    // device resampler is on (me_png_decode_resized_rgb8); "host" (the default) is png_decoder.cpp.  Both write the same
+    // bytes; any other value fails the constructor.
+    bool device_png_decoder() const { return device_png_decoder_; }
     // load_image + (with_orientation: apply_orientation with the file's EXIF value) + resize_exact_lanczos3(width, height)
-    // of a ".jpg" / ".jpeg" file through the device decoder.  False (nothing done) when the decoder is "host" or the file
-    // is not a JPEG by name and signature: the caller takes the host path.  original_*: the oriented size before the resize.
-    bool load_jpeg_resized(const std::string& path, bool with_orientation, uint32_t width, uint32_t height, RgbImage* out,
+    // of a ".jpg" / ".jpeg" or ".png" file through its device decoder.  False (nothing done) when that decoder is "host" or
+    // the file is not of the format by name and signature: the caller takes the host path.  original_*: the oriented size
+    // before the resize.
+    bool load_decoded_resized(const std::string& path, bool with_orientation, uint32_t width, uint32_t height, RgbImage* out,
                            ImageMetadata* metadata, uint32_t* original_width, uint32_t* original_height) const;
 
 private:
@@ -90,6 +97,7 @@ private:
     bool device_jpeg_encoder_ = false;
     JpegOutputParams jpeg_params_;
     bool device_jpeg_decoder_ = false;
+    bool device_png_decoder_ = false;
     mutable bool weights_loaded_ = false;
     friend class DepthProModelLoader;
 };

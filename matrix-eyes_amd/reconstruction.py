@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from .depth_pro import IMG_SIZE, DepthProModelLoader, resolve_jpeg_decoder, resolve_jpeg_entropy, resolve_resampler
+from .depth_pro import IMG_SIZE, DepthProModelLoader, resolve_jpeg_decoder, resolve_jpeg_entropy, resolve_png_decoder, resolve_resampler
 from .output import DepthMap, ImageOutputFormat, VertexMode
 
 _EXIF_IFD = 0x8769
@@ -31,18 +31,21 @@ class SourceImage:                          # reconstruction.rs:74-81
 
     @staticmethod
     def load(path: str, focal_length_35mm: Optional[float] = None, size: int = IMG_SIZE, resampler=None,
-             ctx=None, jpeg_decoder=None, jpeg_entropy=None) -> "SourceImage":
+             ctx=None, jpeg_decoder=None, jpeg_entropy=None, png_decoder=None) -> "SourceImage":
         """reconstruction.rs:87-131: decode, EXIF focal length, orientation, Lanczos3 to size x size.
         resampler: depth_pro.resolve_resampler; "device" resizes on `ctx` (a Context, or a callable that returns one
         and is only called once the file has been decoded).  jpeg_decoder: depth_pro.resolve_jpeg_decoder; "device"
         decodes a .jpg / .jpeg source on `ctx` (Pillow still reads the EXIF block), chained with the resize when the
         resampler is "device" too; jpeg_entropy: depth_pro.resolve_jpeg_entropy, where that decoder runs the Huffman
-        decoding."""
+        decoding.  png_decoder: depth_pro.resolve_png_decoder; "device" does the same for a .png source
+        (me_png_decode_rgb8 / me_png_decode_resized_rgb8; Pillow reads the eXIf chunk)."""
         from PIL import Image, ImageOps
         resampler = resolve_resampler(resampler)
         jpeg_entropy = resolve_jpeg_entropy(jpeg_entropy)
         if resolve_jpeg_decoder(jpeg_decoder) == "device" and path.lower().endswith((".jpg", ".jpeg")):
-            return SourceImage._load_jpeg_on_device(path, focal_length_35mm, size, resampler, ctx, jpeg_entropy)
+            return SourceImage._load_on_device("jpeg", path, focal_length_35mm, size, resampler, ctx, jpeg_entropy)
+        if resolve_png_decoder(png_decoder) == "device" and path.lower().endswith(".png"):
+            return SourceImage._load_on_device("png", path, focal_length_35mm, size, resampler, ctx)
         try:
             img = Image.open(path)
             img.load()
@@ -65,17 +68,21 @@ class SourceImage:                          # reconstruction.rs:74-81
                            focal_length_35mm)
 
     @staticmethod
-    def _load_jpeg_on_device(path, focal_length_35mm, size, resampler, ctx, jpeg_entropy="host") -> "SourceImage":
+    def _load_on_device(kind, path, focal_length_35mm, size, resampler, ctx, jpeg_entropy="host") -> "SourceImage":
+        """kind "jpeg" or "png": the file decoded, oriented and (device resampler) resized on `ctx`"""
         import io
         from PIL import Image
         if ctx is None:
-            raise ReconstructionError("Failed to load source image: the device JPEG decoder needs a context")
+            raise ReconstructionError(f"Failed to load source image: the device {kind.upper()} decoder needs a context")
         try:
             with open(path, "rb") as f:
                 data = f.read()
             ctx = ctx() if callable(ctx) else ctx
-            ctx.set_jpeg_entropy(jpeg_entropy)
-            width, height, _, _ = ctx.jpeg_info(data)
+            if kind == "jpeg":
+                ctx.set_jpeg_entropy(jpeg_entropy)
+            info, decode, decode_resized = ((ctx.jpeg_info, ctx.decode_jpeg, ctx.decode_jpeg_resized) if kind == "jpeg" else
+                                            (ctx.png_info, ctx.decode_png, ctx.decode_png_resized))
+            width, height, _, _ = info(data)
             orientation = 1
             try:                                  # header only: Pillow parses the EXIF block, not the scans
                 head = Image.open(io.BytesIO(data))
@@ -88,9 +95,9 @@ class SourceImage:                          # reconstruction.rs:74-81
                 orientation = 1
             original_size = (height, width) if orientation >= 5 else (width, height)
             if resampler == "device":
-                rgb = ctx.decode_jpeg_resized(data, (size, size), orientation)      # :95-113 in one call
+                rgb = decode_resized(data, (size, size), orientation)               # :95-113 in one call
             else:
-                img = Image.fromarray(ctx.decode_jpeg(data, orientation))
+                img = Image.fromarray(decode(data, orientation))
                 if img.size != (size, size):
                     img = img.resize((size, size), Image.LANCZOS)
                 rgb = np.ascontiguousarray(np.asarray(img, dtype=np.uint8))
@@ -122,18 +129,19 @@ class SourceImage:                          # reconstruction.rs:74-81
 def extract_depth(device: int, model_loader: DepthProModelLoader, source_path: str, destination_path: str,
                   focal_length_35mm: Optional[float], image_format: ImageOutputFormat,
                   vertex_mode: VertexMode, progress=None, noise=None, resampler=None, jpeg_decoder=None,
-                  jpeg_entropy=None) -> None:
+                  jpeg_entropy=None, png_decoder=None) -> None:
     """reconstruction.rs:155-205.  resampler: depth_pro.resolve_resampler, passed down to every resize; jpeg_decoder:
     depth_pro.resolve_jpeg_decoder, for the source photo, and jpeg_entropy: depth_pro.resolve_jpeg_entropy, for its
-    Huffman decoding"""
+    Huffman decoding; png_decoder: depth_pro.resolve_png_decoder, for a .png source photo"""
     resampler = resolve_resampler(resampler)
+    png_decoder = resolve_png_decoder(png_decoder)
     jpeg_decoder = resolve_jpeg_decoder(jpeg_decoder)
     jpeg_entropy = resolve_jpeg_entropy(jpeg_entropy)
     dtype = os.environ.get("MATRIX_EYES_DTYPE", "f16")   # f16 | bf16 | fp8, as the C++ twin
     try:
         img = SourceImage.load(source_path, focal_length_35mm, model_loader.cfg.img_size, resampler=resampler,
                                ctx=lambda: model_loader.context(device, dtype), jpeg_decoder=jpeg_decoder,
-                               jpeg_entropy=jpeg_entropy)
+                               jpeg_entropy=jpeg_entropy, png_decoder=png_decoder)
     except ReconstructionError as err:
         print(err, file=sys.stderr)
         raise
