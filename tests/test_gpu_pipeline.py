@@ -649,7 +649,9 @@ def test_composed_head_equals_the_three_layers(tmp_path):
     the three launches it replaces (ME_HEAD_COMPOSED=0), tiny model, a batch of two, with a deliberately large ConvTranspose
     bias: the maps agree to the 16-bit rounding the composed form SKIPS (the ConvTranspose output is no longer rounded to an
     operand), on the one-pixel frame -- where taps of the 3x3 convolution fall into its zero padding and the composed bias
-    changes -- as well as inside.  (test_extract_depth_tiny / the full-size pairs hold the composed form to the fp32 oracle.)"""
+    changes -- as well as inside.  (test_extract_depth_tiny / the full-size pairs hold the composed form to the fp32 oracle.)
+    tests/test_gpu_exact.py holds both routes EQUAL to the oracle, hence to each other, on checkpoints of small integers, where
+    the skipped rounding changes nothing and a wrong border share is a whole-integer difference."""
     _composed_head_against_the_three_layers(tmp_path, [])
 
 
@@ -713,7 +715,10 @@ def test_composed_features_equal_the_two_layers(tmp_path):
     unit's last convolution writes that input as the zero-bordered 16-bit operand, GemmParams::tap_bias corrects the bias on the
     frame) against the two launches (ME_FEAT_COMPOSED=0): tiny model, a batch of two, a deliberately large out_conv bias.  The
     maps agree to the operand roundings that differ (the feature map is no longer rounded to 16 bits, its pre-image and the composed
-    weights are), on the one-pixel frame of the half-resolution map -- two pixels of the depth map -- as well as inside."""
+    weights are), on the one-pixel frame of the half-resolution map -- two pixels of the depth map -- as well as inside.
+    tests/test_gpu_exact.py holds both routes EQUAL to the oracle, hence to each other, through extract_depth(f_norm = 1) -- the
+    only entry that runs this composition -- on checkpoints of small integers, where the roundings that differ change nothing
+    and a wrong tap_bias share is a whole-integer difference."""
     import os
     import subprocess
     import sys
