@@ -260,7 +260,13 @@ int32_t me_depth_clamp_minmax_async(me_ctx* ctx, float* depth, int64_t count, fl
 
 /* output.rs:141-193 output_stereogram.  depth [rows,cols] already clamped (DepthMap.data);
    noise [out_h,out_w,3] is the reference's per-row rand stream made an input;
-   out [out_h,out_w,3].  Bit-exact with the reference's f32 arithmetic. */
+   out [out_h,out_w,3].  Bit-exact with the reference's f32 arithmetic.  rows >= cols is required: the
+   reference's sampler reads data[cols * y + x] with x < rows, y < cols (output.rs:79), which leaves a map with
+   more columns than rows and panics, so such a map is ME_ERR_BAD_SHAPE here, as are out_w > 16384 and a
+   non-positive size (this holds for every stereogram entry below; nothing is written and no file is created).
+   A caller-supplied [min_depth, max_depth] narrower than the data must still make every source index
+   x + shift - pattern_width land inside the row: the reference panics where it reaches out_w, this library
+   clamps it to out_w - 1 silently. */
 int32_t me_stereogram(me_ctx* ctx, const float* depth, int32_t rows, int32_t cols, float min_depth,
                       float max_depth, int32_t out_w, int32_t out_h, float amplitude,
                       const uint8_t* noise, uint8_t* out);

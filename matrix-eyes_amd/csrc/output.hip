@@ -429,6 +429,12 @@ void stereogram_launch(const float* depth, int32_t rows, int32_t cols, float min
     ME_CHECK(out_w > 0 && out_h > 0 && rows > 0 && cols > 0, ME_ERR_BAD_SHAPE,
              "stereogram: %dx%d from %dx%d", out_w, out_h, rows, cols);
     ME_CHECK(out_w <= 16384, ME_ERR_BAD_SHAPE, "stereogram: width %d > 16384", out_w);
+    // interpolate_point reads data[cols * y + x] with x <= rows - 1, y <= cols - 1 (quirk Q3): up to index
+    // cols * (cols - 1) + rows - 1, which lies inside the rows * cols map only for cols <= rows
+    ME_CHECK(cols <= rows, ME_ERR_BAD_SHAPE,
+             "stereogram: a %dx%d depth map (rows x cols) has more columns than rows: the reference's sampler indexes "
+             "data[cols * y + x] past the end of such a map and panics (output.rs:79); rows >= cols is required",
+             rows, cols);
     int rounds = 1;
     while ((1 << rounds) < out_w) ++rounds;
     const size_t lds = (size_t)out_w * 2 * sizeof(int);

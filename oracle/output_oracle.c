@@ -48,10 +48,19 @@ void oracle_clamp_minmax(float* data, int64_t n, float* min_out, float* max_out)
 typedef struct {
     const float* data;
     uint64_t data_width, data_height; /* = dims()[0], dims()[1]  (:52) */
+    uint64_t len;                     /* elements of data: the slice bound Rust checks */
+    int* out_of_range;                /* set where the reference's slice index panics */
 } DepthMap;
 
-static float depth_value(const DepthMap* m, uint64_t x, uint64_t y) { /* :78-80 */
-    return m->data[m->data_height * y + x];
+/* :78-80.  data_width = rows but the stride is data_height = cols, so for cols > rows the index
+   can pass the end of the map: Rust panics there; here the flag is raised and 0 stands in for the value. */
+static float depth_value(const DepthMap* m, uint64_t x, uint64_t y) {
+    const uint64_t i = m->data_height * y + x;
+    if (i >= m->len) {
+        *m->out_of_range = 1;
+        return 0.0f;
+    }
+    return m->data[i];
 }
 
 static uint64_t clamp_u(uint64_t v, uint64_t lo, uint64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -70,11 +79,15 @@ static float interpolate_point(const DepthMap* m, float x, float y) { /* :83-98 
 }
 
 /* output.rs:141-193 output_stereogram; `noise` replaces rand::rng() (:163-171): one RGB triple per
-   pixel in raster order.  Returns -1 where the reference would panic on an out-of-range index. */
-int oracle_stereogram(const float* depth, int32_t rows, int32_t cols, float min_depth, float max_depth,
-                      int32_t output_width, int32_t output_height, float amplitude,
-                      const uint8_t* noise, uint8_t* out) {
-    const DepthMap m = {depth, (uint64_t)rows, (uint64_t)cols};
+   pixel in raster order.  Returns -1 where the reference would panic on an out-of-range index, of the depth map
+   (:79) or of the output row (:181).  forward (nullable): [0] the pixels with x >= pattern_width whose source index
+   is >= x -- they read the row's not yet overwritten noise -- and [1] those of them with index > x. */
+int oracle_stereogram_counted(const float* depth, int32_t rows, int32_t cols, float min_depth, float max_depth,
+                              int32_t output_width, int32_t output_height, float amplitude,
+                              const uint8_t* noise, uint8_t* out, int64_t* forward) {
+    int out_of_range = 0;
+    const DepthMap m = {depth, (uint64_t)rows, (uint64_t)cols, (uint64_t)rows * (uint64_t)cols, &out_of_range};
+    int64_t fwd = 0, fwd_strict = 0;
     const float depth_multiplier = (float)output_width * amplitude;               /* :160 */
     const uint64_t pattern_width = as_usize(roundf(depth_multiplier * 2.0f + amplitude)); /* :161 */
     uint8_t* output_row = (uint8_t*)malloc((size_t)output_width * 3);
@@ -84,6 +97,10 @@ int oracle_stereogram(const float* depth, int32_t rows, int32_t cols, float min_
         for (int32_t xi = 0; xi < output_width; ++xi) {
             float d = interpolate_point(&m, (float)xi / (float)output_width,
                                         (float)y / (float)output_height);         /* :174-177 */
+            if (out_of_range) {
+                free(output_row);
+                return -1;
+            }
             d = (d - min_depth) / (max_depth - min_depth);                        /* :178 */
             const uint64_t x = (uint64_t)xi;
             const uint8_t* src;
@@ -94,6 +111,7 @@ int oracle_stereogram(const float* depth, int32_t rows, int32_t cols, float min_
                     free(output_row);
                     return -1;
                 }
+                fwd += idx >= x, fwd_strict += idx > x;
                 src = output_row + idx * 3;
             } else {
                 src = noise_row + (x % pattern_width) * 3;                        /* :184 */
@@ -104,7 +122,15 @@ int oracle_stereogram(const float* depth, int32_t rows, int32_t cols, float min_
         memcpy(out + (size_t)y * output_width * 3, output_row, (size_t)output_width * 3); /* :187-189 */
     }
     free(output_row);
+    if (forward) forward[0] = fwd, forward[1] = fwd_strict;
     return 0;
+}
+
+int oracle_stereogram(const float* depth, int32_t rows, int32_t cols, float min_depth, float max_depth,
+                      int32_t output_width, int32_t output_height, float amplitude,
+                      const uint8_t* noise, uint8_t* out) {
+    return oracle_stereogram_counted(depth, rows, cols, min_depth, max_depth, output_width, output_height, amplitude,
+                                     noise, out, NULL);
 }
 
 static uint8_t map_color(int channel, float value) { /* :704-714 */

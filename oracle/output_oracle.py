@@ -25,6 +25,7 @@ def lib():
             build()
         _LIB = C.CDLL(path)
         _LIB.oracle_stereogram.restype = C.c_int
+        _LIB.oracle_stereogram_counted.restype = C.c_int
     return _LIB
 
 
@@ -50,6 +51,24 @@ def stereogram(depth, min_depth, max_depth, out_w, out_h, amplitude, noise):
     if rc != 0:
         raise IndexError("output_row index out of range (the reference panics here)")
     return out
+
+
+def stereogram_counted(depth, min_depth, max_depth, out_w, out_h, amplitude, noise):
+    """stereogram() without the exception -> (rc, out, forward, forward_strict): rc is -1 where the reference panics,
+    on the depth map's index (output.rs:79, a map with more columns than rows) or on the output row's (:181), and the
+    other three are then None; forward counts the pixels at x >= pattern_width whose source index is >= x,
+    forward_strict those whose index is > x."""
+    d = np.ascontiguousarray(depth, np.float32)
+    nz = np.ascontiguousarray(noise, np.uint8)
+    assert d.ndim == 2 and nz.shape == (out_h, out_w, 3)
+    out = np.empty((out_h, out_w, 3), np.uint8)
+    fwd = (C.c_int64 * 2)(0, 0)
+    rc = lib().oracle_stereogram_counted(_p(d), C.c_int32(d.shape[0]), C.c_int32(d.shape[1]), C.c_float(min_depth),
+                                         C.c_float(max_depth), C.c_int32(out_w), C.c_int32(out_h),
+                                         C.c_float(amplitude), _p(nz), _p(out), fwd)
+    if rc != 0:
+        return rc, None, None, None
+    return 0, out, int(fwd[0]), int(fwd[1])
 
 
 def depthmap_rgb(depth, min_depth, max_depth):

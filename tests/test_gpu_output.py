@@ -11,6 +11,7 @@ import pytest
 
 import matrix_eyes_amd as m
 from oracle import output_oracle as OO
+from output_cases import _depth
 from util import ctx_for
 
 pytestmark = pytest.mark.gpu
@@ -19,21 +20,6 @@ KA = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "output_kn
 
 def _ctx():
     return ctx_for("tiny", "f16")
-
-
-def _depth(n, seed=0, kind="scene"):
-    """inverse-depth-like maps: smooth background + a few nearer rectangles (discontinuities)"""
-    rng = np.random.default_rng(seed)
-    yy, xx = np.meshgrid(np.linspace(0, 1, n, dtype=np.float32), np.linspace(0, 1, n, dtype=np.float32),
-                         indexing="ij")
-    d = 0.2 + 0.15 * np.sin(3 * xx + 2 * yy) + 0.1 * yy
-    if kind == "scene":
-        for _ in range(6):
-            x0, y0 = rng.integers(0, n - n // 4, size=2)
-            w, h = rng.integers(n // 16, n // 4, size=2)
-            d[y0:y0 + h, x0:x0 + w] += rng.uniform(0.2, 1.5)
-        d += rng.normal(0, 0.002, size=d.shape).astype(np.float32)
-    return np.ascontiguousarray(d.astype(np.float32))
 
 
 def test_known_answers():
