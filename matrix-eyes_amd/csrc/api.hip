@@ -649,7 +649,7 @@ void extract_depth_impl(me_ctx* ctx, const float* img_dev, int32_t batch, const 
     // launches themselves get slower beside the ConvTranspose, and the forked region adds a failure mode to graph capture
     // (a CaptureAbort between fork and join leaves the side stream attached to the aborted capture until EndCapture returns
     // Unjoined).  ME_OVERLAP_TAIL=1 switches it on for the A/B.
-    static const bool overlap_env = getenv("ME_OVERLAP_TAIL") && atoi(getenv("ME_OVERLAP_TAIL")) != 0;
+    static const bool overlap_env = env_flag("ME_OVERLAP_TAIL");
     const bool overlap = overlap_env && ctx->overlap_tail && ctx->side_stream && !ctx->progress && !profiler().enabled;
     OutBuf ofov;
     if (overlap) {
@@ -671,7 +671,7 @@ void extract_depth_impl(me_ctx* ctx, const float* img_dev, int32_t batch, const 
         stage_decoder_levels(ctx, batch, false, 3, 2);
         ME_HIP(hipEventRecord(ctx->ev_join, ctx->side_stream));
         ctx->stream = main_stream;
-        static const int cap = getenv("ME_OVERLAP_CAP") ? atoi(getenv("ME_OVERLAP_CAP")) : 128;
+        static const int cap = env_int("ME_OVERLAP_CAP", 128);
         ctx->grid_cap = cap;
         stage_encoder_latents(ctx, batch);
         ctx->grid_cap = 0;

@@ -1133,9 +1133,9 @@ void attention_launch(const void* qkv, void* out, int32_t windows, int32_t token
     // workgroups per (window, head), persistent, the 577th query on the vector pipe) instead of attention2_kernel.  Measured
     // equal stand-alone and slower in the step (profiles/r05_attention_recut_ab.txt), so attention2_kernel stays the forward
     // pass's kernel.
-    const char* av = getenv("ME_ATT_V");
-    const bool use_v2 = !(av && atoi(av) == 3);
-    const bool use_pipe = av && atoi(av) == 4;  // attention2p_kernel: the next tile's score MFMAs in front of this tile's softmax
+    const int av = env_int("ME_ATT_V", 0);
+    const bool use_v2 = av != 3;
+    const bool use_pipe = av == 4;  // attention2p_kernel: the next tile's score MFMAs in front of this tile's softmax
     ProfScope prof(stream, !q_prescaled ? "attention_kernel" : (use_v2 ? "attention2_kernel" : "attention3_kernel"),
                    4.0 * windows * heads * (double)tokens * tokens * 64,
                    (double)windows * tokens * heads * 64 * (out8 ? 7.03 : 8.0));  // q, k, v read once + the output
@@ -1153,8 +1153,7 @@ void attention_launch(const void* qkv, void* out, int32_t windows, int32_t token
         if (use_pipe) {
             const int nqb_p = (tokens + 127) / 128;
             const dim3 grid_p(8 * nqb_p * ((windows * heads + 7) / 8));
-            const char* mw = getenv("ME_ATT_MINW");  // (development: 2 = 200 registers, no scratch; default 3 = 168 registers, 16 bytes of scratch)
-            const bool two = mw && atoi(mw) == 2;
+            const bool two = env_int("ME_ATT_MINW", 3) == 2;  // (development: 2 = 200 registers, no scratch; default 3 = 168 registers, 16 bytes of scratch)
 #define ME_ATT2P(T, MW)                                                                                                     \
     hipLaunchKernelGGL((attention2p_kernel<T, MW>), grid_p, dim3(256), 0, stream, (const T*)qkv, (T*)out, tokens, heads, \
                        windows * heads, segs, out8, out8_scale, out8_mt, defer_thr)
@@ -1175,8 +1174,7 @@ void attention_launch(const void* qkv, void* out, int32_t windows, int32_t token
         // three waves per SIMD with the leaner tile against four with the vector-pipe row sums).  ONE form runs at every
         // size -- their row sums round differently, and a batch must equal a loop of batch-one calls bit for bit;
         // ME_ATT_HALVES=1 (development) selects the other.
-        const char* hv = getenv("ME_ATT_HALVES");
-        const bool halves = hv && atoi(hv) != 0;
+        const bool halves = env_flag("ME_ATT_HALVES");
 #define ME_ATT2(T)                                                                                                          \
     do {                                                                                                                    \
         if (halves)                                                                                                         \

@@ -21,6 +21,7 @@
 // LDS images: K rows of 128 bytes, 16-byte chunk c at slot c ^ ((row >> 1) & 7) (a fragment read's sixteen rows spread over all
 // eight slots); V rows with their 32-byte columns at column ^ (row & 3) (a transposed read's four rows touch every bank once).
 #include "attention_shared.h"
+#include "launch.h"
 
 namespace me {
 
@@ -549,24 +550,11 @@ void attention3_launch(const void* qkv, void* out, int32_t windows, int32_t toke
     // persistent grid: the workgroups that are resident at once (a multiple of 8: workgroup b stays on XCD b % 8), no more than
     // there are items.  ME_ATT_GRID (development): another grid, e.g. n_main = one workgroup per item.
     static PerDeviceOnce once_f16, once_bf16;
-    auto resident = [&](PerDeviceOnce& once, const void* kern) {
-        return per_device_once(once, [&](int dev) {
-            int per_cu = 0, cus = 0;
-            ME_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0));
-            ME_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-            int r = (per_cu < 1 ? 1 : per_cu) * cus;
-            r -= r % 8;
-            return r < 8 ? 8 : r;
-        });
-    };
-    int grid_n = dtype == ME_DTYPE_F16 ? resident(once_f16, (const void*)attention3_kernel<f16>)
-                                       : resident(once_bf16, (const void*)attention3_kernel<bf16>);
-    if (const char* gv = getenv("ME_ATT_GRID")) {
-        const int v = atoi(gv);
-        if (v >= 8) grid_n = v - v % 8;
-    }
-    if (grid_n > n_main) grid_n = n_main;
-    const dim3 grid(grid_n);
+    int resident = dtype == ME_DTYPE_F16 ? kernel_resident(once_f16, (const void*)attention3_kernel<f16>, 256, 0)
+                                         : kernel_resident(once_bf16, (const void*)attention3_kernel<bf16>, 256, 0);
+    const int v = env_int("ME_ATT_GRID", 0);
+    if (v >= 8) resident = v - v % 8;
+    const dim3 grid((unsigned)persistent_grid(n_main, resident, 0, 0, 0));
     if (dtype == ME_DTYPE_F16)
         hipLaunchKernelGGL((attention3_kernel<f16>), grid, dim3(256), 0, stream, (const f16*)qkv, (f16*)out, tokens, heads, ngroups, segs,
                            out8, out8_scale, out8_mt, defer_thr, nqb, nunits, n_main, n_extra);

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <atomic>
 #include <string>
 #include <vector>
@@ -49,6 +50,12 @@ struct Error {
     } while (0)
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Environment knobs: a switch that is on unless NAME=0, one that is off unless NAME is a non-zero number, a
+// number with a default.  Whether a knob is read once per process (`static const` at the site) or per call is the site's choice.
+static inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+static inline bool env_on(const char* name) { return env_int(name, 1) != 0; }
+static inline bool env_flag(const char* name) { return env_int(name, 0) != 0; }
 
 // Per-kernel launch configuration that must be set up once PER DEVICE (dynamic-LDS attribute, resident
 // workgroup count): contexts may live on several devices, and on several host threads, of one process.
@@ -315,6 +322,10 @@ int stream_cu_count(hipStream_t stream);
 // the CUs `stream` may use; a launch with N columns needs 8 * N / 256 of them (one row tile per XCD with all its column
 // tiles: they wait for one another)
 int gemm_lnf_resident(int32_t dtype, hipStream_t stream);
+int gemm_fp8_lnf_resident(hipStream_t stream);  // ... of the kernel an fp8 proj / fc2 carries it in (gemm_fp8.hip gemm_pp8t_kernel<.., LNF>)
+// test knobs of the two-group launchers, read once per process (gemm.hip): ME_GEMM_GRID_LIMIT (0: none), ME_LN_SPIN_LIMIT (0: the kernel's bound)
+int gemm_grid_limit();
+int gemm_ln_spin_limit();
 void head_final_halo_launch(const GemmParams& p, int32_t dtype, hipStream_t stream);
 
 // MX fp8 x fp8 (gemm_fp8.hip): EPI_STORE (f16 out16, or fp8 out8 + scales) / EPI_RESID_SCALE

@@ -73,10 +73,7 @@ const char* gemm_config_name(int cfg) { return cfg >= 0 && cfg < CFG_COUNT ? kCf
 // 5 rounds); proj / fc2 (N = 1024) -> 160x128: 1016 tiles = 2 rounds of 512, where 128x128 needs 3 and
 // 256x256 leaves 3/4 of the second round idle; the 256-channel convolutions at 768^2 and 384^2 -> 256x256.
 // The 64x64 tile is for the single-window ViTs (M = 577) and the low-resolution decoder levels.
-static bool dynamic_tile_order() {
-    static const bool on = getenv("ME_GEMM_DYNAMIC_TILES") != nullptr;
-    return on;
-}
+static bool dynamic_tile_order() { static const bool on = getenv("ME_GEMM_DYNAMIC_TILES") != nullptr; return on; }
 
 static int pick_config(int64_t M, int64_t N, int64_t K, int64_t seg1, int64_t seg2, bool resid) {
     const int64_t t1 = cdiv(M, 128) * cdiv(N, 128);
@@ -179,6 +176,17 @@ int stream_cu_count(hipStream_t stream) {
     return granted;
 }
 
+// ME_LOG_LAUNCH: one line per launch on stderr -- which shape a trace row is
+static bool log_launches() { static const bool on = getenv("ME_LOG_LAUNCH") != nullptr; return on; }
+// ME_GEMM_GRID_LIMIT, a diagnostic (tools/dual_stream_probe.py): cap the persistent grid of the two-group launchers (gemm_core.h
+// gemm_launch_pp, gemm_fp8.hip launch_pp8t) so that two launches on two streams share the chip instead of the first one taking
+// every CU until it ends.  On the fused LayerNorm launch a cap that is not a whole number of rounds' units puts column tiles of one
+// row tile into different rounds: the waits run into their bound and raise ME_STATUS_SYNC_TIMEOUT -- which is how
+// tests/test_gpu_pipeline.py forces the fallback path.
+int gemm_grid_limit() { static const int limit = env_int("ME_GEMM_GRID_LIMIT", 0); return limit; }
+// ME_LN_SPIN_LIMIT, the same test's other knob: the polls of GemmParams::ln_spin_limit
+int gemm_ln_spin_limit() { static const int spin = env_int("ME_LN_SPIN_LIMIT", 0); return spin > 0 ? spin : 0; }
+
 void head_composed_launch_f16(const GemmParams& p, hipStream_t stream);
 void head_composed_launch_bf16(const GemmParams& p, hipStream_t stream);
 
@@ -194,8 +202,7 @@ void head_composed_launch(const GemmParams& p_in, int32_t dtype, hipStream_t str
     ME_CHECK(head_composed_fits(p), ME_ERR_BAD_SHAPE, "composed head: %dx%d map, Cin %d, N %d", p.out_H, p.out_W, p.Cin, p.N);
     ME_CHECK(p.A && p.W && p.bias && p.tap_bias && p.w2 && p.b2 && p.out32 && p.pixels_per_image == 4 * p.out_H * p.out_W,
              ME_ERR_BAD_ARG, "composed head: missing operand");
-    static const bool log_launches = getenv("ME_LOG_LAUNCH") != nullptr;
-    if (log_launches) fprintf(stderr, "gemm_launch conv head_composed M=%d N=%d K=%d\n", p.M, p.N, p.K);
+    if (log_launches()) fprintf(stderr, "gemm_launch conv head_composed M=%d N=%d K=%d\n", p.M, p.N, p.K);
     // algorithmic FLOPs: every output phase reads a 2 x 2 window of the 3 x 3 one (4 of 9 taps carry weights): the dense launch
     // executes 9 / 4 of them; counted here are the FLOPs of the two layers it replaces at their own shapes (SURVEY App. B:
     // ConvTranspose 2 * H * W * Cin * Cin * 4 + conv3x3 2 * 4 H W * Cin * 32 * 9)
@@ -229,20 +236,14 @@ void gemm_launch(const GemmParams& p_in, AMode amode, EpiKind epi, int32_t dtype
     GemmParams p = p_in;
     p.resident_out = nullptr;
     p.cu_granted = stream_cu_count(stream);
-    {
-        static const int spin = getenv("ME_LN_SPIN_LIMIT") ? atoi(getenv("ME_LN_SPIN_LIMIT")) : 0;  // test knob
-        p.ln_spin_limit = spin > 0 ? spin : 0;
-    }
+    p.ln_spin_limit = gemm_ln_spin_limit();
     // Dynamic tile order (TileQueue in gemm_core.h) is an opt-in: measured on the full step it gains 0.4 %
     // (26.57 vs 26.68 ms) -- the launches the side streams disturb most (proj / fc2) have two tiles per
     // workgroup, too coarse for a late workgroup to hand work to its neighbours.
     p.queue = dynamic_tile_order() ? queue_for_stream(stream) : nullptr;
     p.status = current_status_word();
-    {
-        const char* gb = getenv("ME_GELU_BATCH");
-        p.gelu_per_granule = gb && atoi(gb) == 0;
-    }
-    static const int patch_rows = getenv("ME_GEMM_PATCH_ROWS") ? atoi(getenv("ME_GEMM_PATCH_ROWS")) : 0;  // A/B knob
+    p.gelu_per_granule = !env_on("ME_GELU_BATCH");  // (read per launch: the tests flip it inside one process)
+    static const int patch_rows = env_int("ME_GEMM_PATCH_ROWS", 0);  // A/B knob
     p.patch_rows = patch_rows;
     ME_CHECK(p.M > 0 && p.N > 0 && p.K > 0, ME_ERR_BAD_SHAPE, "gemm: empty problem %dx%dx%d", p.M,
              p.N, p.K);
@@ -283,14 +284,14 @@ void gemm_launch(const GemmParams& p_in, AMode amode, EpiKind epi, int32_t dtype
     int cfg = force_cfg >= 0 ? force_cfg : pick_config(p.M, p.N, p.K, p.seg1, p.seg2, amode == A_PLAIN && epi == EPI_RESID_SCALE);
     // 3x3 convolutions big enough for the 256x256 tile take its halo form (gemm_core.h conv_halo_kernel): the 18 x 18
     // halo of a 16 x 16 pixel tile staged once per 64 input channels instead of the pixels once per tap
-    static const bool halo_on = !(getenv("ME_CONV_HALO") && atoi(getenv("ME_CONV_HALO")) == 0);
+    static const bool halo_on = env_on("ME_CONV_HALO");
     const bool halo_fits = amode == A_CONV && epi == EPI_STORE && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.out_H % 16 == 0 &&
                            p.out_W % 16 == 0 && p.N % 256 == 0;
     if (force_cfg < 0 && halo_on && halo_fits && cfg == CFG_PP256) {
         cfg = CFG_HALO;
         // 12-row tiles where they fill the rounds better: a tile of 12 x 16 pixels costs about 0.78 of a 16 x 16 one
         // (three quarters of the MFMAs, the same weight staging per slab)
-        static const bool halo12_on = !(getenv("ME_CONV_HALO12") && atoi(getenv("ME_CONV_HALO12")) == 0);
+        static const bool halo12_on = env_on("ME_CONV_HALO12");
         if (halo12_on && p.out_H % 12 == 0) {
             const int64_t nbn = p.N / 256, t16 = (int64_t)(p.M / 256) * nbn, t12 = (int64_t)(p.M / 192) * nbn;
             if ((double)cdiv(t12, 256) * 0.78 < (double)cdiv(t16, 256) * 0.97) cfg = CFG_HALO12;
@@ -301,7 +302,7 @@ void gemm_launch(const GemmParams& p_in, AMode amode, EpiKind epi, int32_t dtype
     // 128x128 implicit-GEMM tile would have been chosen on a map of at least a round of pixel tiles
     const bool halo128_fits = amode == A_CONV && epi == EPI_STORE && p.KH == 3 && p.KW == 3 && p.stride == 1 &&
                               p.out_H % 16 == 0 && p.out_W % 16 == 0 && p.N % 128 == 0;
-    static const bool halo128_on = !(getenv("ME_CONV_HALO128") && atoi(getenv("ME_CONV_HALO128")) == 0);
+    static const bool halo128_on = env_on("ME_CONV_HALO128");
     if (force_cfg < 0 && halo_on && halo128_on && halo128_fits && p.N % 256 != 0 && cfg == CFG_128 &&
         (int64_t)(p.M / 256) * (p.N / 128) >= 256)
         cfg = CFG_HALO_N128;
@@ -322,10 +323,9 @@ void gemm_launch(const GemmParams& p_in, AMode amode, EpiKind epi, int32_t dtype
     static const char* kEpi[] = {"store", "resid_scale", "patch_embed", "?", "convt", "head_final"};
     // the head's final layers on a halo tile (head_conv.hip) where the shape is the model's own; force_cfg >= 0 or
     // ME_HEAD_HALO=0: the implicit-GEMM tile below
-    static const bool head_halo_on = !(getenv("ME_HEAD_HALO") && atoi(getenv("ME_HEAD_HALO")) == 0);
+    static const bool head_halo_on = env_on("ME_HEAD_HALO");
     const bool head_halo = epi == EPI_HEAD_FINAL && amode == A_CONV && force_cfg < 0 && head_halo_on && head_final_halo_fits(p);
-    static const bool log_launches = getenv("ME_LOG_LAUNCH") != nullptr;  // one line per launch: which shape a trace row is
-    if (log_launches)
+    if (log_launches())
         fprintf(stderr, "gemm_launch %s %s M=%d N=%d K=%d k=%dx%d/s%d cfg=%s res32=%d out32=%d out16=%d border=%d lo=%d hi2=%d ln=%d\n",
                 amode == A_PLAIN ? "plain" : "conv", kEpi[epi], p.M, p.N, p.K, p.KH, p.KW, p.stride, gemm_config_name(cfg),
                 p.res32 != nullptr, p.out32 != nullptr, p.out16 != nullptr, p.out16_border, (int)p.lo_off16, (int)p.hi2_off16,

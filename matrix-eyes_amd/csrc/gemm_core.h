@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "launch.h"
 #include "mx_fp8.h"
 
 namespace me {
@@ -2018,44 +2019,12 @@ void gemm_launch_pp(const GemmParams& p, hipStream_t stream) {
     ME_CHECK(p.K >= 128, ME_ERR_BAD_SHAPE, "gemm: the two-group kernel needs K >= 128 (K = %d)", p.K);
     auto kern = gemm_pp_kernel<T, BM, BN, WM, WN, AMODE, EPI, WSLOTS, LNF>;
     static PerDeviceOnce once;
-    // (workgroups per CU) << 12 | CUs of the device
-    const int occ = per_device_once(once, [&](int dev) {
-        ME_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        int per_cu = 0, cus = 0;
-        ME_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, 512, smem));
-        ME_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        return ((per_cu < 1 ? 1 : per_cu) << 12) | (cus < 1 ? 1 : (cus > 4095 ? 4095 : cus));
-    });
-    // resident workgroups: what fits on the CUs the launch stream may use (all of the device's unless it carries a CU mask)
-    int cus = occ & 4095;
-    if (p.cu_granted > 0 && p.cu_granted < cus) cus = p.cu_granted;
-    int resident = (occ >> 12) * cus;
-    resident -= resident % 8;
-    if (resident < 8) resident = 8;
-    if (p.resident_out) {
-        *p.resident_out = resident;
-        return;
-    }
     int64_t ntiles = (BM > 256 ? (int64_t)seg_row_tiles<BM>(p.M, p.seg1, p.seg2) : cdiv(p.M, BM)) * cdiv(p.N, BN);
     if (LNF) ntiles = cdiv((int64_t)seg_row_tiles<BM>(p.M, p.seg1, p.seg2), 8) * 8 * cdiv(p.N, BN);  // the kernel's padded walk
-    ME_CHECK(ntiles > 0 && ntiles < (1ll << 31), ME_ERR_BAD_SHAPE, "gemm grid %lld out of range",
-             (long long)ntiles);
-    int64_t grid = ntiles < resident ? ntiles : resident;
-    if (LNF) {
-        // a round is a whole number of row tiles per XCD, and every workgroup of it must be resident (they wait for one another)
-        const int64_t unit = 8 * cdiv(p.N, BN);
-        // (pipeline.hip ln_fusable asks gemm_lnf_resident first and takes the stand-alone LayerNorm otherwise)
-        ME_CHECK(resident >= unit, ME_ERR_HIP, "gemm: the fused LayerNorm needs %lld resident workgroups (%d fit)", (long long)unit, resident);
-        grid -= grid % unit;
-    }
-    // diagnostic (tools/dual_stream_probe.py): cap the persistent grid so that two launches on two streams share
-    // the chip instead of the first one taking every CU until it ends.  On the fused LayerNorm launch a cap that is not a
-    // whole number of rounds' units puts column tiles of one row tile into different rounds: the waits run into their
-    // bound and raise ME_STATUS_SYNC_TIMEOUT -- which is how tests/test_gpu_pipeline.py forces the fallback path.
-    static const int grid_limit = getenv("ME_GEMM_GRID_LIMIT") ? atoi(getenv("ME_GEMM_GRID_LIMIT")) : 0;
-    if (grid_limit >= 8 && grid > grid_limit) grid = grid_limit - grid_limit % 8;
-    if (!LNF && p.grid_cap >= 8 && grid > p.grid_cap) grid = p.grid_cap - p.grid_cap % 8;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, stream, p);
+    const unsigned grid = persistent_launch_grid(once, (const void*)kern, 512, smem, ntiles, "gemm", p.cu_granted, p.resident_out,
+                                                 LNF ? 8 * cdiv(p.N, BN) : 0, gemm_grid_limit(), p.grid_cap);
+    if (!grid) return;  // the query form
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, stream, p);
     ME_HIP(hipGetLastError());
 }
 
@@ -2064,24 +2033,13 @@ void gemm_launch_cfg(const GemmParams& p, hipStream_t stream) {
     constexpr int smem = 2 * (BM + BN) * 128;
     auto kern = gemm_kernel<T, BM, BN, WM, WN, AMODE, EPI, SPLITK>;
     static PerDeviceOnce once;  // workgroups that fit on the chip at once (per instantiation and device)
-    const int resident = per_device_once(once, [&](int dev) {
-        ME_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        int per_cu = 0, cus = 0;
-        ME_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, WM * WN * 64, smem));
-        ME_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        int r = (per_cu < 1 ? 1 : per_cu) * cus;
-        r -= r % 8;  // whole XCD rounds: workgroup b always lands on XCD b % 8
-        return r < 8 ? 8 : r;
-    });
     int64_t ntiles = cdiv(p.M, BM) * cdiv(p.N, BN);
     if constexpr (SPLITK) {
         ME_CHECK(p.split_k > 1 && p.split_k <= p.K / 64 && p.splitk_ws && p.splitk_cnt, ME_ERR_BAD_ARG, "gemm: split-K %d of K = %d", p.split_k, p.K);
         ntiles *= p.split_k;
     }
-    ME_CHECK(ntiles > 0 && ntiles < (1ll << 31), ME_ERR_BAD_SHAPE, "gemm grid %lld out of range",
-             (long long)ntiles);
-    const int64_t grid = ntiles < resident ? ntiles : resident;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WM * WN * 64), smem, stream, p);
+    const unsigned grid = persistent_launch_grid(once, (const void*)kern, WM * WN * 64, smem, ntiles, "gemm");
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(WM * WN * 64), smem, stream, p);
     ME_HIP(hipGetLastError());
 }
 
@@ -2279,19 +2237,8 @@ void gemm_launch_8ph(const GemmParams& p, hipStream_t stream) {
     ME_CHECK(p.K >= 128, ME_ERR_BAD_SHAPE, "gemm: the 8-phase kernel needs K >= 128 (K = %d)", p.K);
     auto kern = gemm_8ph_kernel<T, EPI>;
     static PerDeviceOnce once;
-    const int resident = per_device_once(once, [&](int dev) {
-        ME_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        int per_cu = 0, cus = 0;
-        ME_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, 512, smem));
-        ME_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        int r = (per_cu < 1 ? 1 : per_cu) * cus;
-        r -= r % 8;
-        return r < 8 ? 8 : r;
-    });
-    const int64_t ntiles = cdiv(p.M, 256) * cdiv(p.N, 256);
-    ME_CHECK(ntiles > 0 && ntiles < (1ll << 31), ME_ERR_BAD_SHAPE, "gemm grid %lld out of range", (long long)ntiles);
-    const int64_t grid = ntiles < resident ? ntiles : resident;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, stream, p);
+    const unsigned grid = persistent_launch_grid(once, (const void*)kern, 512, smem, cdiv(p.M, 256) * cdiv(p.N, 256), "gemm");
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, stream, p);
     ME_HIP(hipGetLastError());
 }
 
@@ -2539,19 +2486,8 @@ void conv_halo_launch(const GemmParams& p, hipStream_t stream) {
              p.Cin);
     auto kern = conv_halo_kernel<T, EPI, TH, BN>;
     static PerDeviceOnce once;
-    const int resident = per_device_once(once, [&](int dev) {
-        ME_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        int per_cu = 0, cus = 0;
-        ME_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, 512, smem));
-        ME_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        int r = (per_cu < 1 ? 1 : per_cu) * cus;
-        r -= r % 8;
-        return r < 8 ? 8 : r;
-    });
-    const int64_t ntiles = (int64_t)(p.M / (TH * 16)) * cdiv(p.N, BN);
-    ME_CHECK(ntiles > 0 && ntiles < (1ll << 31), ME_ERR_BAD_SHAPE, "conv grid %lld out of range", (long long)ntiles);
-    const int64_t grid = ntiles < resident ? ntiles : resident;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, stream, p);
+    const unsigned grid = persistent_launch_grid(once, (const void*)kern, 512, smem, (int64_t)(p.M / (TH * 16)) * cdiv(p.N, BN), "conv");
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, stream, p);
     ME_HIP(hipGetLastError());
 }
 
@@ -2708,10 +2644,7 @@ void gemm_launch_ring(const GemmParams& p, hipStream_t stream) {
     constexpr int smem = NST * (BM + BN) * 128;
     auto kern = gemm_ring_kernel<T, BM, BN, WM, WN, NST, AMODE, EPI>;
     static PerDeviceOnce once;
-    per_device_once(once, [&](int) {
-        ME_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        return 1;
-    });
+    set_max_dynamic_lds_once(once, (const void*)kern, smem);
     const int64_t ntiles = cdiv(p.M, BM) * cdiv(p.N, BN);
     ME_CHECK(ntiles > 0 && ntiles < (1ll << 31), ME_ERR_BAD_SHAPE, "gemm grid %lld out of range",
              (long long)ntiles);

@@ -19,7 +19,6 @@
 //     columns) -- one dwordx2 and one dword load per wave per slab, straight to registers.  They are issued
 //     as asm (invisible to the compiler's waitcnt pass, like the LDS-DMA) at the top of the slab BEFORE the
 //     one they are for, and retired by the kernel's own closing waits, which name the registers as operands.
-#include <cstdlib>
 #include <string>
 
 #include "gemm_core.h"
@@ -272,18 +271,8 @@ static void launch_pp8(const GemmParams& p, hipStream_t stream) {
     constexpr int smem = (2 * 256 + 3 * 256) * 128;
     auto kern = gemm_pp8_kernel<EPI, OUT8>;
     static PerDeviceOnce once;
-    const int resident = per_device_once(once, [&](int dev) {
-        ME_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        int per_cu = 0, cus = 0;
-        ME_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, 512, smem));
-        ME_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        int r = (per_cu < 1 ? 1 : per_cu) * cus;
-        r -= r % 8;
-        return r < 8 ? 8 : r;
-    });
-    const int64_t ntiles = cdiv(p.M, 256) * (p.N / 256);
-    const int64_t grid = ntiles < resident ? ntiles : resident;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, stream, p);
+    const unsigned grid = persistent_launch_grid(once, (const void*)kern, 512, smem, cdiv(p.M, 256) * (p.N / 256), "fp8 gemm");
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, stream, p);
     ME_HIP(hipGetLastError());
 }
 
@@ -544,44 +533,25 @@ __global__ __launch_bounds__(512, 2) void gemm_pp8t_kernel(const GemmParams p) {
     }
 }
 
-// workgroups of the tall fp8 kernel that are resident at once on the CUs `stream` may use (one per CU: 152 KiB of LDS)
+// sized as gemm_core.h gemm_launch_pp sizes its grid (one workgroup per CU: 152 KiB of LDS), without GemmParams::grid_cap
 template <int EPI, int OUT8, bool LNF>
 static void launch_pp8t(const GemmParams& p, hipStream_t stream) {
     constexpr int smem = (2 * 352 + 2 * 256) * 128;
     auto kern = gemm_pp8t_kernel<EPI, OUT8, LNF>;
     static PerDeviceOnce once;
-    const int occ = per_device_once(once, [&](int dev) {
-        ME_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        int per_cu = 0, cus = 0;
-        ME_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, 512, smem));
-        ME_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        return ((per_cu < 1 ? 1 : per_cu) << 12) | (cus < 1 ? 1 : (cus > 4095 ? 4095 : cus));
-    });
-    int cus = occ & 4095;
-    if (p.cu_granted > 0 && p.cu_granted < cus) cus = p.cu_granted;
-    int resident = (occ >> 12) * cus;
-    resident -= resident % 8;
-    if (resident < 8) resident = 8;
     const int64_t nbn = p.N / 256, nbm = seg_row_tiles<352>(p.M, p.seg1, p.seg2);
     const int64_t ntiles = LNF ? cdiv(nbm, 8) * 8 * nbn : nbm * nbn;  // LNF: the kernel's padded walk
-    int64_t grid = ntiles < resident ? ntiles : resident;
-    if (LNF) {
-        const int64_t unit = 8 * nbn;  // a round is a whole number of row tiles per XCD, all of it resident (they wait for one another)
-        ME_CHECK(resident >= unit, ME_ERR_HIP, "fp8 gemm: the fused LayerNorm needs %lld resident workgroups (%d fit)", (long long)unit, resident);
-        grid -= grid % unit;
-    }
-    // (the test knob of gemm_launch_pp: a cap that splits a round makes the LayerNorm exchange time out)
-    static const int grid_limit = getenv("ME_GEMM_GRID_LIMIT") ? atoi(getenv("ME_GEMM_GRID_LIMIT")) : 0;
-    if (grid_limit >= 8 && grid > grid_limit) grid = grid_limit - grid_limit % 8;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, stream, p);
+    const unsigned grid = persistent_launch_grid(once, (const void*)kern, 512, smem, ntiles, "fp8 gemm", p.cu_granted, p.resident_out,
+                                                 LNF ? 8 * nbn : 0, gemm_grid_limit(), 0);
+    if (!grid) return;  // the query form
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, stream, p);
     ME_HIP(hipGetLastError());
 }
 
 // The 352-row tile where its rounds x 352 undercut the 256-row tile's rounds x 256 (pipeline.hip tall_tile_wins, without the
 // short-tail form the fp8 path does not have); ME_FP8_TALL=0 turns it off, =1 forces it.
 static bool fp8_tall_wins(const GemmParams& p) {
-    const char* env = getenv("ME_FP8_TALL");  // (read per launch: the tests flip it inside one process)
-    const int knob = env ? atoi(env) : -1;
+    const int knob = env_int("ME_FP8_TALL", -1);  // (read per launch: the tests flip it inside one process)
     if (knob == 0) return false;
     if (knob == 1) return true;
     const int64_t nbn = p.N / 256;
@@ -597,6 +567,7 @@ static bool fp8_tall_wins(const GemmParams& p) {
 // p.out8 / p.out8_scale when out8) or EPI_RESID_SCALE.
 void gemm_fp8_launch(const GemmParams& p_in, EpiKind epi, hipStream_t stream) {
     GemmParams p = p_in;
+    p.resident_out = nullptr;
     p.status = current_status_word();
     // the 256-row tile takes whole tiles only (M and the row segments multiples of 256); the 352-row tile clamps its rows, its
     // row segments start on a 16-row MFMA tile
@@ -632,8 +603,7 @@ void gemm_fp8_launch(const GemmParams& p_in, EpiKind epi, hipStream_t stream) {
     const bool tall = lnf || !whole256 || fp8_tall_wins(p);
     if (tall) {
         p.cu_granted = stream_cu_count(stream);
-        static const int spin = getenv("ME_LN_SPIN_LIMIT") ? atoi(getenv("ME_LN_SPIN_LIMIT")) : 0;  // test knob
-        p.ln_spin_limit = spin > 0 ? spin : 0;
+        p.ln_spin_limit = gemm_ln_spin_limit();
     }
     const std::string pname = std::string("gemm_kernel<fp8,") + (tall ? "352" : "256") + "x256x128/8w-pp,plain," +
                               (epi == EPI_RESID_SCALE ? "resid_scale>" : "store>");
@@ -660,6 +630,16 @@ void gemm_fp8_launch(const GemmParams& p_in, EpiKind epi, hipStream_t stream) {
     } else {
         fail(ME_ERR_BAD_ARG, "fp8 gemm: epilogue %d", (int)epi);
     }
+}
+
+// what gemm_lnf_resident (gemm.hip) is to the 16-bit kernel: the resident workgroups of the kernel that carries the LayerNorm here
+int gemm_fp8_lnf_resident(hipStream_t stream) {
+    GemmParams p = GemmParams();
+    int32_t resident = 0;
+    p.resident_out = &resident;
+    p.cu_granted = stream_cu_count(stream);
+    launch_pp8t<EPI_RESID_SCALE, 0, true>(p, stream);  // (the query form: nothing is launched)
+    return resident;
 }
 
 // ---- quantisers -----------------------------------------------------------------------------------------

@@ -16,8 +16,6 @@
 //     1 / f_norm, clamp, one f32 per pixel.
 // MFMA orientation as in gemm_core.h: A operand = weights (16 output channels x 32 k), B operand = pixels (16 x 32 k);
 // a lane's accumulator holds channels 4 (lane >> 4) + r of pixel lane & 15.
-#include <cstdlib>
-
 #include "gemm_core.h"
 
 namespace me {
@@ -266,16 +264,18 @@ bool head_final_halo_fits(const GemmParams& p) {
 
 void head_final_halo_launch(const GemmParams& p, int32_t dtype, hipStream_t stream) {
     ME_CHECK(head_final_halo_fits(p), ME_ERR_BAD_SHAPE, "head: the halo kernel takes 3x3 / 128 -> 32 on maps of 12 x 16 pixel multiples");
-    static PerDeviceOnce once;  // per device: the LDS the kernel asks for, and how many workgroups are resident (one per CU)
+    // Rules of its own, so only launch.h's attribute setter and launch_grid.h's minimum fit: one guard over both kernels, resident =
+    // the CU count without an occupancy query (a workgroup's LDS takes the CU; unrounded, 256 where the runtime reports none), grid_cap unrounded.
+    static PerDeviceOnce once;
     const int resident = per_device_once(once, [&](int dev) {
-        ME_HIP(hipFuncSetAttribute((const void*)head_halo_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, HEAD_SMEM));
-        ME_HIP(hipFuncSetAttribute((const void*)head_halo_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, HEAD_SMEM));
+        set_max_dynamic_lds((const void*)head_halo_kernel<f16>, HEAD_SMEM);
+        set_max_dynamic_lds((const void*)head_halo_kernel<bf16>, HEAD_SMEM);
         int cus = 0;
         ME_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
         return cus > 0 ? cus : 256;
     });
     const int ntiles = (p.M / (p.out_H * p.out_W)) * (p.out_H / HEAD_TH) * (p.out_W / 16);
-    int grid = ntiles < resident ? ntiles : resident;
+    int grid = (int)persistent_grid(ntiles, resident, 0, 0, 0);
     if (p.grid_cap >= 8 && grid > p.grid_cap) grid = p.grid_cap;
     if (dtype == ME_DTYPE_F16)
         hipLaunchKernelGGL(head_halo_kernel<f16>, dim3((unsigned)grid), dim3(512), HEAD_SMEM, stream, p);

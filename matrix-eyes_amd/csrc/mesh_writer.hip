@@ -267,7 +267,7 @@ void write_file_parallel(const std::string& path, const char* data, size_t bytes
     // Two threads: the copy into the page cache runs at 2.4 - 2.7 GB/s per FILE with 2 or with 8 writers, and with one
     // rank per GPU writing at once eight writers per file cost the node half of what it can take (tools/
     // node_write_ceiling.py on the 256-core host: 8 processes x 2 threads 20.6 GB/s, x 8 threads 9.7 GB/s).  ME_WRITE_THREADS.
-    static const int want = getenv("ME_WRITE_THREADS") ? std::max(1, std::min(64, atoi(getenv("ME_WRITE_THREADS")))) : 2;
+    static const int want = std::max(1, std::min(64, env_int("ME_WRITE_THREADS", 2)));
     const int nthreads = (int)std::min<int64_t>(nchunks, want);
     std::atomic<int64_t> next{0};
     std::atomic<int> failed{0};

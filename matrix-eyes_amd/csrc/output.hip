@@ -7,6 +7,7 @@
 // explicitly rounded intrinsics (__fmul_rn, __fadd_rn, __fsub_rn, __fdiv_rn) and the whole file is
 // compiled with floating-point contraction off.
 #include "common.h"
+#include "launch.h"
 #include "../../include/me_viridis_lut.h"
 #include "scan.h"
 
@@ -439,11 +440,7 @@ void stereogram_launch(const float* depth, int32_t rows, int32_t cols, float min
     while ((1 << rounds) < out_w) ++rounds;
     const size_t lds = (size_t)out_w * 2 * sizeof(int);
     static PerDeviceOnce once;
-    per_device_once(once, [&](int) {
-        ME_HIP(hipFuncSetAttribute((const void*)stereogram_kernel,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 2 * 4));
-        return 1;
-    });
+    set_max_dynamic_lds_once(once, (const void*)stereogram_kernel, 16384 * 2 * 4);
     hipLaunchKernelGGL(stereogram_kernel, dim3(out_h), dim3(256), lds, stream, depth, rows, cols,
                        min_depth, max_depth, range_dev, out_w, out_h, amplitude, noise, out, rounds);
     ME_HIP(hipGetLastError());

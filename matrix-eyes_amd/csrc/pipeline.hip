@@ -63,6 +63,11 @@ void from_device(me_ctx* ctx, void* dst, const void* src_dev, size_t bytes) {
 
 namespace {
 
+// ME_GEMM_TALL=0: no 352-row tile (tall_tile_wins), and with it no fused LayerNorm (ln_fusable)
+bool tall_tile_enabled() { static const bool on = env_on("ME_GEMM_TALL"); return on; }
+// ME_GEMM_PP192: the 192-row tile for proj (resid_all's A/B), which the fused LayerNorm does not have
+bool pp192_selected() { static const bool on = getenv("ME_GEMM_PP192") != nullptr; return on; }
+
 // ---- thin launch helpers: the descriptors come from gemm_params.h, the launch decisions are made here ----
 // Deterministic split-K for the small deep launches of the tail (gemm_core.h gemm_kernel<..., SPLITK>; VERDICT r4
 // "missing" 6): a launch whose image has fewer than 200 tiles of 128 x 128 and K >= ME_SPLIT_K_MINK (4096) runs on that tile with
@@ -73,8 +78,8 @@ namespace {
 // more than the longer K loop it replaces (+0.15 ms at K >= 2048).
 // Returns the tile configuration to force (1) or -1.
 int maybe_split_k(me_ctx* ctx, GemmParams& p, int64_t rows_per_image, hipStream_t s) {
-    static const bool on = getenv("ME_SPLIT_K") && atoi(getenv("ME_SPLIT_K")) != 0;
-    static const int min_k = getenv("ME_SPLIT_K_MINK") ? atoi(getenv("ME_SPLIT_K_MINK")) : 4096;  // (the tests lower it: a tiny model has no K that deep)
+    static const bool on = env_flag("ME_SPLIT_K");
+    static const int min_k = env_int("ME_SPLIT_K_MINK", 4096);  // (the tests lower it: a tiny model has no K that deep)
     if (!on || rows_per_image <= 0 || p.K < min_k) return -1;
     const int64_t tiles_img = cdiv(rows_per_image, 128) * cdiv((int64_t)p.N, 128);
     if (tiles_img >= 200) return -1;
@@ -330,7 +335,7 @@ struct MergedVit {
     // proj 93.7 -> 82.7 us, fc2 211.7 -> 207.7 us stand-alone (profiles/r03_tail_tile_ab.txt); in the step, same box,
     // alternating runs: 25.17 ms (off) -> 24.90 (proj / fc2 split) -> 24.70 (fc1 too).  ME_GEMM_TAIL96=0 turns it off.
     bool launch_with_short_tail(const GemmParams& p, EpiKind epi) {
-        static const bool enabled = !(getenv("ME_GEMM_TAIL96") && atoi(getenv("ME_GEMM_TAIL96")) == 0);
+        static const bool enabled = env_on("ME_GEMM_TAIL96");
         if (!enabled || p.N % 256 || p.M % 256 || p.K < 128) return false;
         const int64_t nbn = p.N / 256;
         if (256 % nbn) return false;
@@ -363,8 +368,7 @@ struct MergedVit {
     // costs (whole rounds x 256, + 0.69 x 256 for a short tail or a whole round where no tail applies).
     // ME_GEMM_TALL=0 turns it off.
     bool tall_tile_wins(const GemmParams& p) const {
-        static const bool enabled = !(getenv("ME_GEMM_TALL") && atoi(getenv("ME_GEMM_TALL")) == 0);
-        if (!enabled || p.N % 256 || p.K < 128 || ctx->C() < 256) return false;
+        if (!tall_tile_enabled() || p.N % 256 || p.K < 128 || ctx->C() < 256) return false;
         const int64_t nbn = p.N / 256;
         const int64_t tiles352 = (int64_t)seg_row_tiles<352>(p.M, p.seg1, p.seg2) * nbn;
         const int64_t tiles256 = cdiv(p.M, 256) * nbn;
@@ -412,17 +416,16 @@ struct MergedVit {
     // 352-row tile, C in {256, 512, 1024}.  When it applies it applies at EVERY batch size (the tall tile is then taken
     // whatever tall_tile_wins says), so that a row's statistics are summed in the same order whatever batch the row is
     // part of: a batch stays a loop of batch-one calls bit for bit.  ME_LN_FUSE=0: the stand-alone LayerNorm launches.
-    bool ln_fusable() const {
-        static const bool enabled = !(getenv("ME_LN_FUSE") && atoi(getenv("ME_LN_FUSE")) == 0);
-        static const bool tall = !(getenv("ME_GEMM_TALL") && atoi(getenv("ME_GEMM_TALL")) == 0);
-        static const bool pp192 = getenv("ME_GEMM_PP192") != nullptr;
+    // fp8_gemm: the launch that would carry it is gemm8's (gemm_fp8.hip's tall kernel), not resid_all's 16-bit one.
+    bool ln_fusable(bool fp8_gemm) const {
+        static const bool enabled = env_on("ME_LN_FUSE");
         const int C = ctx->C();
-        if (!(enabled && tall && !pp192 && (C == 256 || C == 512 || C == 1024))) return false;
+        if (!(enabled && tall_tile_enabled() && !pp192_selected() && (C == 256 || C == 512 || C == 1024))) return false;
         // the context has seen the exchange time out (api.hip run_with_ln_fallback): stand-alone LayerNorm from then on
         if (ctx->ln_fuse_off) return false;
         // one row tile per XCD with all its column tiles must be resident at once on the CUs the stream may use
         // (a smaller part, a partition mode, a stream with a CU mask): otherwise the stand-alone LayerNorm
-        return gemm_lnf_resident(ctx->dtype, s) >= 8 * (C / 256);
+        return (fp8_gemm ? gemm_fp8_lnf_resident(s) : gemm_lnf_resident(ctx->dtype, s)) >= 8 * (C / 256);
     }
     // returns true when xn holds LayerNorm(ln) of the updated rows
     bool resid_all(const char* A, int K, const SegWeights& w, const LnSet* ln = nullptr,
@@ -435,10 +438,9 @@ struct MergedVit {
         // 192-row form (tile config 5; the segment order above makes every boundary a multiple of 192 at one image)
         // wins for proj stand-alone (94.7 -> 80.3 us) and loses in the step (90 -> 95.6 us per launch, same box,
         // bench.py A/B): ME_GEMM_PP192=1 selects it for that comparison.
-        static const bool use_pp192 = getenv("ME_GEMM_PP192") != nullptr;
         const bool pp = C >= 256 && K >= 128;
-        const bool pp192 = pp && K <= 1024 && use_pp192 && seg1 % 192 == 0 && seg2 % 192 == 0;
-        if (ln && pp && ln_fusable() && (ln_fp8 || !ctx->fp8)) {
+        const bool pp192 = pp && K <= 1024 && pp192_selected() && seg1 % 192 == 0 && seg2 % 192 == 0;
+        if (ln && pp && ln_fusable(false) && (ln_fp8 || !ctx->fp8)) {
             set_fused_layernorm(ctx, p, "vitm.ln.stats", "vitm.ln.count", *ln, ctx->cfg.ln_eps, xn, ln_fp8 ? (uint8_t*)xn : nullptr, xn_s);
             gemm_launch(p, A_PLAIN, EPI_RESID_SCALE, ctx->dtype, s, CFG_PP352);
             return true;
@@ -472,8 +474,8 @@ struct MergedVit {
             else set_out8(p, (uint8_t*)hid, hid_s);
             gemm_fp8_launch(p, EPI_STORE, s);
         } else {
-            static const bool fp8_lnf = !(getenv("ME_FP8_LN_FUSE") && atoi(getenv("ME_FP8_LN_FUSE")) == 0);
-            const bool fuse = ln && fp8_lnf && ln_fusable();
+            static const bool fp8_lnf = env_on("ME_FP8_LN_FUSE");
+            const bool fuse = ln && fp8_lnf && ln_fusable(true);
             if (fuse) set_fused_layernorm(ctx, p, "vitm.ln.stats", "vitm.ln.count", *ln, ctx->cfg.ln_eps, xn, (uint8_t*)xn, xn_s);
             gemm_fp8_launch(p, EPI_RESID_SCALE, s);
             return fuse;
@@ -704,7 +706,7 @@ void stage_encoder_trunk(me_ctx* ctx, const float* img32, int B, bool fov_async 
 // the head behind head[0] as one launch on the half-resolution map (stage_head): needs the un-split chain and the 128-channel
 // halo tile's shapes; ME_HEAD_COMPOSED=0: the three launches
 static bool head_composed_applies(const me_ctx* ctx, int B) {
-    static const bool composed_on = !(getenv("ME_HEAD_COMPOSED") && atoi(getenv("ME_HEAD_COMPOSED")) == 0);
+    static const bool composed_on = env_on("ME_HEAD_COMPOSED");
     const int dec = ctx->cfg.dec_dim, Hh = ctx->S() / 2;
     return composed_on && !ctx->split(SPLIT_HEAD) && ctx->w.head_fused_w && Hh % 16 == 0 && (dec / 2) % 64 == 0 &&
            ((int64_t)B * Hh * Hh) % 256 == 0;
@@ -781,7 +783,7 @@ void stage_decoder_levels(me_ctx* ctx, int B, bool want_features32, int first, i
             // convolution writes out_conv's INPUT as head[0]'s zero-bordered operand, the 1x1 launch and the feature map between
             // them (0.9 GB of traffic at 768 x 768) go.  Not when the caller wants the features themselves, nor under SPLIT_HEAD;
             // ME_FEAT_COMPOSED=0: the two layers as they are.
-            static const bool feat_composed_on = !(getenv("ME_FEAT_COMPOSED") && atoi(getenv("ME_FEAT_COMPOSED")) == 0);
+            static const bool feat_composed_on = env_on("ME_FEAT_COMPOSED");
             ctx->features_pre = feat_composed_on && !want_features32 && head_composed_applies(ctx, B) && ctx->w.feat_fused_w;
             if (ctx->features_pre) {
                 ConvOut o4;

@@ -185,7 +185,9 @@ def test_depth_map_rgb_on_non_square_maps(shape, content):
     assert np.array_equal(dm.depth_map_rgb(), want)
     # the chained form: range read from device memory
     ddm = m.DeviceDepthMap(ctx, torch.from_numpy(d.copy()).cuda(), (shape[1], shape[0]))
-    assert np.array_equal(ddm.depth_map_rgb().cpu().numpy(), want) and ddm.inverse_depth_range() == (mn, mx)
+    got = ddm.depth_map_rgb()
+    # (inverse_depth_range() synchronises the context's stream, which torch's copy back to the host does not wait for: first)
+    assert ddm.inverse_depth_range() == (mn, mx) and np.array_equal(got.cpu().numpy(), want)
 
 
 # ---- stereogram -------------------------------------------------------------------------------------------------------------
