@@ -188,6 +188,43 @@ int32_t me_weights_adopt(me_ctx* ctx);
    me_weights_adopt. */
 uint64_t me_weight_arena_layout(const me_ctx* ctx);
 
+/* ---- the device weight packer and the arena cache (mod.rs:211-247 --convert-checkpoints) ------------------------------
+   Who packs a checkpoint tensor into the arena: 0 (the default) the host, one core, with one synchronous upload per
+   tensor; 1 the device (csrc/weight_pack.hip): me_load_weight and me_load_checkpoint_pt copy the tensor's raw bytes, in the
+   checkpoint's layout and dtype, into a ring of pinned buffers, queue the upload and one pack kernel on the context's
+   stream and return; me_weights_finalize waits for them.  The arena is byte for byte the host packer's.  A HOST source is
+   not read after me_load_weight returns; a DEVICE source is packed where it lies, by a kernel on the context's stream: its contents
+   must be complete when me_load_weight is called (the stream is not ordered behind the caller's) and stay valid and unchanged until
+   me_weights_finalize or me_ctx_synchronize.  Any other value is ME_ERR_BAD_ARG. */
+int32_t me_ctx_set_weight_packer(me_ctx* ctx, int32_t packer);
+/* The arena cache: a 256-byte header (magic, the format constant ME_ARENA_FORMAT of csrc/weight_pack.h, dtype,
+   me_model_config, split mask, layout hash, arena size, the source checkpoint's size and mtime, a checksum of the payload
+   computed on the device) followed by the raw arena, composed slots included.  me_save_weight_arena writes it for a context
+   with finalized weights (ME_ERR_NOT_READY otherwise) to a temporary name beside `path`, then renames; source_path (or
+   NULL) names the checkpoint whose stamp is recorded.  me_load_weight_arena reads it into the arena through pinned
+   memory, verifies the checksum on the device and finalizes like me_weights_adopt; with source_path the recorded stamp must
+   be that file's, if it exists.  A stale file (another stamp or format constant) and a damaged one (short, wrong magic,
+   another context's dtype / configuration / layout / size, checksum mismatch) are ME_ERR_IO; after a damaged one the
+   context is left unfinalized with every tensor marked not loaded. */
+int32_t me_save_weight_arena(me_ctx* ctx, const char* path, const char* source_path);
+int32_t me_load_weight_arena(me_ctx* ctx, const char* path, const char* source_path);
+/* The cache file's name for a checkpoint: "<dir>/<stem>-<f16|bf16|fp8>-<16 hex digits of me_weight_arena_layout>.mearena".
+   Returns its length (buf is NUL-terminated), or -1 for a null argument or a buf that is too small. */
+int64_t me_weight_cache_path(const me_ctx* ctx, const char* checkpoint_path, char* buf, int64_t cap);
+/* --convert-checkpoints, the policy of both command lines (mod.rs:225-247).  A valid cache file whose checkpoint is absent
+   or has the recorded size and mtime is loaded and the checkpoint not opened, whatever `convert` says; a stale one costs
+   one line on stderr, the checkpoint is loaded with the selected packer (and the cache rewritten when convert != 0: the
+   reference would load the stale file); a damaged one is ME_ERR_IO, the message names the file and says to delete it;
+   with no cache file the checkpoint is loaded, and with convert != 0 the cache written afterwards.  *where (or NULL):
+   0 the checkpoint with the host packer, 1 with the device packer, 2 the cache. */
+int32_t me_load_checkpoint_cached(me_ctx* ctx, const char* checkpoint_path, int32_t convert, int32_t* where);
+/* The context's last finished weight load.  info: [0] where the weights came from (as *where above), [1] tensors,
+   [2] bytes read, [3] bytes uploaded.  ms: [0] read and stage (host wall clock: the host packer's loops, or the copies into
+   the pinned ring), [1] upload, [2] pack kernels (the checksum kernel for the cache) -- HIP event times with the device
+   packer and the cache, wall clock with the host packer, [3] compose and finalize, [4] cache write (0: none).
+   ME_ERR_NOT_READY before the first load. */
+int32_t me_last_weight_load(me_ctx* ctx, int64_t info[4], double ms[5]);
+
 /* ---- multi-GPU start-up: one RCCL broadcast of the packed arena, no collective later ---
    rank 0 finalizes its weights, every rank calls me_bcast_weights with the same 128-byte id
    (from me_rccl_unique_id on rank 0, shipped by the launcher's own store). */

@@ -264,6 +264,19 @@ int32_t me_op_jpeg_encode_host(const uint8_t* rgb, int32_t w, int32_t h, int32_t
    [0] upload of a host picture and the tables, [1] fdct, [2] bits and their scan, [3] pack (with the read-back of the
    scan's bits), [4] stuffing, [5] download of the file (0 when it stayed on the device). */
 int32_t me_last_jpeg_encode(me_ctx* ctx, int64_t report[10], double ms[6]);
+/* One pack kernel of the device weight packer (csrc/weight_pack.hip) on its own: a tensor of `dims` in the checkpoint's
+   layout and element type src_dtype (ME_WEIGHT_*) into the arena layout of `kind` -- 0 flat f32, 1 16-bit matrix
+   [N][K], 2 Conv2d [Cout][Cin][kh][kw] -> [Cout][kh*kw][Cin], 3 ConvTranspose2d [Cin][Cout][2][2] -> [(dy*2+dx)*Cout + co][Cin],
+   4 [1][Cin][k][k] -> f32 [k][k][Cin] -- in the context's 16-bit type, with every run of K (or Cin) values written twice,
+   [W | W], when dup != 0 (kinds 1 - 3).  dst receives numel * (dup ? 2 : 1) elements.  Host or device pointers.  Dimensions
+   that do not fit the kind (or more than 64 taps) are ME_ERR_BAD_SHAPE. */
+int32_t me_op_weight_pack(me_ctx* ctx, int32_t kind, int32_t dup, const int64_t* dims, int32_t ndim, const void* src,
+                          int32_t src_dtype, void* dst);
+/* The host packer (csrc/weight_pack.h pack_host, the loops me_load_weight runs with packer 0) without a context: dtype is
+   ME_DTYPE_F16 or ME_DTYPE_BF16.  HOST arrays only, no GPU.  0, or < 0 on a null pointer (-1), a bad dtype (-2) or
+   dimensions that do not fit the kind (-3). */
+int32_t me_op_weight_pack_host(int32_t dtype, int32_t kind, int32_t dup, const int64_t* dims, int32_t ndim, const void* src,
+                               int32_t src_dtype, void* dst);
 /* Names of the GEMM tile configurations (for reports). */
 int32_t me_op_gemm_config_count(void);
 const char* me_op_gemm_config_name(int32_t cfg);

@@ -109,13 +109,14 @@ impl HipDevice {
     }
 
     /// mod.rs:174-249 load_record, once per device: the library reads the PyTorch archive itself (no key remap,
-    /// no transpose adapter: it takes PyTorch names and layouts).
-    pub fn ensure_loaded(&self, checkpoint_path: &str) -> Result<(), HipError> {
+    /// no transpose adapter: it takes PyTorch names and layouts).  mod.rs:211-247: a valid `.mearena` cache beside the
+    /// checkpoint is loaded instead, and written after loading when `convert_checkpoints` is set.
+    pub fn ensure_loaded(&self, checkpoint_path: &str, convert_checkpoints: bool) -> Result<(), HipError> {
         if self.weights_loaded.get() {
             return Ok(());
         }
         let path = CString::new(checkpoint_path).map_err(|_| HipError { code: ffi::ME_ERR_BAD_ARG, message: "path".into() })?;
-        self.check(unsafe { ffi::me_load_checkpoint_pt(self.ctx, path.as_ptr()) })?;
+        self.check(unsafe { ffi::me_load_checkpoint_cached(self.ctx, path.as_ptr(), convert_checkpoints as i32, std::ptr::null_mut()) })?;
         self.weights_loaded.set(true);
         Ok(())
     }

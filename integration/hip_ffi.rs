@@ -90,6 +90,12 @@ extern "C" {
     pub fn me_weight_arena_ptr(ctx: *const MeCtx) -> *mut c_void;
     pub fn me_weights_adopt(ctx: *mut MeCtx) -> i32;
     pub fn me_weight_arena_layout(ctx: *const MeCtx) -> u64;
+    pub fn me_ctx_set_weight_packer(ctx: *mut MeCtx, packer: i32) -> i32;
+    pub fn me_save_weight_arena(ctx: *mut MeCtx, path: *const c_char, source_path: *const c_char) -> i32;
+    pub fn me_load_weight_arena(ctx: *mut MeCtx, path: *const c_char, source_path: *const c_char) -> i32;
+    pub fn me_weight_cache_path(ctx: *const MeCtx, checkpoint_path: *const c_char, buf: *mut c_char, cap: i64) -> i64;
+    pub fn me_load_checkpoint_cached(ctx: *mut MeCtx, checkpoint_path: *const c_char, convert: i32, where_out: *mut i32) -> i32;
+    pub fn me_last_weight_load(ctx: *mut MeCtx, info: *mut i64, ms: *mut f64) -> i32;
     pub fn me_rccl_unique_id(id128: *mut c_void) -> i32;
     pub fn me_bcast_weights(ctx: *mut MeCtx, id128: *const c_void, rank: i32, nranks: i32) -> i32;
     pub fn me_preprocess_u8(ctx: *mut MeCtx, rgb: *const u8, batch: i32, img: *mut f32) -> i32;

@@ -60,6 +60,12 @@ SIGNATURES = {
     "me_weight_arena_ptr": (_vp, [_vp]),
     "me_weights_adopt": (_i32, [_vp]),
     "me_weight_arena_layout": (C.c_uint64, [_vp]),
+    "me_ctx_set_weight_packer": (_i32, [_vp, _i32]),
+    "me_save_weight_arena": (_i32, [_vp, C.c_char_p, C.c_char_p]),
+    "me_load_weight_arena": (_i32, [_vp, C.c_char_p, C.c_char_p]),
+    "me_weight_cache_path": (_i64, [_vp, C.c_char_p, C.c_char_p, _i64]),
+    "me_load_checkpoint_cached": (_i32, [_vp, C.c_char_p, _i32, C.POINTER(_i32)]),
+    "me_last_weight_load": (_i32, [_vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
     "me_rccl_unique_id": (_i32, [_vp]),
     "me_bcast_weights": (_i32, [_vp, _vp, _i32, _i32]),
     "me_preprocess_u8": (_i32, [_vp, _vp, _i32, _vp]),
@@ -167,6 +173,8 @@ SIGNATURES = {
     "me_op_jpeg_entropy": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64]),
     "me_op_jpeg_encode_host": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _i64, C.POINTER(_i64)]),
     "me_last_jpeg_encode": (_i32, [_vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
+    "me_op_weight_pack": (_i32, [_vp, _i32, _i32, C.POINTER(_i64), _i32, _vp, _i32, _vp]),
+    "me_op_weight_pack_host": (_i32, [_i32, _i32, _i32, C.POINTER(_i64), _i32, _vp, _i32, _vp]),
     "me_op_gemm_config_count": (_i32, []),
     "me_op_gemm_config_name": (C.c_char_p, [_i32]),
 }

@@ -279,6 +279,9 @@ int32_t me_ctx_create(int32_t device_id, int32_t dtype, const me_model_config* c
         *ctx->status_host = 0;
         build_weight_table(ctx);
         ME_HIP(hipMalloc((void**)&ctx->arena, ctx->arena_bytes));
+        // the alignment gaps between slots belong to the arena's bytes (the cache file, its checksum, a broadcast): zero, not whatever
+        // the allocation held
+        ME_HIP(hipMemset(ctx->arena, 0, ctx->arena_bytes));
         resolve_weights(ctx);
         *out = ctx;
         return ME_OK;
@@ -307,6 +310,7 @@ void me_ctx_destroy(me_ctx* ctx) {
     me::free_resample_tables(ctx);
     me::free_jpeg_scratch(ctx);
     me::free_png_scratch(ctx);
+    me::free_weight_pack(ctx);
     if (ctx->arena) (void)hipFree(ctx->arena);
     if (ctx->arena8) (void)hipFree(ctx->arena8);
     if (ctx->status_dev) (void)hipFree(ctx->status_dev);
@@ -436,11 +440,7 @@ void* me_weight_arena_ptr(const me_ctx* ctx) { return ctx ? (void*)ctx->arena : 
 
 int32_t me_weights_adopt(me_ctx* ctx) {
     ME_API_BEGIN(ctx)
-    for (WeightSlot& s : ctx->slots) s.loaded = true;
-    ctx->factor_keep.clear();  // host copies of factors of the arena this one replaces
-    build_fp8_weights(ctx);
-    ctx->finalized = true;
-    ctx->drop_graph(), ++ctx->weights_generation;
+    adopt_weights(ctx);
     ME_API_END(ctx)
 }
 

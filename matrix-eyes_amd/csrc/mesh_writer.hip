@@ -320,6 +320,11 @@ void write_mtl(const std::string& dest, const std::string& stem, const char* sou
 
 }  // namespace
 
+namespace me {
+// write_file_parallel for the arena cache (weight_pack.hip)
+void write_bytes_parallel(const std::string& path, const char* data, size_t bytes) { write_file_parallel(path, data, bytes); }
+}  // namespace me
+
 // waits for pending write k; a failure becomes the Error of the caller that waited for it
 static void join_pending_write(me_ctx* ctx, int k) {
     me_ctx::WriteSlot& w = ctx->write_slots[(size_t)k];

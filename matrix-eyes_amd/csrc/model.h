@@ -123,6 +123,8 @@ struct ResampleTable {
     uint64_t stamp = 0;       // last use, for eviction
 };
 
+struct WeightPackState;  // weight_pack_state.h: the device packer's staging ring, the last load's report
+
 }  // namespace me
 
 // The opaque C handle.
@@ -195,6 +197,10 @@ struct me_ctx {
     size_t feat_fused_off = 0;   // 0: not composed
     bool features_pre = false;   // "features.16b" holds out_conv's INPUT (stage_decoder_levels with the composed head[0])
     std::map<std::string, std::vector<float>> factor_keep;
+    // me_ctx_set_weight_packer: 0 the host packer (load_weight's loops on one core, a synchronous upload per tensor),
+    // 1 the device packer (weight_pack.hip: raw bytes through a pinned ring, one pack kernel per tensor on the stream)
+    int32_t weight_packer = 0;
+    me::WeightPackState* wp = nullptr;
 
     // me_status_flags: one device word the kernels OR bits into (ME_STATUS_OVERFLOW_16BIT: an f16 operand store
     // met a magnitude beyond 65504, common.h raise_overflow16)
@@ -364,6 +370,13 @@ void finalize_weights(me_ctx* ctx);
 void load_checkpoint_pt(me_ctx* ctx, const char* path);
 // (re)derives the MX fp8 weight copies from the 16-bit arena (fp8 contexts; no-op otherwise)
 void build_fp8_weights(me_ctx* ctx);
+// what me_weights_adopt does: an arena that arrived from elsewhere (a broadcast, a caller's collective, the cache file)
+void adopt_weights(me_ctx* ctx);
+// weight_pack.hip: the device packer behind load_weight (the slot's tensor, raw, from a host or device pointer: staged,
+// uploaded and packed asynchronously on the context's stream), the wait finalize_weights starts with, and the arena cache
+void device_pack_weight(me_ctx* ctx, WeightSlot& s, const void* data, int32_t weight_dtype);
+void weight_pack_sync(me_ctx* ctx);
+void free_weight_pack(me_ctx* ctx);
 
 // thrown by site_buf when a buffer would have to be (re)allocated while a stream capture is open
 struct CaptureAbort {};

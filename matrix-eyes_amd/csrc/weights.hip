@@ -9,6 +9,7 @@
 
 #include "../host/pt_reader.hpp"
 #include "model.h"
+#include "weight_pack_state.h"
 
 namespace me {
 
@@ -109,63 +110,25 @@ void resolve_upsample(me_ctx* ctx, const std::string& p, int64_t dim_out, int la
     }
 }
 
-// IEEE half <-> float on the host (no dependence on compiler half support in host code paths)
-inline float half_to_float(uint16_t h) {
-    const uint32_t sign = (uint32_t)(h & 0x8000) << 16;
-    uint32_t exp = (h >> 10) & 0x1f, man = h & 0x3ff;
-    uint32_t bits;
-    if (exp == 0) {
-        if (man == 0) {
-            bits = sign;
-        } else {
-            int e = -1;
-            do {
-                ++e;
-                man <<= 1;
-            } while (!(man & 0x400));
-            bits = sign | ((uint32_t)(127 - 15 - e) << 23) | ((man & 0x3ff) << 13);
-        }
-    } else if (exp == 31) {
-        bits = sign | 0x7f800000u | (man << 13);
-    } else {
-        bits = sign | ((exp + 127 - 15) << 23) | (man << 13);
-    }
-    float f;
-    memcpy(&f, &bits, 4);
-    return f;
-}
-inline uint16_t float_to_half(float f) {
-    _Float16 h = (_Float16)f;  // round to nearest even
-    uint16_t u;
-    memcpy(&u, &h, 2);
-    return u;
-}
-inline uint16_t float_to_bf16(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1)) >> 16);
-}
+// conversions and the host packer: weight_pack.h, shared with the device packer's kernels
+using me_pack::float_to_bf16;
+using me_pack::float_to_half;
+using me_pack::half_to_float;
 
-struct HostSrc {
-    const void* p;
-    int32_t dt;
-    float get(int64_t i) const {
-        switch (dt) {
-            case ME_WEIGHT_F32: return ((const float*)p)[i];
-            case ME_WEIGHT_F16: return half_to_float(((const uint16_t*)p)[i]);
-            case ME_WEIGHT_BF16: {
-                const uint32_t u = (uint32_t)((const uint16_t*)p)[i] << 16;
-                float f;
-                memcpy(&f, &u, 4);
-                return f;
-            }
-            default: return (float)((const double*)p)[i];
-        }
-    }
-};
-size_t weight_elem_size(int32_t dt) {
-    return dt == ME_WEIGHT_F32 ? 4 : (dt == ME_WEIGHT_F64 ? 8 : 2);
+size_t weight_elem_size(int32_t dt) { return me_pack::src_elem_size(dt); }
+
+// whether load_weight keeps a host copy of this tensor for a composition at finalize
+bool is_factor(const me_ctx* ctx, const std::string& name) {
+    if (ctx->split(SPLIT_FUSION_OUT) && name.rfind("decoder.fusions.", 0) == 0 &&
+        (name.find(".deconv.weight") != std::string::npos || name.find(".out_conv.weight") != std::string::npos))
+        return true;  // compose_fusion_out
+    if (ctx->head_fused_off && (name == "head.1.weight" || name == "head.1.bias" || name == "head.2.weight" || name == "head.2.bias" ||
+                                name == "head.4.weight"))
+        return true;  // compose_head
+    if (ctx->feat_fused_off && (name == "decoder.fusions.0.out_conv.weight" || name == "decoder.fusions.0.out_conv.bias" ||
+                                name == "head.0.weight" || name == "head.0.bias"))
+        return true;  // compose_features
+    return false;
 }
 
 }  // namespace
@@ -322,90 +285,40 @@ void load_weight(me_ctx* ctx, const char* name, const void* data, int32_t weight
     }
     const int64_t n = s.numel();
     const size_t src_bytes = (size_t)n * weight_elem_size(weight_dtype);
+    const bool device_packer = ctx->weight_packer == 1, factor = is_factor(ctx, s.name);
+    WeightLoadReport& rep = weight_load_begin(ctx);
+    rep.where = device_packer ? WS_PT_DEVICE : WS_PT_HOST;
+    ++rep.tensors, rep.bytes_read += (int64_t)src_bytes;
+    // a device-pointer source comes down for the host packer, and for the few small factors of the compositions
+    const void* host_data = data;
     std::vector<char> staged;
     if (is_device_ptr(data)) {
-        staged.resize(src_bytes);
-        ME_HIP(hipMemcpy(staged.data(), data, src_bytes, hipMemcpyDeviceToHost));
-        data = staged.data();
+        host_data = nullptr;
+        if (!device_packer || factor) {
+            staged.resize(src_bytes);
+            ME_HIP(hipMemcpy(staged.data(), data, src_bytes, hipMemcpyDeviceToHost));
+            host_data = staged.data();
+        }
     }
-    const HostSrc src{data, weight_dtype};
-    if (ctx->split(SPLIT_FUSION_OUT) && s.name.rfind("decoder.fusions.", 0) == 0 &&
-        (s.name.find(".deconv.weight") != std::string::npos || s.name.find(".out_conv.weight") != std::string::npos)) {
-        std::vector<float>& keep = ctx->factor_keep[s.name];  // composed at finalize (compose_fusion_out)
+    if (factor) {
+        std::vector<float>& keep = ctx->factor_keep[s.name];  // composed at finalize (compose_fusion_out, _head, _features)
         keep.resize((size_t)n);
-        for (int64_t i = 0; i < n; ++i) keep[i] = src.get(i);
+        for (int64_t i = 0; i < n; ++i) keep[i] = me_pack::src_get(host_data, weight_dtype, i);
     }
-    if (ctx->head_fused_off && (s.name == "head.1.weight" || s.name == "head.1.bias" || s.name == "head.2.weight" || s.name == "head.2.bias" ||
-                                s.name == "head.4.weight")) {
-        std::vector<float>& keep = ctx->factor_keep[s.name];  // composed at finalize (compose_head)
-        keep.resize((size_t)n);
-        for (int64_t i = 0; i < n; ++i) keep[i] = src.get(i);
+    if (device_packer) {
+        device_pack_weight(ctx, s, data, weight_dtype);
+    } else {
+        const double t0 = wall_ms();
+        me_pack::Shape sh;
+        const char* why = me_pack::make_shape((int32_t)s.kind, s.dup ? 1 : 0, s.dims.data(), (int32_t)s.dims.size(), &sh);
+        ME_CHECK(!why && (size_t)sh.dst_bytes == s.bytes, ME_ERR_BAD_SHAPE, "internal: slot %s: %s", name, why ? why : "size");
+        std::vector<char> packed(s.bytes);
+        me_pack::pack_host(sh, ctx->dtype, host_data, weight_dtype, packed.data());
+        const double t1 = wall_ms();
+        ME_HIP(hipMemcpy(ctx->arena + s.offset, packed.data(), s.bytes, hipMemcpyHostToDevice));
+        rep.ms[0] += t1 - t0, rep.ms[1] += wall_ms() - t1;
+        rep.bytes_uploaded += (int64_t)s.bytes;
     }
-    if (ctx->feat_fused_off && (s.name == "decoder.fusions.0.out_conv.weight" || s.name == "decoder.fusions.0.out_conv.bias" ||
-                                s.name == "head.0.weight" || s.name == "head.0.bias")) {
-        std::vector<float>& keep = ctx->factor_keep[s.name];  // composed at finalize (compose_features)
-        keep.resize((size_t)n);
-        for (int64_t i = 0; i < n; ++i) keep[i] = src.get(i);
-    }
-    std::vector<char> packed(s.bytes);
-    const bool to_bf16 = ctx->dtype == ME_DTYPE_BF16;
-    auto put16 = [&](int64_t dst, int64_t si) {
-        uint16_t* o = reinterpret_cast<uint16_t*>(packed.data());
-        if (!to_bf16 && weight_dtype == ME_WEIGHT_F16)
-            o[dst] = ((const uint16_t*)data)[si];  // fp16 checkpoint, f16 operands: exact
-        else
-            o[dst] = to_bf16 ? float_to_bf16(src.get(si)) : float_to_half(src.get(si));
-    };
-    switch (s.kind) {
-        case PK_VEC_F32: {
-            float* o = reinterpret_cast<float*>(packed.data());
-            if (weight_dtype == ME_WEIGHT_F32)
-                memcpy(o, data, (size_t)n * 4);
-            else
-                for (int64_t i = 0; i < n; ++i) o[i] = src.get(i);
-            break;
-        }
-        // dup: every run of K (or Cin) source values is followed by a copy of itself: [W | W]
-        case PK_MAT_16:
-            if (s.dup) {
-                const int64_t N = s.dims[0], K = n / N;
-                for (int64_t r = 0; r < N; ++r)
-                    for (int64_t k = 0; k < K; ++k) put16(r * 2 * K + k, r * K + k), put16(r * 2 * K + K + k, r * K + k);
-            } else if (!to_bf16 && weight_dtype == ME_WEIGHT_F16) {
-                memcpy(packed.data(), data, (size_t)n * 2);
-            } else {
-                for (int64_t i = 0; i < n; ++i) put16(i, i);
-            }
-            break;
-        case PK_CONV_16: {  // [Cout][Cin][kh][kw] -> [Cout][kh*kw][Cin]
-            const int64_t Cout = s.dims[0], Cin = s.dims[1], kk = s.dims[2] * s.dims[3];
-            const int64_t D = s.dup ? 2 : 1;
-            for (int64_t co = 0; co < Cout; ++co)
-                for (int64_t ci = 0; ci < Cin; ++ci)
-                    for (int64_t t = 0; t < kk; ++t)
-                        for (int64_t d = 0; d < D; ++d)
-                            put16((co * kk + t) * D * Cin + d * Cin + ci, (co * Cin + ci) * kk + t);
-            break;
-        }
-        case PK_CONVT_16: {  // [Cin][Cout][2][2] -> [(dy*2+dx)*Cout + co][Cin]
-            const int64_t Cin = s.dims[0], Cout = s.dims[1];
-            const int64_t D = s.dup ? 2 : 1;
-            for (int64_t ci = 0; ci < Cin; ++ci)
-                for (int64_t co = 0; co < Cout; ++co)
-                    for (int64_t q = 0; q < 4; ++q)
-                        for (int64_t d = 0; d < D; ++d)
-                            put16((q * Cout + co) * D * Cin + d * Cin + ci, (ci * Cout + co) * 4 + q);
-            break;
-        }
-        case PK_CONVK_F32: {  // [1][Cin][k][k] -> f32 [k][k][Cin]
-            const int64_t Cin = s.dims[1], kk = s.dims[2] * s.dims[3];
-            float* o = reinterpret_cast<float*>(packed.data());
-            for (int64_t ci = 0; ci < Cin; ++ci)
-                for (int64_t t = 0; t < kk; ++t) o[t * Cin + ci] = src.get(ci * kk + t);
-            break;
-        }
-    }
-    ME_HIP(hipMemcpy(ctx->arena + s.offset, packed.data(), s.bytes, hipMemcpyHostToDevice));
     s.loaded = true;
     ctx->finalized = false;
 }
@@ -687,7 +600,18 @@ void build_fp8_weights(me_ctx* ctx) {
     ME_HIP(hipStreamSynchronize(ctx->stream));
 }
 
+void adopt_weights(me_ctx* ctx) {
+    weight_pack_sync(ctx);
+    for (WeightSlot& s : ctx->slots) s.loaded = true;
+    ctx->factor_keep.clear();  // host copies of factors of the arena this one replaces
+    build_fp8_weights(ctx);
+    ctx->finalized = true;
+    ctx->drop_graph(), ++ctx->weights_generation;
+}
+
 void finalize_weights(me_ctx* ctx) {
+    weight_pack_sync(ctx);  // the device packer's uploads and kernels: the compositions read the arena from the host
+    const double t0 = wall_ms();
     std::string missing;
     int n = 0;
     for (const WeightSlot& s : ctx->slots)
@@ -704,6 +628,11 @@ void finalize_weights(me_ctx* ctx) {
     build_fp8_weights(ctx);
     ctx->finalized = true;
     ctx->drop_graph(), ++ctx->weights_generation;
+    WeightPackState& st = weight_pack_state(ctx);
+    if (st.open) {  // tensors were loaded since the last finalize: their report is complete
+        st.cur.ms[3] = wall_ms() - t0;
+        st.last = st.cur, st.reported = true, st.open = false;
+    }
 }
 
 }  // namespace me

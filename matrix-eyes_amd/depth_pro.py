@@ -148,6 +148,18 @@ def resolve_jpeg_entropy(jpeg_entropy=None) -> str:
     return _resolve_choice(jpeg_entropy, "MATRIX_EYES_JPEG_ENTROPY", "host", JPEG_ENTROPIES, "jpeg entropy decoder")
 
 
+WEIGHT_PACKERS = ("host", "device")
+WEIGHT_SOURCES = ("pt-host", "pt-device", "cache")
+
+
+def resolve_weight_packer(weight_packer=None) -> str:
+    """Who packs a checkpoint's tensors into the weight arena: "host" (the default: one core, one synchronous upload per
+    tensor) or "device" (me_ctx_set_weight_packer(ctx, 1): raw bytes through a pinned ring, one pack kernel per tensor).
+    The same arena bytes either way.  None reads MATRIX_EYES_WEIGHT_PACKER; anything but the two names is an argument
+    error."""
+    return _resolve_choice(weight_packer, "MATRIX_EYES_WEIGHT_PACKER", "host", WEIGHT_PACKERS, "weight packer")
+
+
 class _DevMem:
     """`nbytes` of device memory at `ptr`, as torch.as_tensor takes it"""
 
@@ -167,7 +179,9 @@ def _device_file(ptr, n, rgb):
 class Context:
     """One GPU: stream, packed weights, workspaces (`me_ctx`)."""
 
-    def __init__(self, device_id: int = 0, dtype: str = "f16", cfg: Optional[ModelConfig] = None):
+    def __init__(self, device_id: int = 0, dtype: str = "f16", cfg: Optional[ModelConfig] = None, weight_packer: str = "host"):
+        if weight_packer not in WEIGHT_PACKERS:
+            raise L.MatrixEyesError(1, f"weight packer {weight_packer!r}: expected one of {', '.join(WEIGHT_PACKERS)}")
         self.lib = L.load_library()
         self.cfg = cfg or ModelConfig()
         self.dtype = dtype
@@ -178,6 +192,8 @@ class Context:
         if rc != L.ME_OK:
             raise L.MatrixEyesError(rc, self.lib.me_last_error(None).decode())
         self._progress_ref = None
+        if weight_packer == "device":
+            self.set_weight_packer("device")
 
     # -- lifetime
     def close(self):
@@ -309,7 +325,14 @@ class Context:
                 a, wd = a.astype(np.float32), L.ME_WEIGHT_F32
             ptr, shape, keep = C.c_void_p(a.ctypes.data), a.shape, a
         dims = (C.c_int64 * len(shape))(*shape)
+        if _is_torch(tensor) and keep.is_cuda:
+            # whatever torch still has queued that writes the tensor: the context's stream is not ordered behind torch's
+            torch.cuda.current_stream(keep.device).synchronize()
         self._check(self.lib.me_load_weight(self._h, name.encode(), ptr, wd, dims, len(shape)))
+        if _is_torch(tensor) and keep.is_cuda and keep.data_ptr() != tensor.data_ptr():
+            # the device packer packs a device source where it lies, behind this call: a temporary copy made above must
+            # outlive that launch (the caller's own tensor is the caller's to keep until finalize)
+            self.synchronize()
         del keep
 
     def load_state_dict(self, state: Dict[str, object]):
@@ -329,6 +352,43 @@ class Context:
         self._check(self.lib.me_load_checkpoint_pt(self._h, os.fsencode(path)))
         n = self.lib.me_unused_weight_count(self._h)
         self.unused_keys = [self.lib.me_unused_weight_name(self._h, i).decode() for i in range(n)]
+
+    def set_weight_packer(self, who: str) -> None:
+        """resolve_weight_packer's "host" / "device" for this context's weight loads (me_ctx_set_weight_packer)"""
+        self._check(self.lib.me_ctx_set_weight_packer(self._h, 1 if resolve_weight_packer(who) == "device" else 0))
+
+    def weight_cache_path(self, checkpoint_path: str) -> str:
+        """The arena cache file's name for a checkpoint (me_weight_cache_path)"""
+        buf = C.create_string_buffer(len(os.fsencode(checkpoint_path)) + 64)
+        n = self.lib.me_weight_cache_path(self._h, os.fsencode(checkpoint_path), buf, len(buf))
+        if n < 0:
+            raise L.MatrixEyesError(1, "me_weight_cache_path failed")
+        return os.fsdecode(buf.value)
+
+    def save_weight_arena(self, path: str, source_path: Optional[str] = None) -> None:
+        self._check(self.lib.me_save_weight_arena(self._h, os.fsencode(path), os.fsencode(source_path) if source_path else None))
+
+    def load_weight_arena(self, path: str, source_path: Optional[str] = None) -> None:
+        self._check(self.lib.me_load_weight_arena(self._h, os.fsencode(path), os.fsencode(source_path) if source_path else None))
+
+    def load_checkpoint_cached(self, checkpoint_path: str, convert: bool = False) -> str:
+        """me_load_checkpoint_cached, the policy of --convert-checkpoints; returns where the weights came from: one of
+        WEIGHT_SOURCES"""
+        where = C.c_int32(-1)
+        self._check(self.lib.me_load_checkpoint_cached(self._h, os.fsencode(checkpoint_path), 1 if convert else 0, C.byref(where)))
+        self.unused_keys = []                      # the cache holds the arena only: the checkpoint's keys were not read
+        if where.value != 2:
+            n = self.lib.me_unused_weight_count(self._h)
+            self.unused_keys = [self.lib.me_unused_weight_name(self._h, i).decode() for i in range(n)]
+        return WEIGHT_SOURCES[where.value]
+
+    def last_weight_load(self):
+        """(report, ms) of me_last_weight_load: report a dict of where (one of WEIGHT_SOURCES), tensors, bytes_read,
+        bytes_uploaded; ms a dict of the five legs stage, upload, pack, finalize, cache_write"""
+        info, ms = (C.c_int64 * 4)(), (C.c_double * 5)()
+        self._check(self.lib.me_last_weight_load(self._h, info, ms))
+        return ({"where": WEIGHT_SOURCES[info[0]], "tensors": int(info[1]), "bytes_read": int(info[2]), "bytes_uploaded": int(info[3])},
+                dict(zip(("stage", "upload", "pack", "finalize", "cache_write"), (float(v) for v in ms))))
 
     def weight_arena_bytes(self) -> int:
         return int(self.lib.me_weight_arena_bytes(self._h))
@@ -636,7 +696,9 @@ class DepthProModelLoader:
     def __init__(self, checkpoint_path: Optional[str] = "./checkpoints/depth_pro.pt",
                  convert_checkpoints: bool = False, cfg: Optional[ModelConfig] = None):
         self.checkpoint_path = checkpoint_path
-        self.convert_checkpoints = convert_checkpoints  # .mpk cache: Burn-private, not produced
+        # mod.rs:211-247: the converted file is the packed weight arena, "<stem>-<dtype>-<layout hash>.mearena" beside the
+        # checkpoint (Context.load_checkpoint_cached); loaded whenever it is there and valid, written when this is set
+        self.convert_checkpoints = convert_checkpoints
         self.cfg = cfg or ModelConfig()
         self._ctx = None
 
@@ -653,13 +715,14 @@ class DepthProModelLoader:
 
     def context(self, device: int = 0, dtype: str = "f16") -> Context:
         if self._ctx is None:
-            ctx = Context(device, dtype, self.cfg)
+            ctx = Context(device, dtype, self.cfg, weight_packer=resolve_weight_packer())
             if self.checkpoint_path in (None, "synthetic") or os.environ.get("ME_TORCH_LOAD"):
                 ctx.load_state_dict(self._state_dict())
             else:
-                # the library maps and parses the .pt archive itself (me_load_checkpoint_pt); ME_TORCH_LOAD=1
+                # the arena cache beside the checkpoint if it is there and valid; otherwise the library maps and parses the
+                # .pt archive itself (me_load_checkpoint_pt) and, with convert_checkpoints, writes the cache; ME_TORCH_LOAD=1
                 # goes through torch.load instead
-                ctx.load_checkpoint_pt(self.checkpoint_path)
+                ctx.load_checkpoint_cached(self.checkpoint_path, self.convert_checkpoints)
             self._ctx = ctx
         return self._ctx
 

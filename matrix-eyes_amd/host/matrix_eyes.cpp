@@ -84,6 +84,8 @@ Device::Device() {
     }
     // acts only behind MATRIX_EYES_JPEG_DECODER=device: the host decoder has one entropy loop
     const bool device_jpeg_entropy = env_host_or_device("MATRIX_EYES_JPEG_ENTROPY", false);
+    // who packs the checkpoint's tensors into the weight arena (the same bytes either way)
+    const bool device_weight_packer = env_host_or_device("MATRIX_EYES_WEIGHT_PACKER", false);
     me_model_config cfg;
     me_default_config(&cfg);
     if (model && std::strcmp(model, "tiny") == 0) {
@@ -98,6 +100,7 @@ Device::Device() {
                                      &cfg, &ctx_);
     if (rc != ME_OK) throw ModelError(rc, std::string("cannot initialise the HIP device: ") + me_last_error(nullptr));
     if (device_jpeg_entropy && me_ctx_set_jpeg_entropy(ctx_, 1) != ME_OK) throw ModelError(ME_ERR_BAD_ARG, me_last_error(ctx_));
+    if (device_weight_packer && me_ctx_set_weight_packer(ctx_, 1) != ME_OK) throw ModelError(ME_ERR_BAD_ARG, me_last_error(ctx_));
 }
 
 Device::~Device() {
@@ -174,12 +177,12 @@ bool Device::load_decoded_resized(const std::string& path, bool with_orientation
 void DepthProModelLoader::ensure_loaded(const Device& device) const {
     if (device.weights_loaded_) return;
     me_ctx* ctx = device.ctx();
-    // mod.rs:229-249: the library reads the PyTorch archive itself; keys the model does not use are skipped
-    const int32_t rc = me_load_checkpoint_pt(ctx, checkpoint_path_.c_str());
+    // mod.rs:211-249: a valid arena cache beside the checkpoint is loaded instead of it; otherwise the library reads the
+    // PyTorch archive itself (keys the model does not use are skipped) and, with --convert-checkpoints, writes the cache
+    const int32_t rc = me_load_checkpoint_cached(ctx, checkpoint_path_.c_str(), convert_checkpoints_ ? 1 : 0, nullptr);
     if (rc == ME_ERR_IO)  // LoaderError::Pytorch
         throw ModelError(ME_ERR_IO, std::string("Model error: ") + me_last_error(ctx));
     check_model(ctx, rc, "failed to load checkpoint");
-    (void)convert_checkpoints_;
     device.weights_loaded_ = true;
 }
 

@@ -104,9 +104,10 @@ private:
 
 class DepthProModelLoader {
 public:
-    // convert_checkpoints: the reference caches a Burn-private .mpk next to the checkpoint (mod.rs:211-227);
-    // the packed weight arena lives in HBM for the life of the Device instead, so the flag is accepted and
-    // has nothing to do.
+    // convert_checkpoints: the reference caches a converted file next to the checkpoint and loads it on later runs
+    // (mod.rs:211-247); here that file is the packed weight arena (me_load_checkpoint_cached: "<stem>-<dtype>-<layout
+    // hash>.mearena", loaded whenever it is there and valid, written after loading when the flag is set).
+    // MATRIX_EYES_WEIGHT_PACKER=host|device: who packs the .pt's tensors when there is no cache (the same arena bytes).
     DepthProModelLoader(const std::string& checkpoint_path, bool convert_checkpoints)
         : checkpoint_path_(checkpoint_path), convert_checkpoints_(convert_checkpoints) {}
 
