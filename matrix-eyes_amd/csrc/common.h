@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/matrix_eyes_hip.h"
+#include "tile_choice.h"  // AMode, EpiKind, CFG_*, cdiv, seg_row_tiles: whatever a launch decision is stated in
 
 namespace me {
 
@@ -48,8 +49,6 @@ struct Error {
     do {                                            \
         if (!(cond)) ::me::fail((code), __VA_ARGS__); \
     } while (0)
-
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // Environment knobs: a switch that is on unless NAME=0, one that is off unless NAME is a non-zero number, a
 // number with a default.  Whether a knob is read once per process (`static const` at the site) or per call is the site's choice.
@@ -163,21 +162,7 @@ __device__ __forceinline__ void wait_vmcnt() {
 // W is always row-major [N][K], K contiguous (the PyTorch Linear layout; conv weights are
 // repacked to [Cout][tap][Cin] at load time).
 // ---------------------------------------------------------------------------------------
-enum AMode : int32_t {
-    A_PLAIN = 0,  // A row-major [M][lda]
-    A_CONV = 1    // A gathered from a zero-bordered NHWC map: row m = (b,y,x), k = (tap, cin)
-};
-
-enum EpiKind : int32_t {
-    EPI_STORE = 0,       // out32 [M][ldc] / out16 (row-major, or pixels of a zero-bordered NHWC
-                         // map when out16_border) = act(acc + bias + res32 + res32b)
-    EPI_RESID_SCALE = 1, // out32[m][n] = res32[m][n] + gamma[n]*(acc + bias[n])  (ViT proj / fc2)
-    EPI_PATCH_EMBED = 2, // out32[(m/P)*(P+1) + 1 + m%P][n] = acc + bias[n] + pos[1 + m%P][n]
-    EPI_CONVT = 4,       // ConvTranspose2d(2,2,s2) pixel shuffle: n = (dy*2+dx)*Cout + co
-    EPI_HEAD_FINAL = 5,  // relu(acc+bias) . w2 + b2 -> relu -> / f_norm -> clamp  (N <= 32)
-    EPI_HEAD_COMPOSED = 6 // the same behind the composed ConvTranspose o conv3x3 of the head (weights.hip compose_head): N = 4
-                          // output phases x 32 channels on the half-resolution map, out32 = the full-resolution depth
-};
+// AMode (A_PLAIN / A_CONV) and EpiKind (EPI_*): tile_choice.h
 
 enum Act : int32_t { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2 };
 
@@ -291,18 +276,9 @@ struct GemmParams {
 };
 constexpr int kGemmQueueWords = 9 * 32;
 
-// row tiles of a launch tiled per row segment (gemm_core.h seg_tile_rows; the 352-row tile)
-template <int BM>
-__host__ __device__ __forceinline__ int seg_row_tiles(int M, int seg1, int seg2) {
-    if (seg1 == 0) return (M + BM - 1) / BM;
-    const int e1 = seg2 ? seg2 : M;
-    return (seg1 + BM - 1) / BM + (e1 - seg1 + BM - 1) / BM + (seg2 ? (M - seg2 + BM - 1) / BM : 0);
-}
-
-
-// Tile configurations of gemm_launch (gemm.hip kCfgNames has their shapes).  The ids are what me_op_* take as tile_cfg.
-enum { CFG_PP256 = 0, CFG_128 = 1, CFG_64 = 2, CFG_160 = 3, CFG_RING64 = 4, CFG_PP192 = 5, CFG_8PH = 6, CFG_PP96 = 7,
-       CFG_RING128 = 8, CFG_HALO = 9, CFG_PP352 = 10, CFG_HALO12 = 11, CFG_HALO_N128 = 12, CFG_COUNT = 13 };
+// Tile configurations of gemm_launch: the CFG_* ids, what each is and admits, and every rule that picks one live in tile_choice.h.
+// The knobs those rules read, as the environment had them when the process first asked (gemm.hip).
+const TileKnobs& tile_knobs();
 // dtype: ME_DTYPE_F16 / ME_DTYPE_BF16.  Picks a tile configuration from (M, N, K) unless force_cfg names one.
 void gemm_launch(const GemmParams& p, AMode amode, EpiKind epi, int32_t dtype, hipStream_t stream,
                  int32_t force_cfg = -1);

@@ -59,58 +59,28 @@ ProfScope::~ProfScope() {
     if (index >= 0) (void)hipEventRecord(profiler().entries[index].e1, stream);
 }
 
-// Tile configurations by id (common.h CFG_*)
-static const char* kCfgNames[] = {"256x256x64/8w-pp", "128x128x64/4w", "64x64x64/4w", "160x128x64/4w",
-                                  "64x64x64/4w-ring6", "192x256x64/8w-pp", "256x256x64/8w-8ph", "96x256x64/8w-pp",
-                                  "128x256x64/8w-ring3", "16x16px-x256x64/8w-halo", "352x256x64/8w-pp", "12x16px-x256x64/8w-halo", "16x16px-x128x64/8w-halo"};
 int gemm_num_configs() { return CFG_COUNT; }
-const char* gemm_config_name(int cfg) { return cfg >= 0 && cfg < CFG_COUNT ? kCfgNames[cfg] : "?"; }
+const char* gemm_config_name(int cfg) { return cfg >= 0 && cfg < CFG_COUNT ? kTileConfigs[cfg].name : "?"; }
 
-// Tile choice.  The persistent kernels run ceil(tiles / resident workgroups) rounds, so the cost of a
-// configuration is rounds x (tile area) x (workgroups sharing a CU) / (its main-loop efficiency relative
-// to the two-group 256x256 kernel, measured at M = 80780 where rounds do not matter: profiles/
-// r01_kernel_microbench_f16.json).  Examples at M = 20195: qkv / fc1 (N = 3072 / 4096) -> 256x256 (4 and
-// 5 rounds); proj / fc2 (N = 1024) -> 160x128: 1016 tiles = 2 rounds of 512, where 128x128 needs 3 and
-// 256x256 leaves 3/4 of the second round idle; the 256-channel convolutions at 768^2 and 384^2 -> 256x256.
-// The 64x64 tile is for the single-window ViTs (M = 577) and the low-resolution decoder levels.
-static bool dynamic_tile_order() { static const bool on = getenv("ME_GEMM_DYNAMIC_TILES") != nullptr; return on; }
+// The knobs of tile_choice.h's rules, read once per process (ME_FP8_TALL is not among them: gemm_fp8.hip reads it per launch).
+const TileKnobs& tile_knobs() {
+    static const TileKnobs knobs = [] {
+        TileKnobs k;
+        k.dynamic_tiles = getenv("ME_GEMM_DYNAMIC_TILES") != nullptr;
+        k.conv_halo = env_on("ME_CONV_HALO"), k.conv_halo12 = env_on("ME_CONV_HALO12"), k.conv_halo128 = env_on("ME_CONV_HALO128");
+        k.tall = env_on("ME_GEMM_TALL");
+        k.tall_bias = getenv("ME_GEMM_TALL_BIAS") ? atof(getenv("ME_GEMM_TALL_BIAS")) : 0.95;
+        k.tail96 = env_on("ME_GEMM_TAIL96");
+        k.pp192 = getenv("ME_GEMM_PP192") != nullptr;
+        k.split_k = env_flag("ME_SPLIT_K");
+        k.split_k_min_k = env_int("ME_SPLIT_K_MINK", 4096);  // (the tests lower it: a tiny model has no K that deep)
+        return k;
+    }();
+    return knobs;
+}
 
-static int pick_config(int64_t M, int64_t N, int64_t K, int64_t seg1, int64_t seg2, bool resid) {
-    const int64_t t1 = cdiv(M, 128) * cdiv(N, 128);
-    if (N < 128 || t1 < 256) {
-        // few 64x64 tiles and a long K (the M = 577 fc2: 160 tiles x 64 slabs): the six-slot ring keeps
-        // five slabs in flight (33 -> 19 us); with many tiles its 96 KiB of LDS per workgroup costs more
-        // in occupancy than the latency it hides
-        return cdiv(M, 64) * cdiv(N, 64) <= 512 && K >= 2048 ? CFG_RING64 : CFG_64;
-    }
-    struct Cand {
-        int cfg, bm, bn, per_cu;
-        double eff;
-    };
-    // 192x256 (residual epilogue only): at M = 21760, N = 1024 it turns 340 tiles (1.33 rounds of 256) into 432 (1.69
-    // rounds).  Measured standalone: proj (K = 1024) 94.7 -> 80.3 us, fc2 (K = 4096) 229 -> 252 us -- the shorter
-    // tile moves 17 % more operand bytes per MFMA through L2 -> LDS and a K = 4096 main loop pays for that, a
-    // K = 1024 one is half epilogue and gains from the rounds.
-    const Cand cands[] = {{CFG_PP256, 256, 256, 1, 1.0},
-                          {CFG_PP192, 192, 256, 1, K <= 1024 ? 0.88 : 0.68},
-                          {CFG_160, 160, 128, 2, 0.80},
-                          {CFG_128, 128, 128, 2, 0.76}};
-    int best = CFG_128;
-    double best_cost = 0.0;
-    for (const Cand& c : cands) {
-        if (c.cfg == CFG_PP192 && !resid) continue;
-        if (N < c.bn || ((c.cfg == CFG_PP256 || c.cfg == CFG_PP192) && K < 128)) continue;
-        if (seg1 % c.bm || seg2 % c.bm) continue;  // row segments must start on tile boundaries
-        const int64_t tiles = cdiv(M, c.bm) * cdiv(N, c.bn);
-        // static order: whole rounds; dynamic order: workgroups draw tiles until none are left, so the
-        // launch takes the average share plus about half a tile of tail
-        const double rounds = dynamic_tile_order() && tiles > 256 * c.per_cu
-                                  ? (double)tiles / (256.0 * c.per_cu) + 0.5
-                                  : (double)cdiv(tiles, (int64_t)256 * c.per_cu);
-        const double cost = rounds * c.bm * c.bn * c.per_cu / c.eff;
-        if (best_cost == 0.0 || cost < best_cost) best = c.cfg, best_cost = cost;
-    }
-    return best;
+static TileProblem tile_problem(const GemmParams& p, AMode amode, EpiKind epi) {
+    return {p.M, p.N, p.K, p.seg1, p.seg2, amode, epi, p.KH, p.KW, p.stride, p.out_H, p.out_W, p.Cin, p.tap_bias != nullptr, p.ln_out16 != nullptr};
 }
 
 template <typename T>
@@ -240,7 +210,7 @@ void gemm_launch(const GemmParams& p_in, AMode amode, EpiKind epi, int32_t dtype
     // Dynamic tile order (TileQueue in gemm_core.h) is an opt-in: measured on the full step it gains 0.4 %
     // (26.57 vs 26.68 ms) -- the launches the side streams disturb most (proj / fc2) have two tiles per
     // workgroup, too coarse for a late workgroup to hand work to its neighbours.
-    p.queue = dynamic_tile_order() ? queue_for_stream(stream) : nullptr;
+    p.queue = tile_knobs().dynamic_tiles ? queue_for_stream(stream) : nullptr;
     p.status = current_status_word();
     p.gelu_per_granule = !env_on("ME_GELU_BATCH");  // (read per launch: the tests flip it inside one process)
     static const int patch_rows = env_int("ME_GEMM_PATCH_ROWS", 0);  // A/B knob
@@ -266,10 +236,10 @@ void gemm_launch(const GemmParams& p_in, AMode amode, EpiKind epi, int32_t dtype
                      p.N % 8 == 0 && !p.out32 && !p.res32 && !p.res32b && !p.lo_off16 && !p.hi2_off16 && p.act != ACT_GELU,
                  ME_ERR_BAD_ARG, "conv: per-tap bias shares take a 3x3 stride-1 convolution with a bordered 16-bit output and nothing else");
     if (p.ln_out16) {
-        ME_CHECK(force_cfg == CFG_PP352 && amode == A_PLAIN && epi == EPI_RESID_SCALE && (p.N == 256 || p.N == 512 || p.N == 1024) &&
-                     p.ldc == p.N && p.ln_w && p.ln_b && p.ln_stats && p.ln_count && p.bias && p.gamma && p.res32 && p.out32 &&
-                     p.K >= 128,
-                 ME_ERR_BAD_ARG, "gemm: the fused LayerNorm takes the 352-row tile's residual epilogue with N in {256, 512, 1024}");
+        // (that it runs on the 352-row tile's residual epilogue: tile_choice.h config_refusal, below)
+        ME_CHECK((p.N == 256 || p.N == 512 || p.N == 1024) && p.ldc == p.N && p.ln_w && p.ln_b && p.ln_stats && p.ln_count && p.bias &&
+                     p.gamma && p.res32 && p.out32,
+                 ME_ERR_BAD_ARG, "gemm: the fused LayerNorm takes N in {256, 512, 1024} with its weights, statistics and counters");
         ME_CHECK(p.seg1 == 0 || (p.ln_w_s1 && p.ln_b_s1 && (p.seg2 == 0 || (p.ln_w_s2 && p.ln_b_s2))), ME_ERR_BAD_ARG,
                  "gemm: a row segment without LayerNorm weights");
         // out8 beside ln_out16: the normalised rows leave as MX fp8 + activation-layout scales instead of 16-bit
@@ -281,45 +251,12 @@ void gemm_launch(const GemmParams& p_in, AMode amode, EpiKind epi, int32_t dtype
         ME_CHECK(epi == EPI_STORE && p.qcols % 64 == 0 && p.qcols <= p.N && p.out16 && !p.out32 && p.act == ACT_NONE &&
                      !p.lo_off16 && !p.hi2_off16,
                  ME_ERR_BAD_ARG, "gemm: scaled leading columns (qcols = %d) take a plain 16-bit output", p.qcols);
-    int cfg = force_cfg >= 0 ? force_cfg : pick_config(p.M, p.N, p.K, p.seg1, p.seg2, amode == A_PLAIN && epi == EPI_RESID_SCALE);
-    // 3x3 convolutions big enough for the 256x256 tile take its halo form (gemm_core.h conv_halo_kernel): the 18 x 18
-    // halo of a 16 x 16 pixel tile staged once per 64 input channels instead of the pixels once per tap
-    static const bool halo_on = env_on("ME_CONV_HALO");
-    const bool halo_fits = amode == A_CONV && epi == EPI_STORE && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.out_H % 16 == 0 &&
-                           p.out_W % 16 == 0 && p.N % 256 == 0;
-    if (force_cfg < 0 && halo_on && halo_fits && cfg == CFG_PP256) {
-        cfg = CFG_HALO;
-        // 12-row tiles where they fill the rounds better: a tile of 12 x 16 pixels costs about 0.78 of a 16 x 16 one
-        // (three quarters of the MFMAs, the same weight staging per slab)
-        static const bool halo12_on = env_on("ME_CONV_HALO12");
-        if (halo12_on && p.out_H % 12 == 0) {
-            const int64_t nbn = p.N / 256, t16 = (int64_t)(p.M / 256) * nbn, t12 = (int64_t)(p.M / 192) * nbn;
-            if ((double)cdiv(t12, 256) * 0.78 < (double)cdiv(t16, 256) * 0.97) cfg = CFG_HALO12;
-        }
-    }
-    if (cfg == CFG_HALO) ME_CHECK(halo_fits, ME_ERR_BAD_SHAPE, "conv: the halo tile takes 3x3 stride-1 convolutions on maps of 16-pixel multiples, N a multiple of 256");
-    // N = 128 (the head's first convolution, 256 -> 128 at 768 x 768): the halo tile with 128 channels where the
-    // 128x128 implicit-GEMM tile would have been chosen on a map of at least a round of pixel tiles
-    const bool halo128_fits = amode == A_CONV && epi == EPI_STORE && p.KH == 3 && p.KW == 3 && p.stride == 1 &&
-                              p.out_H % 16 == 0 && p.out_W % 16 == 0 && p.N % 128 == 0;
-    static const bool halo128_on = env_on("ME_CONV_HALO128");
-    if (force_cfg < 0 && halo_on && halo128_on && halo128_fits && p.N % 256 != 0 && cfg == CFG_128 &&
-        (int64_t)(p.M / 256) * (p.N / 128) >= 256)
-        cfg = CFG_HALO_N128;
-    if (cfg == CFG_HALO_N128)
-        ME_CHECK(halo128_fits, ME_ERR_BAD_SHAPE, "conv: the 128-channel halo tile takes 3x3 stride-1 convolutions on maps of 16-pixel multiples, N a multiple of 128");
-    if (cfg == CFG_HALO12)
-        ME_CHECK(amode == A_CONV && epi == EPI_STORE && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.out_H % 12 == 0 &&
-                     p.out_W % 16 == 0 && p.N % 256 == 0,
-                 ME_ERR_BAD_SHAPE, "conv: the 12-row halo tile takes 3x3 stride-1 convolutions on maps of 12 x 16 pixel multiples, N a multiple of 256");
-    if ((cfg == CFG_PP256 || cfg == CFG_PP192 || cfg == CFG_8PH || cfg == CFG_PP96 || cfg == CFG_PP352) && p.K < 128) cfg = CFG_128;  // they prefetch two slabs ahead
-    {
-        // (the 352-row tile lays its row tiles out per segment, gemm_core.h seg_tile_rows: any boundary will do)
-        static const int kTileRows[CFG_COUNT] = {256, 128, 64, 160, 64, 192, 256, 96, 128, 256, 1, 1, 256};
-        const int bm = epi == EPI_HEAD_FINAL ? 256 : kTileRows[cfg];
-        ME_CHECK(p.seg1 % bm == 0 && p.seg2 % bm == 0 && (p.seg2 == 0 || p.seg2 > p.seg1), ME_ERR_BAD_ARG,
-                 "gemm: row segments %d / %d do not start on %d-row tile boundaries", p.seg1, p.seg2, bm);
-    }
+    // which tile, and whether it takes this problem (tile_choice.h): nothing is launched on a refusal
+    const TileProblem problem = tile_problem(p, amode, epi);
+    const int cfg = resolve_config(problem, force_cfg, tile_knobs());
+    if (const TileRefusal no = config_refusal(problem, cfg); no.kind != TILE_OK)
+        fail(no.kind == TILE_BAD_SHAPE ? ME_ERR_BAD_SHAPE : ME_ERR_BAD_ARG, "gemm: tile config %d (%s), %s M=%d N=%d K=%d, row segments %d / %d: %s", cfg,
+             gemm_config_name(cfg), amode == A_CONV ? "conv" : "plain", p.M, p.N, p.K, p.seg1, p.seg2, no.why);
     static const char* kEpi[] = {"store", "resid_scale", "patch_embed", "?", "convt", "head_final"};
     // the head's final layers on a halo tile (head_conv.hip) where the shape is the model's own; force_cfg >= 0 or
     // ME_HEAD_HALO=0: the implicit-GEMM tile below

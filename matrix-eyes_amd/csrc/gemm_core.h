@@ -2656,73 +2656,53 @@ void gemm_launch_ring(const GemmParams& p, hipStream_t stream) {
 template <typename T, int AMODE, int EPI>
 void gemm_dispatch(const GemmParams& p, int cfg, hipStream_t stream);
 
-#define ME_GEMM_DISPATCH_BODY(T, AMODE, EPI)                                              \
-    template <>                                                                           \
-    void gemm_dispatch<T, AMODE, EPI>(const GemmParams& p, int cfg, hipStream_t stream) { \
-        switch (cfg) {                                                                    \
-            case 0: gemm_launch_pp<T, 256, 256, 2, 4, AMODE, EPI>(p, stream); break;       \
-            case 1:                                                                       \
-                if constexpr (EPI == EPI_STORE) {                                         \
-                    if (p.split_k > 1) {                                                  \
-                        gemm_launch_cfg<T, 128, 128, 2, 2, AMODE, EPI, true>(p, stream);  \
-                        break;                                                            \
-                    }                                                                     \
-                }                                                                         \
-                gemm_launch_cfg<T, 128, 128, 2, 2, AMODE, EPI>(p, stream);                \
-                break;                                                                    \
-            case 2: gemm_launch_cfg<T, 64, 64, 2, 2, AMODE, EPI>(p, stream); break;       \
-            case 3: gemm_launch_cfg<T, 160, 128, 2, 2, AMODE, EPI>(p, stream); break;     \
-            case 4: gemm_launch_ring<T, 64, 64, 2, 2, 6, AMODE, EPI>(p, stream); break;    \
-            case 5: gemm_launch_pp<T, 192, 256, 2, 4, AMODE, EPI>(p, stream); break;       \
-            case 7: /* short tail tile behind whole rounds of config 0 (pipeline.hip resid_all) */ \
-                if constexpr (EPI == EPI_STORE || EPI == EPI_RESID_SCALE)                \
-                    gemm_launch_pp<T, 96, 256, 1, 8, AMODE, EPI>(p, stream);              \
-                else                                                                      \
-                    fail(ME_ERR_BAD_ARG, "gemm: the 96-row tile takes store / residual epilogues only"); \
-                break;                                                                    \
-            case 8: /* the same, three ring slots: two slabs in flight behind a short tile's few MFMAs */ \
-                if constexpr (EPI == EPI_STORE || EPI == EPI_RESID_SCALE)                \
-                    gemm_launch_ring<T, 128, 256, 2, 4, 3, AMODE, EPI>(p, stream);        \
-                else                                                                      \
-                    fail(ME_ERR_BAD_ARG, "gemm: the 128-row ring tile takes store / residual epilogues only"); \
-                break;                                                                    \
-            case 9:                                                                       \
-                if constexpr (AMODE == A_CONV && EPI == EPI_STORE)                        \
-                    conv_halo_launch<T, EPI>(p, stream);                                  \
-                else                                                                      \
-                    fail(ME_ERR_BAD_ARG, "gemm: the halo tile is a 3x3 convolution");     \
-                break;                                                                    \
-            case 12: /* the halo tile with 128 output channels (the head's 256 -> 128 convolution at 768 x 768) */ \
-                if constexpr (AMODE == A_CONV && EPI == EPI_STORE)                        \
-                    conv_halo_launch<T, EPI, 16, 128>(p, stream);                         \
-                else                                                                      \
-                    fail(ME_ERR_BAD_ARG, "gemm: the halo tile is a 3x3 convolution");     \
-                break;                                                                    \
-            case 11: /* the halo tile on 12 x 16 pixels (three full rounds of a 384 x 384 map instead of 2.25) */ \
-                if constexpr (AMODE == A_CONV && EPI == EPI_STORE)                        \
-                    conv_halo_launch<T, EPI, 12>(p, stream);                              \
-                else                                                                      \
-                    fail(ME_ERR_BAD_ARG, "gemm: the halo tile is a 3x3 convolution");     \
-                break;                                                                    \
-            case 10: /* 352-row two-group tile, two weight slots: one exact round where 256-row tiles leave a tail */ \
-                if constexpr (AMODE == A_PLAIN && EPI == EPI_RESID_SCALE) {                \
-                    if (p.ln_out16)                                                       \
-                        gemm_launch_pp<T, 352, 256, 2, 4, AMODE, EPI, 2, true>(p, stream); \
-                    else                                                                  \
-                        gemm_launch_pp<T, 352, 256, 2, 4, AMODE, EPI, 2>(p, stream);      \
-                } else if constexpr (AMODE == A_PLAIN && EPI == EPI_STORE)                \
-                    gemm_launch_pp<T, 352, 256, 2, 4, AMODE, EPI, 2>(p, stream);          \
-                else                                                                      \
-                    fail(ME_ERR_BAD_ARG, "gemm: the 352-row tile takes plain linears with store / residual epilogues only"); \
-                break;                                                                    \
-            case 6:                                                                       \
-                if constexpr (AMODE == A_PLAIN && (EPI == EPI_STORE || EPI == EPI_RESID_SCALE))   \
-                    gemm_launch_8ph<T, EPI>(p, stream);                                   \
-                else                                                                      \
-                    fail(ME_ERR_BAD_ARG, "gemm: the 8-phase configuration takes plain linears only"); \
-                break;                                                                    \
-            default: fail(ME_ERR_BAD_ARG, "gemm: bad tile config %d", cfg);               \
-        }                                                                                 \
+// One arm per configuration; tile_choice.h kTileConfigs[id].admits says which (A-mode, epilogue) pairs an arm is compiled for.  The arms
+// stand in the order in which the configurations were added, not in id order: the compiler emits the kernels into the code object in
+// the order the arms instantiate them, and reordering them reorders (and so changes) the device code of all four gemm_*.hip objects.
+// gemm_launch has asked config_refusal before it comes here, so the refusal below the switch is not reached: it is what the arms that
+// are not compiled fall through to.
+#define ME_TILE_ARM(ID, ...)                                 \
+    case ID:                                                 \
+        if constexpr (tile_admits(ID, kAMode, kEpi)) {       \
+            __VA_ARGS__;                                     \
+            return;                                          \
+        }                                                    \
+        break;
+#define ME_GEMM_DISPATCH_BODY(T, AMODE, EPI)                                                                            \
+    template <>                                                                                                         \
+    void gemm_dispatch<T, AMODE, EPI>(const GemmParams& p, int cfg, hipStream_t stream) {                               \
+        constexpr int kAMode = AMODE, kEpi = EPI; /* (what ME_TILE_ARM asks the table about) */                         \
+        switch (cfg) {                                                                                                  \
+            ME_TILE_ARM(CFG_PP256, gemm_launch_pp<T, 256, 256, 2, 4, AMODE, EPI>(p, stream))                            \
+            ME_TILE_ARM(CFG_128, if constexpr (EPI == EPI_STORE) {                                                      \
+                if (p.split_k > 1) {                                                                                    \
+                    gemm_launch_cfg<T, 128, 128, 2, 2, AMODE, EPI, true>(p, stream);                                    \
+                    return;                                                                                             \
+                }                                                                                                       \
+            } gemm_launch_cfg<T, 128, 128, 2, 2, AMODE, EPI>(p, stream))                                                \
+            ME_TILE_ARM(CFG_64, gemm_launch_cfg<T, 64, 64, 2, 2, AMODE, EPI>(p, stream))                                \
+            ME_TILE_ARM(CFG_160, gemm_launch_cfg<T, 160, 128, 2, 2, AMODE, EPI>(p, stream))                             \
+            ME_TILE_ARM(CFG_RING64, gemm_launch_ring<T, 64, 64, 2, 2, 6, AMODE, EPI>(p, stream))                        \
+            ME_TILE_ARM(CFG_PP192, gemm_launch_pp<T, 192, 256, 2, 4, AMODE, EPI>(p, stream))                            \
+            /* short tail tile behind whole rounds of CFG_PP256 (pipeline.hip launch_with_short_tail) */                \
+            ME_TILE_ARM(CFG_PP96, gemm_launch_pp<T, 96, 256, 1, 8, AMODE, EPI>(p, stream))                              \
+            /* the same, three ring slots: two slabs in flight behind a short tile's few MFMAs */                       \
+            ME_TILE_ARM(CFG_RING128, gemm_launch_ring<T, 128, 256, 2, 4, 3, AMODE, EPI>(p, stream))                     \
+            ME_TILE_ARM(CFG_HALO, conv_halo_launch<T, EPI>(p, stream))                                                  \
+            /* the halo tile with 128 output channels (the head's 256 -> 128 convolution at 768 x 768) */               \
+            ME_TILE_ARM(CFG_HALO_N128, conv_halo_launch<T, EPI, 16, 128>(p, stream))                                    \
+            /* the halo tile on 12 x 16 pixels (three full rounds of a 384 x 384 map instead of 2.25) */                \
+            ME_TILE_ARM(CFG_HALO12, conv_halo_launch<T, EPI, 12>(p, stream))                                            \
+            /* 352-row two-group tile, two weight slots: one exact round where 256-row tiles leave a tail */             \
+            ME_TILE_ARM(CFG_PP352, if constexpr (EPI == EPI_RESID_SCALE) {                                              \
+                if (p.ln_out16) {                                                                                       \
+                    gemm_launch_pp<T, 352, 256, 2, 4, AMODE, EPI, 2, true>(p, stream);                                  \
+                    return;                                                                                             \
+                }                                                                                                       \
+            } gemm_launch_pp<T, 352, 256, 2, 4, AMODE, EPI, 2>(p, stream))                                              \
+            ME_TILE_ARM(CFG_8PH, gemm_launch_8ph<T, EPI>(p, stream))                                                    \
+        }                                                                                                               \
+        fail(ME_ERR_BAD_ARG, "gemm: tile config %d is not compiled for (A-mode %d, epilogue %d)", cfg, (int)AMODE, (int)EPI); \
     }
 
 }  // namespace me

@@ -548,20 +548,6 @@ static void launch_pp8t(const GemmParams& p, hipStream_t stream) {
     ME_HIP(hipGetLastError());
 }
 
-// The 352-row tile where its rounds x 352 undercut the 256-row tile's rounds x 256 (pipeline.hip tall_tile_wins, without the
-// short-tail form the fp8 path does not have); ME_FP8_TALL=0 turns it off, =1 forces it.
-static bool fp8_tall_wins(const GemmParams& p) {
-    const int knob = env_int("ME_FP8_TALL", -1);  // (read per launch: the tests flip it inside one process)
-    if (knob == 0) return false;
-    if (knob == 1) return true;
-    const int64_t nbn = p.N / 256;
-    const double cost352 = (double)cdiv((int64_t)seg_row_tiles<352>(p.M, p.seg1, p.seg2) * nbn, 256) * 352.0;
-    const double cost256 = (double)cdiv(cdiv(p.M, 256) * nbn, 256) * 256.0;
-    // a row of the tall tile costs about a tenth more (weights one slab ahead instead of two): fc1 at one image -- four rounds
-    // of 352 against six of 256, 1408 : 1536 -- measured 3.40 against 3.33 ms per step on the 256-row tile
-    return cost352 * 1.1 < cost256;
-}
-
 // fp8 x fp8 GEMM.  p.A / p.W: e4m3 bytes, p.lda in bytes; p.a_scale / p.w_scale (+ _s1 / _s2) in the layouts
 // above with p.a_mt = (rows padded to 128) / 128.  epi: EPI_STORE (16-bit output in f16, or fp8 + scales into
 // p.out8 / p.out8_scale when out8) or EPI_RESID_SCALE.
@@ -600,7 +586,9 @@ void gemm_fp8_launch(const GemmParams& p_in, EpiKind epi, hipStream_t stream) {
             ME_CHECK(p.out8_scale && (int64_t)p.out8_mt * 128 >= p.M, ME_ERR_BAD_ARG,
                      "fp8 gemm: the fused LayerNorm's fp8 output needs its block scales (%d tiles of 128 rows for %d rows)", p.out8_mt, p.M);
     }
-    const bool tall = lnf || !whole256 || fp8_tall_wins(p);
+    // the 352-row tile where the 256-row one cannot run, or where tile_choice.h rates it cheaper (ME_FP8_TALL read per launch: the tests flip it
+    // inside one process)
+    const bool tall = lnf || !whole256 || fp8_tall_wins(p.M, p.N, p.seg1, p.seg2, env_int("ME_FP8_TALL", -1));
     if (tall) {
         p.cu_granted = stream_cu_count(stream);
         p.ln_spin_limit = gemm_ln_spin_limit();

@@ -63,37 +63,19 @@ void from_device(me_ctx* ctx, void* dst, const void* src_dev, size_t bytes) {
 
 namespace {
 
-// ME_GEMM_TALL=0: no 352-row tile (tall_tile_wins), and with it no fused LayerNorm (ln_fusable)
-bool tall_tile_enabled() { static const bool on = env_on("ME_GEMM_TALL"); return on; }
-// ME_GEMM_PP192: the 192-row tile for proj (resid_all's A/B), which the fused LayerNorm does not have
-bool pp192_selected() { static const bool on = getenv("ME_GEMM_PP192") != nullptr; return on; }
-
-// ---- thin launch helpers: the descriptors come from gemm_params.h, the launch decisions are made here ----
-// Deterministic split-K for the small deep launches of the tail (gemm_core.h gemm_kernel<..., SPLITK>; VERDICT r4
-// "missing" 6): a launch whose image has fewer than 200 tiles of 128 x 128 and K >= ME_SPLIT_K_MINK (4096) runs on that tile with
-// S work items per tile, S the largest power of two that keeps the launch within 640 work items and a K range of at least 512.
-// Decided from ONE image's rows, so a batch takes the decision of its images (a batch stays a loop of batch-one calls bit for
-// bit).  OFF unless ME_SPLIT_K=1: measured, the two K = 9216 convolutions it applies to gain 0.02 ms per step together, and with
-// a lower K bound (the 96 x 96 level's 3x3 convolutions, the upsample chains' 1x1) the partials' round trip through memory costs
-// more than the longer K loop it replaces (+0.15 ms at K >= 2048).
-// Returns the tile configuration to force (1) or -1.
+// ---- thin launch helpers: the descriptors come from gemm_params.h, the launch decisions from tile_choice.h ----
+// Deterministic split-K for the small deep launches of the tail (tile_choice.h split_k_factor): the workspace of the launch.
+// Returns the tile configuration to force (CFG_128) or -1.
 int maybe_split_k(me_ctx* ctx, GemmParams& p, int64_t rows_per_image, hipStream_t s) {
-    static const bool on = env_flag("ME_SPLIT_K");
-    static const int min_k = env_int("ME_SPLIT_K_MINK", 4096);  // (the tests lower it: a tiny model has no K that deep)
-    if (!on || rows_per_image <= 0 || p.K < min_k) return -1;
-    const int64_t tiles_img = cdiv(rows_per_image, 128) * cdiv((int64_t)p.N, 128);
-    if (tiles_img >= 200) return -1;
-    int S = 1;
-    while (S < 8 && tiles_img * (S * 2) <= 640 && p.K / (S * 2) >= 512) S *= 2;
+    const int S = split_k_factor(rows_per_image, p.M, p.N, p.K, tile_knobs());
     if (S == 1) return -1;
     const int64_t tiles = cdiv((int64_t)p.M, 128) * cdiv((int64_t)p.N, 128);
-    if (tiles > 4096) return -1;
     // one workspace per stream (launches of one stream follow one another; a second stream must not share it)
     const std::string tag = "splitk." + std::to_string((uintptr_t)s);
     p.split_k = S;
     p.splitk_ws = (float*)site_buf(ctx, tag + ".ws", (size_t)tiles * S * 128 * 128 * 4);   // grows to the largest launch
     p.splitk_cnt = (unsigned*)site_buf(ctx, tag + ".cnt", 4096 * 4);   // zero when allocated; the last arriver of a tile resets its word
-    return 1;
+    return CFG_128;
 }
 
 // out = act(A[M][K] . W[N][K]^T + bias) as 16-bit and/or f32 rows of N (split operands, model.h SplitStage: a_split: A holds
@@ -325,25 +307,10 @@ struct MergedVit {
         segs.w1 = w1, segs.b1 = b1, segs.w2 = w2, segs.b2 = b2;
     }
 
-    // Whole rounds + a short tail.  A persistent 256x256 launch runs ceil(tiles / 256) rounds, and at one image the last
-    // round of fc1 (1360 tiles: 5.31 rounds) and of proj / fc2 (340 tiles: 1.33 rounds) is a third full.  The main loops
-    // are bound by what a CU can stage into LDS per slab ((BM + BN) x 128 bytes at ~50 GB/s per CU), not by the MFMAs,
-    // so a 96x256 tile costs 0.69 of a 256x256 tile's main loop and 0.375 of its epilogue: when the last round is at
-    // most half full, its rows run as a SECOND launch of 96-row tiles (tile config 7; <= 256 of them, one short round
-    // in which every workgroup has a tile) behind the whole rounds.  The rows of the second launch all belong to the
-    // last row segment.  Results are bit-identical (same K order per output element).  Measured at one image, FOV head:
-    // proj 93.7 -> 82.7 us, fc2 211.7 -> 207.7 us stand-alone (profiles/r03_tail_tile_ab.txt); in the step, same box,
-    // alternating runs: 25.17 ms (off) -> 24.90 (proj / fc2 split) -> 24.70 (fc1 too).  ME_GEMM_TAIL96=0 turns it off.
-    bool launch_with_short_tail(const GemmParams& p, EpiKind epi) {
-        static const bool enabled = env_on("ME_GEMM_TAIL96");
-        if (!enabled || p.N % 256 || p.M % 256 || p.K < 128) return false;
-        const int64_t nbn = p.N / 256;
-        if (256 % nbn) return false;
-        const int64_t per_round = 256 / nbn, row_tiles = p.M / 256;      // row tiles per round of 256 workgroups
-        const int64_t rounds = row_tiles / per_round, rem = row_tiles % per_round;
-        const int64_t rows1 = rounds * per_round * 256, rows2 = p.M - rows1;
-        const int64_t last_seg = p.seg2 ? p.seg2 : p.seg1;
-        if (rounds < 1 || rem == 0 || 2 * rem > per_round || cdiv(rows2, 96) * nbn > 256 || rows1 < last_seg) return false;
+    // Whole rounds + a short tail (tile_choice.h short_tail_rows1): the first rows1 rows on the 256x256 tile, the rest -- all of the last
+    // row segment -- as a second launch of 96-row tiles with that segment's weights
+    void launch_with_short_tail(const GemmParams& p, EpiKind epi, int64_t rows1) {
+        const int64_t rows2 = p.M - rows1;
         GemmParams a = p, b = p;
         a.M = (int)rows1;
         a.flop_rows = (int)std::min<int64_t>(real_rows(), rows1);
@@ -358,28 +325,6 @@ struct MergedVit {
         else if (p.seg1) b.W = p.W_s1, b.bias = p.bias_s1, b.gamma = p.gamma_s1;
         gemm_launch(a, A_PLAIN, epi, ctx->dtype, s, CFG_PP256);
         gemm_launch(b, A_PLAIN, epi, ctx->dtype, s, CFG_PP96);
-        return true;
-    }
-
-    // The 352-row tile (tile config 10).  256 CUs x one tile each cover 64 x 352 = 22528 rows of an N = 1024 launch: at
-    // one image proj / fc2 are ONE exact round (3 + 3 + 58 row tiles x 4 = 256 tiles) instead of a round of 256x256
-    // tiles and a second launch of short tiles that the CU cannot stage fast enough (1.375 tile-times against 1 + 0.69),
-    // and fc1 is four rounds instead of five and a tail.  Chosen when its rounds x 352 undercut what the 256-row path
-    // costs (whole rounds x 256, + 0.69 x 256 for a short tail or a whole round where no tail applies).
-    // ME_GEMM_TALL=0 turns it off.
-    bool tall_tile_wins(const GemmParams& p) const {
-        if (!tall_tile_enabled() || p.N % 256 || p.K < 128 || ctx->C() < 256) return false;
-        const int64_t nbn = p.N / 256;
-        const int64_t tiles352 = (int64_t)seg_row_tiles<352>(p.M, p.seg1, p.seg2) * nbn;
-        const int64_t tiles256 = cdiv(p.M, 256) * nbn;
-        const double cost352 = (double)cdiv(tiles352, 256) * 352.0;
-        const int64_t whole = tiles256 / 256, rem = tiles256 % 256;
-        const bool short_tail = whole >= 1 && rem != 0 && 2 * rem <= 256 && 256 % nbn == 0;
-        const double cost256 = ((double)whole + (rem == 0 ? 0.0 : (short_tail ? 0.69 : 1.0))) * 256.0;
-        // a near-tie goes to the tall tile: qkv's 768 tall tiles (three exact rounds, 1056) against 1020 tiles of
-        // 256 x 256 (3.98 rounds, 1024) measured 0.5 % faster in the step (23.27 -> 23.16 ms, three alternating runs)
-        static const double bias = getenv("ME_GEMM_TALL_BIAS") ? atof(getenv("ME_GEMM_TALL_BIAS")) : 0.95;
-        return cost352 * bias < cost256;
     }
 
     // the weights of block i's three physical segments: one linear's members of VitBlockW (gamma: the residual forms)
@@ -400,14 +345,9 @@ struct MergedVit {
         set_segments(p, seg1, seg2, w);
         set_scaled_cols(p, qcols, kAttnQScale);  // qkv: Q leaves scaled for the attention kernel
         p.flop_rows = (int)real_rows();
-        // fc1 at one image: five whole rounds + 224 short tiles instead of a sixth round a third full (qkv's 1020 tiles
-        // are 3.98 rounds and N = 3072 does not divide the round: launch_with_short_tail declines)
-        if (tall_tile_wins(p)) {
-            gemm_launch(p, A_PLAIN, EPI_STORE, ctx->dtype, s, CFG_PP352);
-            return;
-        }
-        if (ctx->C() >= 256 && launch_with_short_tail(p, EPI_STORE)) return;
-        gemm_launch(p, A_PLAIN, EPI_STORE, ctx->dtype, s);
+        const VitLinearPlan plan = vit_linear_plan(p.M, N, K, seg1, seg2, ctx->C(), false, false, false, tile_knobs());
+        if (plan.kind == VIT_ROUNDS_TAIL) launch_with_short_tail(p, EPI_STORE, plan.rows1);
+        else gemm_launch(p, A_PLAIN, EPI_STORE, ctx->dtype, s, plan.cfg);
     }
     // ... or the residual update x += gamma * (A W^T + b) (proj, fc2).  On the two-group 256x256 tile: the
     // patch encoder's rows alone take 160x128 (two exact rounds), but with the small segments' 24 tiles more
@@ -420,7 +360,7 @@ struct MergedVit {
     bool ln_fusable(bool fp8_gemm) const {
         static const bool enabled = env_on("ME_LN_FUSE");
         const int C = ctx->C();
-        if (!(enabled && tall_tile_enabled() && !pp192_selected() && (C == 256 || C == 512 || C == 1024))) return false;
+        if (!(enabled && tile_knobs().tall && !tile_knobs().pp192 && (C == 256 || C == 512 || C == 1024))) return false;
         // the context has seen the exchange time out (api.hip run_with_ln_fallback): stand-alone LayerNorm from then on
         if (ctx->ln_fuse_off) return false;
         // one row tile per XCD with all its column tiles must be resident at once on the CUs the stream may use
@@ -434,24 +374,13 @@ struct MergedVit {
         GemmParams p = resid_params(Rtot, C, K, A, nullptr, nullptr, nullptr, tok);
         set_segments(p, seg1, seg2, w);
         p.flop_rows = (int)real_rows();
-        // the two-group 256x256 kernel (the cost model rates 128x128 a hair cheaper here; measured it is not).  Its
-        // 192-row form (tile config 5; the segment order above makes every boundary a multiple of 192 at one image)
-        // wins for proj stand-alone (94.7 -> 80.3 us) and loses in the step (90 -> 95.6 us per launch, same box,
-        // bench.py A/B): ME_GEMM_PP192=1 selects it for that comparison.
-        const bool pp = C >= 256 && K >= 128;
-        const bool pp192 = pp && K <= 1024 && pp192_selected() && seg1 % 192 == 0 && seg2 % 192 == 0;
-        if (ln && pp && ln_fusable(false) && (ln_fp8 || !ctx->fp8)) {
+        const bool ln_wanted = ln && (ln_fp8 || !ctx->fp8);
+        const VitLinearPlan plan = vit_linear_plan(p.M, C, K, seg1, seg2, C, true, ln_wanted, ln_wanted && ln_fusable(false), tile_knobs());
+        if (plan.kind == VIT_FUSED_LN_352)
             set_fused_layernorm(ctx, p, "vitm.ln.stats", "vitm.ln.count", *ln, ctx->cfg.ln_eps, xn, ln_fp8 ? (uint8_t*)xn : nullptr, xn_s);
-            gemm_launch(p, A_PLAIN, EPI_RESID_SCALE, ctx->dtype, s, CFG_PP352);
-            return true;
-        }
-        if (pp && !pp192 && tall_tile_wins(p)) {
-            gemm_launch(p, A_PLAIN, EPI_RESID_SCALE, ctx->dtype, s, CFG_PP352);
-            return false;
-        }
-        if (pp && !pp192 && launch_with_short_tail(p, EPI_RESID_SCALE)) return false;
-        gemm_launch(p, A_PLAIN, EPI_RESID_SCALE, ctx->dtype, s, pp192 ? CFG_PP192 : (pp ? CFG_PP256 : -1));
-        return false;
+        if (plan.kind == VIT_ROUNDS_TAIL) launch_with_short_tail(p, EPI_RESID_SCALE, plan.rows1);
+        else gemm_launch(p, A_PLAIN, EPI_RESID_SCALE, ctx->dtype, s, plan.cfg);
+        return plan.kind == VIT_FUSED_LN_352;
     }
 
     // the MX fp8 form of gemm_all / resid_all (gemm_fp8.hip): A = xn or hid as e4m3 + block scales

@@ -977,3 +977,125 @@ def test_head_final(dtype, case):
     for cfg, got in outs.items():
         assert float((got - ref).abs().max()) < 2e-5 * scale, (cfg, float((got - ref).abs().max()), scale)
     assert float((outs[-1] - outs[2]).abs().max()) < 2e-5 * scale
+
+
+def test_refused_tile_configs_report_and_launch_nothing():
+    """Every me_op_* entry that takes tile_cfg, at the smallest legal shape (M = N = K = 64; an 8 x 8 map with Cin = 64), with each
+    id the table of csrc/tile_choice.h does not admit for it (tests/tile_choice_cases.py ADMITS / TWO_SLAB / HALO_IDS: the same
+    table, which tests/test_tile_choice_cpu.py holds the header to), with CFG_COUNT, and with -2.  A refusal is a host check before
+    any launch: the entry returns the table's code -- ME_ERR_BAD_SHAPE from a halo tile's shape rule, ME_ERR_BAD_ARG for a pair
+    the id is not compiled for and for an id out of range -- and the output keeps its fill.  What the rules let pass runs: K < 128
+    moves a two-slab id to the 128x128 tile before the table is asked, the head's final layers are one kernel whatever id is
+    forced (so only the halo ids' shape rule refuses them), a negative id is the automatic choice.  Then the same context runs
+    every entry on the automatic choice and gives the bits it gave before the refusals."""
+    import ctypes as C
+    from tile_choice_cases import (A_CONV, A_PLAIN, ADMITS, CFG_128, CFG_COUNT, EPI_CONVT, EPI_HEAD_FINAL, EPI_PATCH_EMBED,
+                                   EPI_RESID_SCALE, EPI_STORE, HALO_IDS, TWO_SLAB)
+    BAD_ARG, BAD_SHAPE = 1, 2
+    ctx = ctx_for("tiny", "f16")
+    lib, h = ctx.lib, ctx.handle
+    M = N = K = 64
+    B, H, W, Cin, Cout = 1, 8, 8, 64, 64
+    g = torch.Generator().manual_seed(64)
+    a = dev16(torch.randn(M, K, generator=g), "f16")
+    w = dev16(torch.randn(N, K, generator=g) / 8, "f16")
+    bias, gamma = torch.randn(N, generator=g).cuda(), torch.rand(N, generator=g).cuda()
+    x = torch.randn(B, Cin, H, W, generator=g)
+    wc = torch.randn(Cout, Cin, 3, 3, generator=g) / 24
+    xb, wc16 = bordered(x, "f16"), dev16(pack_conv(wc), "f16")
+    x16 = dev16(x.permute(0, 2, 3, 1).reshape(B * H * W, Cin), "f16")
+    wt16 = dev16(pack_convt(torch.randn(Cin, 16, 2, 2, generator=g) / 8), "f16")
+    wh16 = dev16(pack_conv(torch.randn(32, Cin, 3, 3, generator=g) / 24), "f16")
+    w2, b2 = torch.randn(32, generator=g).cuda(), torch.tensor([0.4]).cuda()
+    patches = dev16(torch.randn(64, 768, generator=g), "f16")
+    wp = dev16(torch.randn(64, 768, generator=g) / 28, "f16")
+    pos = torch.randn(65, 64, generator=g).cuda()
+    arr = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() if t is not None else None for t in ts])
+    f32 = lambda *shape: torch.full(shape, 7.0, dtype=torch.float32, device="cuda")
+    f16 = lambda *shape: torch.full(shape, 7.0, dtype=torch.float16, device="cuda")
+    # name -> (A-mode, epilogue, K, output, call(output, tile_cfg))
+    entries = {
+        "linear": (A_PLAIN, EPI_STORE, K, f32(M, N),
+                   lambda o, c: lib.me_op_linear(h, M, N, K, ptr(a), ptr(w), ptr(bias), None, ptr(o), 0, c)),
+        "linear_residual": (A_PLAIN, EPI_RESID_SCALE, K, f32(M, N),
+                            lambda o, c: lib.me_op_linear_residual(h, M, N, K, ptr(a), ptr(w), ptr(bias), ptr(gamma), ptr(o), c)),
+        "linear_scaled_cols": (A_PLAIN, EPI_STORE, K, f16(M, N),
+                               lambda o, c: lib.me_op_linear_scaled_cols(h, M, N, K, ptr(a), ptr(w), ptr(bias), ptr(o), 64, 0.125, c)),
+        "linear_split": (A_PLAIN, EPI_STORE, K, f16(M, 2 * N),
+                         lambda o, c: lib.me_op_linear_split(h, M, N, K, ptr(a), ptr(w), ptr(bias), ptr(o), None, 0, c)),
+        "linear_segments": (A_PLAIN, EPI_STORE, K, f16(M, N),
+                            lambda o, c: lib.me_op_linear_segments(h, M, N, K, ptr(a), 0, 0, arr([w, None, None]), arr([bias, None, None]),
+                                                                   None, ptr(o), None, 0, c)),
+        "conv2d": (A_CONV, EPI_STORE, 9 * Cin, f32(B * H * W, Cout),
+                   lambda o, c: lib.me_op_conv2d(h, ptr(xb), B, H, W, Cin, ptr(wc16), Cout, 3, 1, ptr(bias), None, None, ptr(o), None, 0, 0,
+                                                 0, c)),
+        "conv2d_forms": (A_CONV, EPI_STORE, 9 * Cin, f32(B * H * W, Cout),
+                         lambda o, c: lib.me_op_conv2d_forms(h, ptr(xb), B, H, W, Cin, ptr(wc16), Cout, 3, 1, ptr(bias), None, None, ptr(o),
+                                                             None, 0, 1, 0, 0, c)),
+        "head_final": (A_CONV, EPI_HEAD_FINAL, 9 * Cin, f32(B * H * W),
+                       lambda o, c: lib.me_op_head_final(h, ptr(xb), B, H, W, Cin, ptr(wh16), 32, ptr(bias), ptr(w2), ptr(b2), None,
+                                                         -float("inf"), float("inf"), ptr(o), c)),
+        "conv_transpose2x2": (A_PLAIN, EPI_CONVT, Cin, f32(B * 2 * H * 2 * W, 16),
+                              lambda o, c: lib.me_op_conv_transpose2x2(h, ptr(x16), B, H, W, Cin, ptr(wt16), 16, ptr(bias), ptr(o), None, 0, c)),
+        "conv_transpose2x2_forms": (A_PLAIN, EPI_CONVT, Cin, f32(B * 2 * H * 2 * W, 16),
+                                    lambda o, c: lib.me_op_conv_transpose2x2_forms(h, ptr(x16), B, H, W, Cin, ptr(wt16), 16, ptr(bias), ptr(o),
+                                                                                   None, 0, 0, 0, 0, 0, c)),
+        "patch_embed": (A_PLAIN, EPI_PATCH_EMBED, 768, f32(65, 64),
+                        lambda o, c: lib.me_op_patch_embed(h, ptr(patches), 1, 64, 64, ptr(wp), ptr(bias), ptr(pos), ptr(o), c)),
+    }
+
+    def code_of(amode, epi, k, cfg):
+        """the table's answer for a forced id on this entry's problem: 0 when it runs"""
+        if cfg < 0:
+            return 0
+        if cfg in HALO_IDS:       # no entry here is a 3x3 convolution on a map of 16 x 16 or 12 x 16 pixel tiles
+            return BAD_SHAPE
+        if (amode, epi) == (A_CONV, EPI_HEAD_FINAL):
+            return 0
+        if cfg >= CFG_COUNT:
+            return BAD_ARG
+        cfg = CFG_128 if cfg in TWO_SLAB and k < 128 else cfg
+        return 0 if (amode, epi) in ADMITS[cfg] else BAD_ARG
+
+    def automatic(name):
+        amode, epi, k, out, call = entries[name]
+        got = torch.full_like(out, 7.0)
+        torch.cuda.synchronize()
+        _check(ctx, call(got, -1))
+        ctx.synchronize()
+        return got
+
+    before = {name: automatic(name) for name in entries}
+    # the automatic choice is right to begin with (each entry's own test has the tolerances: f32 accumulation over K <= 768)
+    ref = a.double() @ w.double().T + bias.double()
+    assert max_abs_rel(before["linear"], ref) < 2e-5
+    assert max_abs_rel(before["linear_residual"], 7.0 + gamma.double() * ref) < 2e-5
+    xc = xb[:, 1:H + 1, 1:W + 1, :].permute(0, 3, 1, 2).double().cpu()
+    refc = F.conv2d(xc, dev16(wc, "f16").double().cpu(), bias.double().cpu(), padding=1).permute(0, 2, 3, 1).reshape(B * H * W, Cout)
+    assert max_abs_rel(before["conv2d"].cpu(), refc) < 3e-5
+    for name, got in before.items():
+        rows = got[1:] if name == "patch_embed" else got        # (row 0 of a window is the class token's: not this launch's)
+        assert not bool((rows == 7.0).any()), name
+
+    refused = 0
+    for name, (amode, epi, k, out, call) in entries.items():
+        torch.cuda.synchronize()
+        for cfg in list(range(CFG_COUNT)) + [CFG_COUNT, -2]:
+            want = code_of(amode, epi, k, cfg)
+            if want == 0 and cfg not in (CFG_COUNT, -2):
+                continue                                        # an admitted id: the entries' own tests run those
+            rc = call(out, cfg)
+            assert rc == want, (name, cfg, rc, want, lib.me_last_error(h))
+            if want:
+                assert lib.me_last_error(h)
+                refused += 1
+                continue
+            ctx.synchronize()                                   # -2, or the head's one kernel under an id beyond the table: it ran
+            assert float((out - before[name]).abs().max()) <= 2e-5 * float(before[name].abs().max()), (name, cfg)
+            out.fill_(7.0)
+            torch.cuda.synchronize()
+        ctx.synchronize()
+        assert bool((out == 7.0).all()), name                   # no refused call wrote a byte
+    assert refused >= 3 * len(entries)
+    for name in entries:
+        assert torch.equal(automatic(name), before[name]), name

@@ -590,8 +590,8 @@ np.save(sys.argv[2], d)
 
 def test_tile_choices_change_no_bit(tmp_path):
     """The three ways proj / fc2 / fc1 of one image can run -- ONE round of 352-row tiles laid out per row segment
-    (pipeline.hip tall_tile_wins, the default), whole rounds of 256x256 + a second launch of 96x256 tiles over the
-    remaining rows (launch_with_short_tail; ME_GEMM_TALL=0), single 256x256 launches (and ME_GEMM_TAIL96=0) -- keep
+    (csrc/tile_choice.h tall_tile_wins, the default), whole rounds of 256x256 + a second launch of 96x256 tiles over the
+    remaining rows (short_tail_rows1 / launch_with_short_tail; ME_GEMM_TALL=0), single 256x256 launches (and ME_GEMM_TAIL96=0) -- keep
     the same K order per output element: the full-size depth is bit for bit the same, with the LayerNorm launched on
     its own everywhere (ME_LN_FUSE=0).  LayerNorm inside the tall tile's residual epilogue (ME_LN_FUSE=1) sums a row's
     statistics in another order (1e-7 relative): a handful of 16-bit roundings fall the other way in the first block,
@@ -762,7 +762,7 @@ np.save(sys.argv[2], d)
 
 def test_split_k_tail_launches_are_deterministic(tmp_path):
     """The deep, small launches of the decoder / upsample tail as tile x K-range work items (gemm_core.h gemm_kernel<..., SPLITK>,
-    pipeline.hip maybe_split_k): every work item writes its f32 partial, the LAST arriver of a tile sums them in split order.
+    csrc/tile_choice.h split_k_factor, pipeline.hip maybe_split_k): every work item writes its f32 partial, the LAST arriver of a tile sums them in split order.
     Opt-in (ME_SPLIT_K=1: it does not pay); the test lowers its K bound so that a tiny model has such launches.
     Repeated runs and a batch against its images give the same bits (inside the child); against ME_SPLIT_K=0 only the order of
     the f32 sums differs -- which moves 16-bit operand roundings downstream, so the two maps differ like any two correct 16-bit

@@ -27,7 +27,7 @@ PASSES = [["FETCH_SIZE"], ["WRITE_SIZE"], ["SQ_VALU_MFMA_BUSY_CYCLES", "GRBM_GUI
           ["SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_ANY"], ["SQ_LDS_BANK_CONFLICT", "SQ_LDS_IDX_ACTIVE"],
           ["TCC_HIT_sum", "TCC_MISS_sum"], ["TCC_REQ_sum", "TCC_EA0_RDREQ_sum"]]
 # the launches of one step at one image: qkv / fc1 / proj / fc2 on the 352-row tile (config 10: three / four / one exact
-# rounds, pipeline.hip tall_tile_wins); the 3x3 convolutions on the halo tile (config 9).
+# rounds, tile_choice.h tall_tile_wins); the 3x3 convolutions on the halo tile (config 9).
 # The round-3 short-tail launches (ME_GEMM_TALL=0) stay selectable: fc1_tail:7 proj_tail:7 fc2_tail:7 with fc1:0 ...
 DEFAULT = ["qkv_tall:10", "fc1_tall:10", "proj_tall:10", "fc2_tall:10", "conv768:9", "attn:0"]
 CFG_NAMES = {0: "256x256x64/8w-pp", 1: "128x128x64/4w", 2: "64x64x64/4w", 3: "160x128x64/4w", 4: "64x64x64/4w-ring6",
@@ -58,7 +58,7 @@ def describe(op, cfg):
         resid = op == "fc2_8"
         out = PROBE_M * n * (8 if resid else (2 if op == "qkv8" else 1 + 1 / 32))
         bytes_ = PROBE_M * k * (1 + 1 / 32) + n * k * (1 + 1 / 32) + out + n * 4 * (2 if resid else 1)
-        # (fc2 at one image runs on the 352-row tile, gemm_fp8.hip fp8_tall_wins; the probe launches the plain residual form)
+        # (fc2 at one image runs on the 352-row tile, tile_choice.h fp8_tall_wins; the probe launches the plain residual form)
         return f"gemm_kernel<fp8,{'352' if resid else '256'}x256x128/8w-pp,plain,{'resid_scale' if resid else 'store'}>", int(bytes_)
     if op == "conv768":   # 16-bit bordered input, weights, f32 residual in, f32 + 16-bit out
         px = 768 * 768
