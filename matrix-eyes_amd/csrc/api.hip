@@ -1,14 +1,13 @@
 // extern "C" boundary of libmatrixeyes_hip.so (include/matrix_eyes_hip.h, matrix_eyes_hip_ops.h).
 // Every entry point converts internal me::Error into a status code + last_error text (model.h
 // ME_API_BEGIN / ME_API_END); nothing throws or aborts across the boundary.  The raster and file
-// entries of the output back end are in output_api.hip.
+// entries of the output back end are in output_api.hip, the photo-input entries in input_api.hip.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
 
 #include "../../include/matrix_eyes_hip_ops.h"
-#include "../host/image_io.hpp"
 #include "gemm_params.h"
 #include "mx_fp8.h"
 
@@ -93,6 +92,8 @@ void check_pending_status(me_ctx* ctx) {
 }  // namespace
 
 namespace me {
+std::string& create_error() { return g_create_error; }
+
 OutBuf out_buf(me_ctx* ctx, void* user, size_t bytes, const std::string& name) {
     OutBuf o;
     o.user = user, o.bytes = bytes;
@@ -901,280 +902,6 @@ int32_t me_depth_clamp_minmax_async(me_ctx* ctx, float* depth, int64_t count, fl
              "me_depth_clamp_minmax_async: depth and minmax_dev must be device memory");
     depth_clamp_minmax_launch(depth, count, minmax_dev, ctx->stream);
     ME_API_END(ctx)
-}
-
-int32_t me_resize_lanczos3_rgb8(me_ctx* ctx, const uint8_t* src, int32_t w, int32_t h, uint8_t* dst, int32_t nw,
-                                int32_t nh) {
-    ME_API_BEGIN(ctx)
-    ME_CHECK(src && dst, ME_ERR_BAD_ARG, "me_resize_lanczos3_rgb8: null pointer");
-    check_resize_shape("me_resize_lanczos3_rgb8", w, h, nw, nh);
-    const size_t nin = (size_t)w * h * 3, nout = (size_t)nw * nh * 3;
-    const uintptr_t a = (uintptr_t)src, b = (uintptr_t)dst;
-    ME_CHECK(a + nin <= b || b + nout <= a, ME_ERR_BAD_ARG, "me_resize_lanczos3_rgb8: src and dst overlap");
-    const uint8_t* s = (const uint8_t*)to_device(ctx, src, nin, "resample.src");
-    OutBuf o = out_buf(ctx, dst, nout, "resample.dst");
-    resize_lanczos3_rgb8(ctx, s, w, h, (uint8_t*)o.dev, nw, nh);
-    finish(ctx, o);
-    ME_API_END(ctx)
-}
-
-// ---- JPEG decoding (jpeg_decode.hip) -------------------------------------------------------------------------------
-int32_t me_jpeg_info(const uint8_t* file, int64_t nbytes, int32_t* width, int32_t* height, int64_t* exif_offset,
-                     int64_t* exif_nbytes) {
-    if (!file || nbytes < 0 || !width || !height || !exif_offset || !exif_nbytes) {
-        g_create_error = "me_jpeg_info: null pointer";
-        return ME_ERR_BAD_ARG;
-    }
-    try {
-        const std::vector<uint8_t> bytes(file, file + nbytes);
-        const matrix_eyes::JpegCoefficients head = matrix_eyes::parse_jpeg_header(bytes, "<jpeg>");
-        *width = head.width, *height = head.height;
-        *exif_offset = (int64_t)head.exif_offset, *exif_nbytes = (int64_t)head.exif_nbytes;
-    } catch (const std::exception& e) {
-        g_create_error = e.what();
-        return ME_ERR_BAD_ARG;
-    }
-    return ME_OK;
-}
-
-int32_t me_op_jpeg_decode_host(const uint8_t* file, int64_t nbytes, uint8_t* rgb, int32_t w, int32_t h) {
-    if (!file || nbytes < 0 || !rgb) return -1;
-    try {
-        const std::vector<uint8_t> bytes(file, file + nbytes);
-        const matrix_eyes::RgbImage img = matrix_eyes::decode_jpeg(bytes, "<jpeg>", nullptr);
-        if ((int64_t)img.width != w || (int64_t)img.height != h) return -2;
-        std::memcpy(rgb, img.data.data(), img.data.size());
-    } catch (const std::exception&) {
-        return -3;
-    }
-    return 0;
-}
-
-namespace {
-void check_jpeg_args(const char* who, const uint8_t* file, int64_t nbytes, int32_t orientation, const void* dst) {
-    ME_CHECK(file && dst && nbytes >= 0, ME_ERR_BAD_ARG, "%s: null pointer", who);
-    ME_CHECK(orientation >= 1 && orientation <= 8, ME_ERR_BAD_ARG, "%s: orientation %d outside 1..8", who, orientation);
-    ME_CHECK(!is_device_ptr(file), ME_ERR_BAD_ARG, "%s: the file's bytes must be in host memory (they are parsed there)", who);
-}
-}  // namespace
-
-int32_t me_jpeg_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t orientation, uint8_t* rgb, int32_t w,
-                            int32_t h) {
-    ME_API_BEGIN(ctx)
-    check_jpeg_args("me_jpeg_decode_rgb8", file, nbytes, orientation, rgb);
-    ME_CHECK(w > 0 && h > 0, ME_ERR_BAD_SHAPE, "me_jpeg_decode_rgb8: %dx%d", w, h);
-    const size_t nout = (size_t)w * h * 3;
-    const bool dev = is_device_ptr(rgb);
-    int32_t ow = 0, oh = 0;
-    uint8_t* d = jpeg_decode_rgb8(ctx, file, nbytes, orientation, dev ? rgb : nullptr, w, h, &ow, &oh);
-    if (!dev) {
-        ME_HIP(hipMemcpyAsync(rgb, d, nout, hipMemcpyDeviceToHost, ctx->stream));
-        ME_HIP(hipEventRecord(ctx->jpeg_ev[4], ctx->stream));
-        ctx->jpeg_timed_download = true;
-        ME_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    ME_API_END(ctx)
-}
-
-int32_t me_jpeg_decode_resized_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t orientation, uint8_t* dst,
-                                    int32_t nw, int32_t nh) {
-    ME_API_BEGIN(ctx)
-    check_jpeg_args("me_jpeg_decode_resized_rgb8", file, nbytes, orientation, dst);
-    ME_CHECK(nw > 0 && nh > 0 && nw <= ME_RESIZE_MAX_DIM && nh <= ME_RESIZE_MAX_DIM, ME_ERR_BAD_SHAPE,
-             "me_jpeg_decode_resized_rgb8: -> %dx%d", nw, nh);
-    {
-        int32_t fw = 0, fh = 0;  // the file's size before anything is decoded: the resampler's bound
-        int64_t eo = 0, en = 0;
-        if (me_jpeg_info(file, nbytes, &fw, &fh, &eo, &en) != ME_OK) fail(ME_ERR_BAD_ARG, "%s", g_create_error.c_str());
-        check_resize_shape("me_jpeg_decode_resized_rgb8", fw, fh, nw, nh);
-    }
-    int32_t ow = 0, oh = 0;
-    const uint8_t* full = jpeg_decode_rgb8(ctx, file, nbytes, orientation, nullptr, 0, 0, &ow, &oh);
-    OutBuf o = out_buf(ctx, dst, (size_t)nw * nh * 3, "jpeg.resized");
-    resize_lanczos3_rgb8(ctx, full, ow, oh, (uint8_t*)o.dev, nw, nh);
-    finish(ctx, o);
-    ME_API_END(ctx)
-}
-
-// ---- PNG decoding (png_decode.hip) ---------------------------------------------------------------------------------
-int32_t me_png_info(const uint8_t* file, int64_t nbytes, int32_t* width, int32_t* height, int64_t* exif_offset,
-                    int64_t* exif_nbytes) {
-    if (!file || nbytes < 0 || !width || !height || !exif_offset || !exif_nbytes) {
-        g_create_error = "me_png_info: null pointer";
-        return ME_ERR_BAD_ARG;
-    }
-    try {
-        const std::vector<uint8_t> bytes(file, file + nbytes);
-        const matrix_eyes::PngFrame head = matrix_eyes::parse_png_header(bytes, "<png>");
-        *width = (int32_t)head.width, *height = (int32_t)head.height;
-        *exif_offset = (int64_t)head.exif_offset, *exif_nbytes = (int64_t)head.exif_nbytes;
-    } catch (const std::exception& e) {
-        g_create_error = e.what();
-        return ME_ERR_BAD_ARG;
-    }
-    return ME_OK;
-}
-
-int32_t me_op_png_decode_host(const uint8_t* file, int64_t nbytes, uint8_t* rgb, int32_t w, int32_t h) {
-    if (!file || nbytes < 0 || !rgb) return -1;
-    try {
-        const std::vector<uint8_t> bytes(file, file + nbytes);
-        const matrix_eyes::RgbImage img = matrix_eyes::decode_png(bytes, "<png>", nullptr);
-        if ((int64_t)img.width != w || (int64_t)img.height != h) return -2;
-        std::memcpy(rgb, img.data.data(), img.data.size());
-    } catch (const std::exception& e) {
-        g_create_error = e.what();
-        return -3;
-    }
-    return 0;
-}
-
-int32_t me_png_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t orientation, uint8_t* rgb, int32_t w,
-                           int32_t h) {
-    ME_API_BEGIN(ctx)
-    check_jpeg_args("me_png_decode_rgb8", file, nbytes, orientation, rgb);
-    ME_CHECK(w > 0 && h > 0, ME_ERR_BAD_SHAPE, "me_png_decode_rgb8: %dx%d", w, h);
-    const size_t nout = (size_t)w * h * 3;
-    const bool dev = is_device_ptr(rgb);
-    int32_t ow = 0, oh = 0;
-    uint8_t* d = png_decode_rgb8(ctx, file, nbytes, orientation, dev ? rgb : nullptr, w, h, &ow, &oh);
-    if (!dev) {
-        ME_HIP(hipMemcpyAsync(rgb, d, nout, hipMemcpyDeviceToHost, ctx->stream));
-        ME_HIP(hipEventRecord(ctx->png_ev[3 * (size_t)ctx->png_timed_bands + 2], ctx->stream));
-        ctx->png_timed_download = true;
-        ME_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    ME_API_END(ctx)
-}
-
-int32_t me_png_decode_resized_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t orientation, uint8_t* dst,
-                                   int32_t nw, int32_t nh) {
-    ME_API_BEGIN(ctx)
-    check_jpeg_args("me_png_decode_resized_rgb8", file, nbytes, orientation, dst);
-    ME_CHECK(nw > 0 && nh > 0 && nw <= ME_RESIZE_MAX_DIM && nh <= ME_RESIZE_MAX_DIM, ME_ERR_BAD_SHAPE,
-             "me_png_decode_resized_rgb8: -> %dx%d", nw, nh);
-    {
-        int32_t fw = 0, fh = 0;  // the file's size before anything is inflated: the resampler's bound
-        int64_t eo = 0, en = 0;
-        if (me_png_info(file, nbytes, &fw, &fh, &eo, &en) != ME_OK) fail(ME_ERR_BAD_ARG, "%s", g_create_error.c_str());
-        check_resize_shape("me_png_decode_resized_rgb8", fw, fh, nw, nh);
-    }
-    int32_t ow = 0, oh = 0;
-    const uint8_t* full = png_decode_rgb8(ctx, file, nbytes, orientation, nullptr, 0, 0, &ow, &oh);
-    OutBuf o = out_buf(ctx, dst, (size_t)nw * nh * 3, "png.resized");
-    resize_lanczos3_rgb8(ctx, full, ow, oh, (uint8_t*)o.dev, nw, nh);
-    finish(ctx, o);
-    ME_API_END(ctx)
-}
-
-int32_t me_last_png_timing(me_ctx* ctx, double ms_out[5]) {
-    ME_API_BEGIN(ctx)
-    ME_CHECK(ms_out, ME_ERR_BAD_ARG, "me_last_png_timing: null pointer");
-    ME_CHECK(ctx->png_timed, ME_ERR_NOT_READY, "me_last_png_timing: no PNG decode has completed on this context");
-    ME_HIP(hipStreamSynchronize(ctx->stream));
-    ms_out[0] = ctx->png_inflate_ms;
-    for (int i = 1; i < 5; ++i) ms_out[i] = 0.0;
-    auto between = [&](size_t a, size_t b) {
-        float ms = 0.f;
-        ME_HIP(hipEventElapsedTime(&ms, ctx->png_ev[a], ctx->png_ev[b]));
-        return (double)ms;
-    };
-    const size_t bands = (size_t)ctx->png_timed_bands;
-    for (size_t i = 0; i < bands; ++i) ms_out[1] += between(3 * i, 3 * i + 1), ms_out[2] += between(3 * i + 1, 3 * i + 2);
-    ms_out[3] = between(3 * bands, 3 * bands + 1);
-    if (ctx->png_timed_download) ms_out[4] = between(3 * bands + 1, 3 * bands + 2);
-    ME_API_END(ctx)
-}
-
-int32_t me_op_png_unfilter(me_ctx* ctx, const uint8_t* stream, int64_t nbytes, int32_t width, int32_t height, int32_t bit_depth,
-                           int32_t colour_type, int32_t interlace, int32_t band_rows, uint8_t* out) {
-    ME_API_BEGIN(ctx)
-    ME_CHECK(stream && out && nbytes >= 0, ME_ERR_BAD_ARG, "me_op_png_unfilter: null pointer");
-    ME_CHECK(width > 0 && height > 0 && (int64_t)width * height <= matrix_eyes::kMaxPixels, ME_ERR_BAD_SHAPE, "me_op_png_unfilter: %dx%d",
-             width, height);
-    const bool depth_ok = bit_depth == 1 || bit_depth == 2 || bit_depth == 4 || bit_depth == 8 || bit_depth == 16;
-    ME_CHECK(depth_ok && me_pngdec::channels_of(colour_type) && !(bit_depth < 8 && colour_type != 0 && colour_type != 3) &&
-                 !(bit_depth == 16 && colour_type == 3) && (interlace == 0 || interlace == 1) && band_rows >= 0,
-             ME_ERR_BAD_ARG, "me_op_png_unfilter: depth %d, colour type %d, interlace %d, band_rows %d", bit_depth, colour_type, interlace,
-             band_rows);
-    const me_pngdec::Geom g = me_pngdec::make_geom(width, height, bit_depth, colour_type, interlace);
-    ME_CHECK(nbytes == g.total, ME_ERR_BAD_SHAPE, "me_op_png_unfilter: the stream of this picture has %lld bytes, not %lld",
-             (long long)g.total, (long long)nbytes);
-    if (!is_device_ptr(stream))   // a filter byte above 4 never reaches the kernel
-        for (int ps = 0; ps < g.npass; ++ps)
-            for (int32_t py = 0; g.pass[ps].pw && py < g.pass[ps].ph; ++py)
-                ME_CHECK(stream[g.pass[ps].offset + (int64_t)py * ((int64_t)g.pass[ps].stride + 1)] <= 4, ME_ERR_BAD_ARG,
-                         "me_op_png_unfilter: bad PNG filter");
-    const uint8_t* s = (const uint8_t*)to_device(ctx, stream, (size_t)nbytes, "png.op.in");
-    OutBuf o = out_buf(ctx, out, (size_t)nbytes, "png.op.out");
-    png_unfilter(ctx, s, (uint8_t*)o.dev, width, height, bit_depth, colour_type, interlace, band_rows);
-    finish(ctx, o);
-    ME_API_END(ctx)
-}
-
-int32_t me_last_jpeg_timing(me_ctx* ctx, double ms_out[5]) {
-    ME_API_BEGIN(ctx)
-    ME_CHECK(ms_out, ME_ERR_BAD_ARG, "me_last_jpeg_timing: null pointer");
-    ME_CHECK(ctx->jpeg_timed, ME_ERR_NOT_READY, "me_last_jpeg_timing: no JPEG decode has completed on this context");
-    ME_HIP(hipStreamSynchronize(ctx->stream));
-    ms_out[0] = ctx->jpeg_entropy_ms;
-    for (int i = 0; i < 4; ++i) {
-        float ms = 0.f;
-        if (i < 3 || ctx->jpeg_timed_download) ME_HIP(hipEventElapsedTime(&ms, ctx->jpeg_ev[i], ctx->jpeg_ev[i + 1]));
-        ms_out[1 + i] = ms;
-    }
-    ME_API_END(ctx)
-}
-
-int32_t me_ctx_set_jpeg_entropy(me_ctx* ctx, int32_t mode) {
-    ME_API_BEGIN(ctx)
-    ME_CHECK(mode == 0 || mode == 1, ME_ERR_BAD_ARG, "me_ctx_set_jpeg_entropy: mode %d (0 host, 1 device)", mode);
-    ctx->jpeg_entropy_mode = mode;
-    ME_API_END(ctx)
-}
-
-int32_t me_last_jpeg_entropy(me_ctx* ctx, int64_t report[8], double ms[3]) {
-    ME_API_BEGIN(ctx)
-    ME_CHECK(report && ms, ME_ERR_BAD_ARG, "me_last_jpeg_entropy: null pointer");
-    ME_CHECK(ctx->jpeg_timed || ctx->jpeg_entropy_reported, ME_ERR_NOT_READY,
-             "me_last_jpeg_entropy: no JPEG decode has completed on this context");
-    // a decode that never tried the device (mode 0) reports the host, with nothing else to say
-    const JpegEntropyReport r = ctx->jpeg_entropy_reported ? ctx->jpeg_entropy_report : JpegEntropyReport();
-    report[0] = r.where, report[1] = r.reason, report[2] = r.segments, report[3] = r.subseqs, report[4] = r.subseq_bits;
-    report[5] = r.rounds, report[6] = r.upload_bytes, report[7] = r.workgroups;
-    for (int i = 0; i < 3; ++i) ms[i] = r.ms[i];
-    ME_API_END(ctx)
-}
-
-int32_t me_op_jpeg_entropy(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t subseq_bits, int16_t* coef,
-                           int64_t count) {
-    ME_API_BEGIN(ctx)
-    ME_CHECK(file && coef && nbytes >= 0, ME_ERR_BAD_ARG, "me_op_jpeg_entropy: null pointer");
-    ME_CHECK(!is_device_ptr(file), ME_ERR_BAD_ARG, "me_op_jpeg_entropy: the file's bytes must be in host memory");
-    const std::vector<uint8_t> bytes(file, file + nbytes);
-    matrix_eyes::JpegEntropyPlan plan;
-    if (!jpeg_entropy_decode(ctx, bytes, subseq_bits, plan)) {
-        ctx->last_error = "me_op_jpeg_entropy: declined, reason " + std::to_string(ctx->jpeg_entropy_report.reason) +
-                          (plan.why.empty() ? "" : " (" + plan.why + ")");
-        return ME_OP_JPEG_ENTROPY_DECLINED;
-    }
-    ME_CHECK(count == (int64_t)plan.frame.total_coefs, ME_ERR_BAD_SHAPE, "me_op_jpeg_entropy: the file has %zu coefficients, not %lld",
-             plan.frame.total_coefs, (long long)count);
-    from_device(ctx, coef, site_buf(ctx, "jpeg.coef", (size_t)count * sizeof(int16_t)), (size_t)count * sizeof(int16_t));
-    ME_API_END(ctx)
-}
-
-int32_t me_op_jpeg_coefficients_host(const uint8_t* file, int64_t nbytes, int16_t* coef, int64_t count) {
-    if (!file || nbytes < 0 || !coef) return -1;
-    try {
-        const std::vector<uint8_t> bytes(file, file + nbytes);
-        const matrix_eyes::JpegCoefficients c = matrix_eyes::decode_jpeg_coefficients(bytes, "<jpeg>");
-        if ((int64_t)c.total_coefs != count) return -2;
-        std::memcpy(coef, c.comps[0].coef, (size_t)count * sizeof(int16_t));
-    } catch (const std::exception&) {
-        return -3;
-    }
-    return 0;
 }
 
 int32_t me_mesh_index(me_ctx* ctx, const float* depth, int32_t width, int32_t height,

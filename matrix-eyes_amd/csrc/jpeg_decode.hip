@@ -116,24 +116,7 @@ __global__ __launch_bounds__(256) void jpeg_finish_kernel(const Frame f, const u
 }
 
 // pinned memory for the entropy decoder (JpegCoefAlloc): the upload of the call before may still be reading the buffer
-int16_t* pinned_coefficients(void* user, size_t count) {
-    me_ctx* ctx = (me_ctx*)user;
-    if (!ctx->jpeg_uploaded) {
-        ME_HIP(hipEventCreateWithFlags(&ctx->jpeg_uploaded, hipEventDisableTiming));
-        for (hipEvent_t& e : ctx->jpeg_ev) ME_HIP(hipEventCreate(&e));
-    }
-    if (ctx->jpeg_upload_pending) {
-        ME_HIP(hipEventSynchronize(ctx->jpeg_uploaded));
-        ctx->jpeg_upload_pending = false;
-    }
-    if (count > ctx->jpeg_pinned_count) {
-        if (ctx->jpeg_pinned) ME_HIP(hipHostFree(ctx->jpeg_pinned));
-        ctx->jpeg_pinned = nullptr, ctx->jpeg_pinned_count = 0;
-        ME_HIP(hipHostMalloc((void**)&ctx->jpeg_pinned, count * sizeof(int16_t), hipHostMallocDefault));
-        ctx->jpeg_pinned_count = count;
-    }
-    return ctx->jpeg_pinned;
-}
+int16_t* pinned_coefficients(void* user, size_t count) { return jpeg_pinned_buffer((me_ctx*)user, count); }
 
 // frame geometry, upsampling modes and colour handling of Decoder::finish, and the tables of Decoder::idct_all
 void plan(const matrix_eyes::JpegCoefficients& c, int32_t orientation, Frame& f, IdctTables& tab, size_t& plane_bytes) {
@@ -167,19 +150,11 @@ void plan(const matrix_eyes::JpegCoefficients& c, int32_t orientation, Frame& f,
 
 }  // namespace
 
-int16_t* jpeg_pinned_buffer(me_ctx* ctx, size_t count) { return pinned_coefficients(ctx, count); }
-
 void free_jpeg_scratch(me_ctx* ctx) {
     free_jpeg_entropy_scratch(ctx);
     free_jpeg_encode_scratch(ctx);
-    if (ctx->jpeg_pinned) (void)hipHostFree(ctx->jpeg_pinned);
-    ctx->jpeg_pinned = nullptr, ctx->jpeg_pinned_count = 0;
-    if (ctx->jpeg_uploaded) (void)hipEventDestroy(ctx->jpeg_uploaded);
-    ctx->jpeg_uploaded = nullptr;
-    for (hipEvent_t& e : ctx->jpeg_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
+    ctx->jpeg_upload.release();
+    ctx->jpeg_marks.destroy();
 }
 
 uint8_t* jpeg_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t orientation, uint8_t* dst_dev,
@@ -193,11 +168,7 @@ uint8_t* jpeg_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int3
     try {
         // the size first: a caller's buffer of another size is refused before any decoding
         const matrix_eyes::JpegCoefficients head = matrix_eyes::parse_jpeg_header(bytes, name);
-        const bool swap = orientation >= 5;
-        *ow = swap ? head.height : head.width, *oh = swap ? head.width : head.height;
-        ME_CHECK((want_w <= 0 && want_h <= 0) || (want_w == *ow && want_h == *oh), ME_ERR_BAD_SHAPE,
-                 "JPEG decode: the picture is %dx%d (orientation %d), the destination %dx%d", *ow, *oh, orientation, want_w,
-                 want_h);
+        oriented_size_or_refuse("JPEG", head.width, head.height, orientation, want_w, want_h, ow, oh);
         const auto t0 = std::chrono::steady_clock::now();
         ctx->jpeg_entropy_reported = false;
         if (ctx->jpeg_entropy_mode == 1) {
@@ -221,24 +192,23 @@ uint8_t* jpeg_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int3
     uint8_t* planes = (uint8_t*)site_buf(ctx, "jpeg.planes", plane_bytes);
     if (!dst_dev) dst_dev = (uint8_t*)site_buf(ctx, "jpeg.rgb", (size_t)f.width * f.height * 3);
 
-    ME_HIP(hipEventRecord(ctx->jpeg_ev[0], s));
+    ctx->jpeg_marks.record(0, s);
     if (!on_device) {
         ME_HIP(hipMemcpyAsync(coef, c.comps[0].coef, c.total_coefs * sizeof(int16_t), hipMemcpyHostToDevice, s));
-        ME_HIP(hipEventRecord(ctx->jpeg_uploaded, s));
-        ctx->jpeg_upload_pending = true;
+        ctx->jpeg_upload.uploaded_on(s);
     }
-    ME_HIP(hipEventRecord(ctx->jpeg_ev[1], s));
+    ctx->jpeg_marks.record(1, s);
 
     const int nchunks = (int)cdiv(f.total_blocks, kIdctChunk);
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)std::min(nchunks, kIdctMaxGrid)), dim3(kIdctWaves * 64), 0, s, f, tab,
                        (const int16_t*)coef, planes);
     ME_HIP(hipGetLastError());
-    ME_HIP(hipEventRecord(ctx->jpeg_ev[2], s));
+    ctx->jpeg_marks.record(2, s);
 
     const dim3 fgrid((unsigned)cdiv(cdiv(f.width, kFinishPixels), 256), (unsigned)f.height);
     hipLaunchKernelGGL(jpeg_finish_kernel, fgrid, dim3(256), 0, s, f, (const uint8_t*)planes, dst_dev);
     ME_HIP(hipGetLastError());
-    ME_HIP(hipEventRecord(ctx->jpeg_ev[3], s));
+    ctx->jpeg_marks.record(3, s);
     ctx->jpeg_timed = true, ctx->jpeg_timed_download = false;
     return dst_dev;
 }

@@ -135,8 +135,6 @@ DeviceFile jpeg_encode_device(me_ctx* ctx, const uint8_t* rgb_any, int32_t w, in
     hipStream_t s = ctx->stream;
     // the output back end may run on its own stream (me_ctx_set_output_overlap): its scratch is its own
     const std::string tag = (ctx->out_stream && s == ctx->out_stream) ? "out.jpegenc." : "jpegenc.";
-    if (!ctx->jpeg_encode_ev[0])
-        for (hipEvent_t& e : ctx->jpeg_encode_ev) ME_HIP(hipEventCreate(&e));
     JpegEncodeReport& rep = ctx->jpeg_encode_report;
     rep = JpegEncodeReport();
     ctx->jpeg_encode_reported = false;
@@ -154,19 +152,19 @@ DeviceFile jpeg_encode_device(me_ctx* ctx, const uint8_t* rgb_any, int32_t w, in
     uint64_t* agg = (uint64_t*)site_buf(ctx, tag + "agg", (size_t)block_groups * sizeof(uint64_t));
     uint64_t* carry = (uint64_t*)site_buf(ctx, tag + "carry", (size_t)(block_groups + 1) * sizeof(uint64_t));
 
-    ME_HIP(hipEventRecord(ctx->jpeg_encode_ev[0], s));
+    ctx->jpeg_encode_marks.record(0, s);
     const uint8_t* rgb = (const uint8_t*)to_device(ctx, rgb_any, (size_t)w * h * 3, tag + "rgb");
     ME_HIP(hipMemcpyAsync(dtab, tables.data(), sizeof(EncTables), hipMemcpyHostToDevice, s));
-    ME_HIP(hipEventRecord(ctx->jpeg_encode_ev[1], s));
+    ctx->jpeg_encode_marks.record(1, s);
     const int64_t fdct_groups = (int64_t)cdiv(nblocks, kFdctBlocks), wave_groups = (int64_t)cdiv(nblocks, kWaveBlocks);
     hipLaunchKernelGGL(jpeg_fdct_kernel, dim3((unsigned)fdct_groups), dim3(kThreads), 0, s, (const EncTables*)dtab, rgb, coef);
     ME_HIP(hipGetLastError());
-    ME_HIP(hipEventRecord(ctx->jpeg_encode_ev[2], s));
+    ctx->jpeg_encode_marks.record(2, s);
     hipLaunchKernelGGL(jpeg_bits_kernel, dim3((unsigned)wave_groups), dim3(kThreads), 0, s, (const EncTables*)dtab,
                        (const int16_t*)coef, nbits);
     ME_HIP(hipGetLastError());
     me_scan::launch_two_level<kThreads>(nbits, nblocks, before, agg, carry, s);
-    ME_HIP(hipEventRecord(ctx->jpeg_encode_ev[3], s));
+    ctx->jpeg_encode_marks.record(3, s);
     uint64_t total_bits = 0;
     ME_HIP(hipMemcpyAsync(&total_bits, carry + block_groups, sizeof(total_bits), hipMemcpyDeviceToHost, s));
     ME_HIP(hipStreamSynchronize(s));
@@ -189,14 +187,14 @@ DeviceFile jpeg_encode_device(me_ctx* ctx, const uint8_t* rgb_any, int32_t w, in
     hipLaunchKernelGGL(jpeg_pack_kernel, dim3((unsigned)wave_groups), dim3(kThreads), 0, s, (const EncTables*)dtab,
                        (const int16_t*)coef, (const uint64_t*)before, (const uint64_t*)carry, words);
     ME_HIP(hipGetLastError());
-    ME_HIP(hipEventRecord(ctx->jpeg_encode_ev[4], s));
+    ctx->jpeg_encode_marks.record(4, s);
     hipLaunchKernelGGL(jpeg_stuff_count_kernel, dim3((unsigned)chunk_groups), dim3(kThreads), 0, s, (const uint32_t*)words, nchunks, ff);
     ME_HIP(hipGetLastError());
     me_scan::launch_two_level<kThreads>(ff, nchunks, ff_before, ff_agg, ff_carry, s);
     hipLaunchKernelGGL(jpeg_stuff_kernel, dim3((unsigned)chunk_groups), dim3(kThreads), 0, s, (const EncTables*)dtab,
                        (const uint32_t*)words, nbytes, nchunks, (const uint64_t*)ff_before, (const uint64_t*)ff_carry, file);
     ME_HIP(hipGetLastError());
-    ME_HIP(hipEventRecord(ctx->jpeg_encode_ev[5], s));
+    ctx->jpeg_encode_marks.record(5, s);
     uint64_t stuffed = 0;
     ME_HIP(hipMemcpyAsync(&stuffed, ff_carry + chunk_groups, sizeof(stuffed), hipMemcpyDeviceToHost, s));
     ME_HIP(hipStreamSynchronize(s));
@@ -213,12 +211,7 @@ DeviceFile jpeg_encode_device(me_ctx* ctx, const uint8_t* rgb_any, int32_t w, in
     return f;
 }
 
-void free_jpeg_encode_scratch(me_ctx* ctx) {
-    for (hipEvent_t& e : ctx->jpeg_encode_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-}
+void free_jpeg_encode_scratch(me_ctx* ctx) { ctx->jpeg_encode_marks.destroy(); }
 
 }  // namespace me
 
@@ -230,11 +223,7 @@ extern "C" int32_t me_last_jpeg_encode(me_ctx* ctx, int64_t report[10], double m
     report[0] = r.blocks, report[1] = r.scan_bits, report[2] = r.stuffed, report[3] = r.file_bytes, report[4] = r.fdct_groups;
     report[5] = r.wave_groups, report[6] = r.block_scan_groups, report[7] = r.stuff_groups, report[8] = r.stuff_groups;
     report[9] = r.capacity;
-    for (int i = 0; i < 6; ++i) {
-        float t = 0.f;
-        if (i < 5 || r.downloaded) ME_HIP(hipEventElapsedTime(&t, ctx->jpeg_encode_ev[i], ctx->jpeg_encode_ev[i + 1]));
-        ms[i] = t;
-    }
+    for (int i = 0; i < 6; ++i) ms[i] = i < 5 || r.downloaded ? ctx->jpeg_encode_marks.ms(i, i + 1) : 0.0;
     ME_API_END(ctx)
 }
 

@@ -141,10 +141,8 @@ bool jpeg_entropy_decode(me_ctx* ctx, const std::vector<uint8_t>& file, int32_t 
         rep.reason = plan.reason;
         return false;
     }
-    if (!ctx->jpeg_entropy_ev[0]) {
-        for (hipEvent_t& e : ctx->jpeg_entropy_ev) ME_HIP(hipEventCreate(&e));
+    if (!ctx->jpeg_entropy_status)
         ME_HIP(hipHostMalloc((void**)&ctx->jpeg_entropy_status, (kRoundsPerBatch + 1) * sizeof(int32_t), hipHostMallocDefault));
-    }
     const size_t cap = upload_capacity(plan, S);
     uint32_t* host = reinterpret_cast<uint32_t*>(jpeg_pinned_buffer(ctx, cap * 2));
     const Layout lay = prepare(plan, file.data(), S, host);
@@ -164,11 +162,10 @@ bool jpeg_entropy_decode(me_ctx* ctx, const std::vector<uint8_t>& file, int32_t 
     const size_t total_coefs = plan.frame.total_coefs;
     int16_t* coef = (int16_t*)site_buf(ctx, "jpeg.coef", total_coefs * sizeof(int16_t));
 
-    ME_HIP(hipEventRecord(ctx->jpeg_entropy_ev[0], s));
+    ctx->jpeg_entropy_marks.record(0, s);
     ME_HIP(hipMemcpyAsync(dev, host, lay.total * 4, hipMemcpyHostToDevice, s));
-    ME_HIP(hipEventRecord(ctx->jpeg_uploaded, s));
-    ctx->jpeg_upload_pending = true;
-    ME_HIP(hipEventRecord(ctx->jpeg_entropy_ev[1], s));
+    ctx->jpeg_upload.uploaded_on(s);
+    ctx->jpeg_entropy_marks.record(1, s);
     ME_HIP(hipMemsetAsync(ctl, 0, (size_t)(max_rounds + 2) * sizeof(int32_t), s));
     ME_HIP(hipMemsetAsync(coef, 0, total_coefs * sizeof(int16_t), s));
     const Stream st = stream_of(dev, lay);
@@ -203,13 +200,10 @@ bool jpeg_entropy_decode(me_ctx* ctx, const std::vector<uint8_t>& file, int32_t 
     ME_HIP(hipGetLastError());
     hipLaunchKernelGGL(jpeg_entropy_write_kernel, grid, block, 0, s, st, final_state, before, (const Counts*)carry, coef, ctl);
     ME_HIP(hipGetLastError());
-    ME_HIP(hipEventRecord(ctx->jpeg_entropy_ev[2], s));
+    ctx->jpeg_entropy_marks.record(2, s);
     ME_HIP(hipMemcpyAsync(ctx->jpeg_entropy_status, ctl, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     ME_HIP(hipStreamSynchronize(s));
-    float up = 0.f, kern = 0.f;
-    ME_HIP(hipEventElapsedTime(&up, ctx->jpeg_entropy_ev[0], ctx->jpeg_entropy_ev[1]));
-    ME_HIP(hipEventElapsedTime(&kern, ctx->jpeg_entropy_ev[1], ctx->jpeg_entropy_ev[2]));
-    rep.ms[1] = up, rep.ms[2] = kern;
+    rep.ms[1] = ctx->jpeg_entropy_marks.ms(0, 1), rep.ms[2] = ctx->jpeg_entropy_marks.ms(1, 2);
     if (ctx->jpeg_entropy_status[0] != 0) {
         rep.reason = ctx->jpeg_entropy_status[0];
         return false;
@@ -219,10 +213,7 @@ bool jpeg_entropy_decode(me_ctx* ctx, const std::vector<uint8_t>& file, int32_t 
 }
 
 void free_jpeg_entropy_scratch(me_ctx* ctx) {
-    for (hipEvent_t& e : ctx->jpeg_entropy_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
+    ctx->jpeg_entropy_marks.destroy();
     if (ctx->jpeg_entropy_status) (void)hipHostFree(ctx->jpeg_entropy_status);
     ctx->jpeg_entropy_status = nullptr;
 }

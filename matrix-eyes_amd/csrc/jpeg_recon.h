@@ -18,6 +18,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "orient.h"
+
 namespace me_jpeg {
 
 constexpr int kLanes = 64;          // lanes of one 8x8 block: lane t makes sample t
@@ -203,20 +205,9 @@ JPEG_FN void pixel_rgb(const Frame& f, const uint8_t* planes, int32_t x, int32_t
     ycc_to_rgb(s0, s1, s2, rgb);
 }
 
-// where pixel (x, y) of the decoded picture lands in the oriented one (apply_orientation of host/image_io.cpp, inverted):
-// its pixel index there.  Orientations 5..8 swap the sides.
+// where pixel (x, y) of the decoded picture lands in the oriented one (orient.h): its pixel index there
 JPEG_FN int64_t oriented_index(const Frame& f, int32_t x, int32_t y) {
-    const int64_t w = f.width, h = f.height;
-    switch (f.orientation) {
-        case 2: return (int64_t)y * w + (w - 1 - x);
-        case 3: return (h - 1 - y) * w + (w - 1 - x);
-        case 4: return (h - 1 - y) * w + x;
-        case 5: return (int64_t)x * h + y;
-        case 6: return (int64_t)x * h + (h - 1 - y);
-        case 7: return (w - 1 - x) * h + (h - 1 - y);
-        case 8: return (w - 1 - x) * h + y;
-        default: return (int64_t)y * w + x;
-    }
+    return me_orient::oriented_index(f.width, f.height, x, y, f.orientation);
 }
 
 }  // namespace me_jpeg

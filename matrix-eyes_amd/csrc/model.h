@@ -125,6 +125,62 @@ struct ResampleTable {
 
 struct WeightPackState;  // weight_pack_state.h: the device packer's staging ring, the last load's report
 
+// A pinned host staging buffer that one asynchronous upload at a time reads (the photo decoders, input_api.hip): grown to
+// the high-water mark; `uploaded` is recorded behind every upload, and the next call waits for it on the host before it
+// writes or frees the buffer (calls may be queued without a synchronise between them).
+struct PinnedUpload {
+    void* host = nullptr;
+    size_t capacity = 0;
+    hipEvent_t uploaded = nullptr;
+    bool pending = false;
+    void* reserve(size_t bytes) {
+        if (!uploaded) ME_HIP(hipEventCreateWithFlags(&uploaded, hipEventDisableTiming));
+        if (pending) {
+            ME_HIP(hipEventSynchronize(uploaded));
+            pending = false;
+        }
+        if (bytes > capacity) {
+            if (host) ME_HIP(hipHostFree(host));
+            host = nullptr, capacity = 0;
+            ME_HIP(hipHostMalloc(&host, bytes, hipHostMallocDefault));
+            capacity = bytes;
+        }
+        return host;
+    }
+    void uploaded_on(hipStream_t stream) {
+        ME_HIP(hipEventRecord(uploaded, stream));
+        pending = true;
+    }
+    void release() {
+        if (host) (void)hipHostFree(host);
+        if (uploaded) (void)hipEventDestroy(uploaded);
+        *this = PinnedUpload();
+    }
+};
+
+// The timing marks around the legs of a context's last call of one kind: events made on first use, kept for the next call.
+struct LegMarks {
+    std::vector<hipEvent_t> ev;
+    hipEvent_t at(size_t i) {
+        while (ev.size() <= i) {
+            hipEvent_t e = nullptr;
+            ME_HIP(hipEventCreate(&e));
+            ev.push_back(e);
+        }
+        return ev[i];
+    }
+    void record(size_t i, hipStream_t stream) { ME_HIP(hipEventRecord(at(i), stream)); }
+    double ms(size_t a, size_t b) {
+        float t = 0.f;
+        ME_HIP(hipEventElapsedTime(&t, at(a), at(b)));
+        return (double)t;
+    }
+    void destroy() {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        ev.clear();
+    }
+};
+
 }  // namespace me
 
 // The opaque C handle.
@@ -267,43 +323,6 @@ struct me_ctx {
     std::vector<me::ResampleTable> rs_tables;
     uint64_t rs_stamp = 0;
 
-    // JPEG decoding (jpeg_decode.hip): the pinned host buffer the entropy decoder fills and the upload reads, grown to the
-    // high-water mark; `jpeg_uploaded` is recorded behind every upload, and the next decode waits for it on the host
-    // before it writes the buffer again (calls may be queued without a synchronise between them).  jpeg_ev: the marks
-    // around the legs of the last decode (me_last_jpeg_timing).
-    int16_t* jpeg_pinned = nullptr;
-    size_t jpeg_pinned_count = 0;
-    hipEvent_t jpeg_uploaded = nullptr;
-    bool jpeg_upload_pending = false;
-    hipEvent_t jpeg_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool jpeg_timed = false, jpeg_timed_download = false;
-    double jpeg_entropy_ms = 0.0;
-    // The entropy leg on the device (jpeg_entropy.hip; me_ctx_set_jpeg_entropy): 0 host, 1 device.  The report of the last
-    // attempt (me_last_jpeg_entropy), the marks around its upload and kernels, and the pinned words its status comes back in.
-    int32_t jpeg_entropy_mode = 0;
-    JpegEntropyReport jpeg_entropy_report;
-    bool jpeg_entropy_reported = false;
-    hipEvent_t jpeg_entropy_ev[3] = {nullptr, nullptr, nullptr};
-    int32_t* jpeg_entropy_status = nullptr;
-    // JPEG encoding (jpeg_encode.hip): the report of the last encode and the marks around its legs (me_last_jpeg_encode)
-    JpegEncodeReport jpeg_encode_report;
-    bool jpeg_encode_reported = false;
-    hipEvent_t jpeg_encode_ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    // PNG decoding (png_decode.hip): the pinned host buffer zlib inflates into and the uploads read, grown to the high-water
-    // mark; `png_uploaded` is recorded behind the last upload of a decode, and the next decode waits for it on the host
-    // before it inflates into the buffer again.  png_status: the pinned word the finish kernel's palette status comes back
-    // in.  png_ev: the marks of the last decode (me_last_png_timing): three per band (before its upload, between upload and
-    // unfilter launch, behind the launch), then before and behind the finish kernel and behind the download.
-    uint8_t* png_pinned = nullptr;
-    size_t png_pinned_bytes = 0;
-    int32_t* png_status = nullptr;
-    hipEvent_t png_uploaded = nullptr;
-    bool png_upload_pending = false;
-    std::vector<hipEvent_t> png_ev;
-    int32_t png_timed_bands = 0;
-    bool png_timed = false, png_timed_download = false;
-    double png_inflate_ms = 0.0;
-
     // The whole extract_depth step as one hipGraph (shapes are static per batch size).  A call whose pointers
     // all live on the device and that needs no host callback is enqueued eagerly the first time it is seen,
     // captured the second time and replayed with one hipGraphLaunch from then on; anything that changes what the
@@ -352,6 +371,37 @@ struct me_ctx {
         return h;
     }
 
+    // Photo input (input_api.hip; DESIGN.md "The photo front end").  Kept behind everything the model's units read, so
+    // that a change here moves no offset they use.  One staging buffer and one set of marks per format: a JPEG and a PNG
+    // decode queued back to back never share a buffer, and each format's timing report outlives the other's decodes.
+    // JPEG decoding (jpeg_decode.hip): jpeg_upload is what the entropy decoder fills and the upload reads; jpeg_marks are
+    // the marks around the legs of the last decode (me_last_jpeg_timing).
+    me::PinnedUpload jpeg_upload;
+    me::LegMarks jpeg_marks;
+    bool jpeg_timed = false, jpeg_timed_download = false;
+    double jpeg_entropy_ms = 0.0;
+    // The entropy leg on the device (jpeg_entropy.hip; me_ctx_set_jpeg_entropy): 0 host, 1 device.  The report of the last
+    // attempt (me_last_jpeg_entropy), the marks around its upload and kernels, and the pinned words its status comes back in.
+    int32_t jpeg_entropy_mode = 0;
+    JpegEntropyReport jpeg_entropy_report;
+    bool jpeg_entropy_reported = false;
+    me::LegMarks jpeg_entropy_marks;
+    int32_t* jpeg_entropy_status = nullptr;
+    // JPEG encoding (jpeg_encode.hip): the report of the last encode and the marks around its legs (me_last_jpeg_encode)
+    JpegEncodeReport jpeg_encode_report;
+    bool jpeg_encode_reported = false;
+    me::LegMarks jpeg_encode_marks;
+    // PNG decoding (png_decode.hip): png_upload is what zlib inflates into and the uploads read; png_status: the pinned word
+    // the finish kernel's palette status comes back in.  png_marks: the marks of the last decode (me_last_png_timing): three
+    // per band (before its upload, between upload and unfilter launch, behind the launch), then before and behind the finish
+    // kernel and behind the download.
+    me::PinnedUpload png_upload;
+    int32_t* png_status = nullptr;
+    me::LegMarks png_marks;
+    int32_t png_timed_bands = 0;
+    bool png_timed = false, png_timed_download = false;
+    double png_inflate_ms = 0.0;
+
     // geometry helpers
     int g() const { return cfg.grid; }
     int P() const { return cfg.grid * cfg.grid; }
@@ -398,6 +448,8 @@ struct OutBuf {
 };
 OutBuf out_buf(me_ctx* ctx, void* user, size_t bytes, const std::string& name);
 void finish(me_ctx* ctx, const OutBuf& o);
+// api.hip: the calling thread's error text of the entries that take no context (me_last_error(nullptr))
+std::string& create_error();
 
 // ---- stages (all device pointers; see pipeline.hip) ----
 struct VitTaps {
@@ -454,7 +506,16 @@ uint8_t* jpeg_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int3
                           int32_t want_w, int32_t want_h, int32_t* ow, int32_t* oh);
 void free_jpeg_scratch(me_ctx* ctx);
 // the context's pinned staging buffer of `count` int16_t, once the upload of the call before has left it
-int16_t* jpeg_pinned_buffer(me_ctx* ctx, size_t count);
+inline int16_t* jpeg_pinned_buffer(me_ctx* ctx, size_t count) { return (int16_t*)ctx->jpeg_upload.reserve(count * sizeof(int16_t)); }
+// The size first: a w x h picture under `orientation` is *ow x *oh, and a destination of another size (want_w / want_h > 0)
+// is refused before any decoding.  `format`: "JPEG" / "PNG".
+inline void oriented_size_or_refuse(const char* format, int32_t w, int32_t h, int32_t orientation, int32_t want_w, int32_t want_h,
+                                    int32_t* ow, int32_t* oh) {
+    const bool swap = orientation >= 5;
+    *ow = swap ? h : w, *oh = swap ? w : h;
+    ME_CHECK((want_w <= 0 && want_h <= 0) || (want_w == *ow && want_h == *oh), ME_ERR_BAD_SHAPE,
+             "%s decode: the picture is %dx%d (orientation %d), the destination %dx%d", format, *ow, *oh, orientation, want_w, want_h);
+}
 // jpeg_entropy.hip: the scan's coefficients made on the device, into the "jpeg.coef" buffer.  subseq_bits 0: the default.
 // False: declined (ctx->jpeg_entropy_report.reason), the host decoder is to run.
 bool jpeg_entropy_decode(me_ctx* ctx, const std::vector<uint8_t>& file, int32_t subseq_bits,

@@ -53,7 +53,7 @@ void write_device_file(me_ctx* ctx, const DeviceFile& f, const char* path, hipEv
 void write_jpeg(me_ctx* ctx, const uint8_t* rgb_any, int32_t w, int32_t h, int32_t quality, int32_t subsampling, const char* path) {
     const DeviceFile f = jpeg_encode_device(ctx, rgb_any, w, h, quality, subsampling);
     ctx->jpeg_encode_report.downloaded = true;
-    write_device_file(ctx, f, path, ctx->jpeg_encode_ev[6]);
+    write_device_file(ctx, f, path, ctx->jpeg_encode_marks.at(6));
 }
 
 void stereogram_impl(me_ctx* ctx, const float* depth, int32_t rows, int32_t cols, float min_depth, float max_depth,

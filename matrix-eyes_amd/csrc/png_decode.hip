@@ -230,15 +230,6 @@ bool bad_filter(const Geom& g, const Band& b, const uint8_t* stream) {
     return false;
 }
 
-hipEvent_t timing_event(me_ctx* ctx, size_t i) {
-    while (ctx->png_ev.size() <= i) {
-        hipEvent_t e = nullptr;
-        ME_HIP(hipEventCreate(&e));
-        ctx->png_ev.push_back(e);
-    }
-    return ctx->png_ev[i];
-}
-
 // what inflate_png's callback works with: bands are uploaded and launched as the inflate completes them
 struct Feed {
     me_ctx* ctx;
@@ -258,37 +249,24 @@ struct Feed {
                 break;
             }
             hipStream_t s = u.stream;
-            ME_HIP(hipEventRecord(timing_event(ctx, 3 * (size_t)u.next), s));
+            ctx->png_marks.record(3 * (size_t)u.next, s);
             if (end > uploaded) {
                 ME_HIP(hipMemcpyAsync(dev + uploaded, pinned + uploaded, (size_t)(end - uploaded), hipMemcpyHostToDevice, s));
                 uploaded = end;
             }
-            ME_HIP(hipEventRecord(timing_event(ctx, 3 * (size_t)u.next + 1), s));
+            ctx->png_marks.record(3 * (size_t)u.next + 1, s);
             u.launch(b, dev, dev);
-            ME_HIP(hipEventRecord(timing_event(ctx, 3 * (size_t)u.next + 2), s));
+            ctx->png_marks.record(3 * (size_t)u.next + 2, s);
             ++u.next;
         }
     }
     static void callback(void* user, size_t complete) { ((Feed*)user)->upto(complete); }
 };
 
-// the pinned buffer the inflate lands in: the upload of the call before may still be reading it
+// the pinned buffer the inflate lands in (the upload of the call before may still be reading it), and the status word
 uint8_t* pinned_stream(me_ctx* ctx, size_t bytes) {
-    if (!ctx->png_uploaded) {
-        ME_HIP(hipEventCreateWithFlags(&ctx->png_uploaded, hipEventDisableTiming));
-        ME_HIP(hipHostMalloc((void**)&ctx->png_status, sizeof(int32_t), hipHostMallocDefault));
-    }
-    if (ctx->png_upload_pending) {
-        ME_HIP(hipEventSynchronize(ctx->png_uploaded));
-        ctx->png_upload_pending = false;
-    }
-    if (bytes > ctx->png_pinned_bytes) {
-        if (ctx->png_pinned) ME_HIP(hipHostFree(ctx->png_pinned));
-        ctx->png_pinned = nullptr, ctx->png_pinned_bytes = 0;
-        ME_HIP(hipHostMalloc((void**)&ctx->png_pinned, bytes, hipHostMallocDefault));
-        ctx->png_pinned_bytes = bytes;
-    }
-    return ctx->png_pinned;
+    if (!ctx->png_status) ME_HIP(hipHostMalloc((void**)&ctx->png_status, sizeof(int32_t), hipHostMallocDefault));
+    return (uint8_t*)ctx->png_upload.reserve(bytes);
 }
 
 // The device path met a defect (the stream does not inflate, a filter byte above 4, a palette index past the palette): the
@@ -305,14 +283,10 @@ uint8_t* pinned_stream(me_ctx* ctx, size_t bytes) {
 }  // namespace
 
 void free_png_scratch(me_ctx* ctx) {
-    if (ctx->png_pinned) (void)hipHostFree(ctx->png_pinned);
-    ctx->png_pinned = nullptr, ctx->png_pinned_bytes = 0;
+    ctx->png_upload.release();
     if (ctx->png_status) (void)hipHostFree(ctx->png_status);
     ctx->png_status = nullptr;
-    if (ctx->png_uploaded) (void)hipEventDestroy(ctx->png_uploaded);
-    ctx->png_uploaded = nullptr;
-    for (hipEvent_t e : ctx->png_ev) (void)hipEventDestroy(e);
-    ctx->png_ev.clear();
+    ctx->png_marks.destroy();
 }
 
 uint8_t* png_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32_t orientation, uint8_t* dst_dev,
@@ -328,10 +302,7 @@ uint8_t* png_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32
         fail(ME_ERR_BAD_ARG, "%s", err.what());
     }
     // the size first: a caller's buffer of another size is refused before any decoding
-    const bool swap = orientation >= 5;
-    *ow = (int32_t)(swap ? f.height : f.width), *oh = (int32_t)(swap ? f.width : f.height);
-    ME_CHECK((want_w <= 0 && want_h <= 0) || (want_w == *ow && want_h == *oh), ME_ERR_BAD_SHAPE,
-             "PNG decode: the picture is %dx%d (orientation %d), the destination %dx%d", *ow, *oh, orientation, want_w, want_h);
+    oriented_size_or_refuse("PNG", (int32_t)f.width, (int32_t)f.height, orientation, want_w, want_h, ow, oh);
 
     uint8_t* pinned = pinned_stream(ctx, f.total);
     uint8_t* stream = (uint8_t*)site_buf(ctx, "png.stream", f.total);
@@ -350,10 +321,7 @@ uint8_t* png_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32
         inflated = false;
     }
     ctx->png_inflate_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (feed.uploaded > 0) {
-        ME_HIP(hipEventRecord(ctx->png_uploaded, s));
-        ctx->png_upload_pending = true;
-    }
+    if (feed.uploaded > 0) ctx->png_upload.uploaded_on(s);
     if (!inflated || feed.defect || feed.u.next != feed.u.nbands) refuse_as_the_host(bytes, name);
     const size_t band_events = 3 * (size_t)feed.u.nbands;
 
@@ -364,13 +332,12 @@ uint8_t* png_decode_rgb8(me_ctx* ctx, const uint8_t* file, int64_t nbytes, int32
         if (plte_bytes) ME_HIP(hipMemcpyAsync(plte, f.plte.data(), plte_bytes, hipMemcpyHostToDevice, s));
         ME_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
     }
-    ME_HIP(hipEventRecord(timing_event(ctx, band_events), s));
+    ctx->png_marks.record(band_events, s);
     const int64_t pixels = (int64_t)f.width * f.height;
     hipLaunchKernelGGL(png_finish_kernel, dim3((unsigned)std::min<int64_t>(cdiv(pixels, 256), kFinishMaxGrid)), dim3(256), 0, s,
                        f.geom, orientation, (const uint8_t*)stream, (const uint8_t*)plte, (int32_t)plte_bytes, dst_dev, status);
     ME_HIP(hipGetLastError());
-    ME_HIP(hipEventRecord(timing_event(ctx, band_events + 1), s));
-    (void)timing_event(ctx, band_events + 2);   // the download's mark (api.hip)
+    ctx->png_marks.record(band_events + 1, s);
     if (palette) {   // the one case that waits for the device: the status word decides between pixels and a refusal
         ME_HIP(hipMemcpyAsync(ctx->png_status, status, sizeof(int32_t), hipMemcpyDeviceToHost, s));
         ME_HIP(hipStreamSynchronize(s));

@@ -6,6 +6,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "orient.h"
+
 #if defined(__HIPCC__)
 #define PNGDEC_FN __host__ __device__ inline
 #else
@@ -134,22 +136,7 @@ PNGDEC_FN bool pixel_rgb(const Geom& g, const uint8_t* row, int32_t px, const ui
     }
 }
 
-// where picture pixel (x, y) goes under apply_orientation(orientation): the pixel index in the oriented picture
-// (oriented width: height for 5..8, else width)
-PNGDEC_FN int64_t oriented_index(int32_t w, int32_t h, int32_t x, int32_t y, int orientation) {
-    int64_t ox, oy;
-    switch (orientation) {
-        case 2: ox = w - 1 - x, oy = y; break;          // flip horizontally
-        case 3: ox = w - 1 - x, oy = h - 1 - y; break;  // rotate 180
-        case 4: ox = x, oy = h - 1 - y; break;          // flip vertically
-        case 5: ox = y, oy = x; break;                  // transpose
-        case 6: ox = h - 1 - y, oy = x; break;          // rotate 90 clockwise
-        case 7: ox = h - 1 - y, oy = w - 1 - x; break;  // transverse
-        case 8: ox = y, oy = w - 1 - x; break;          // rotate 270 clockwise
-        default: ox = x, oy = y; break;
-    }
-    return oy * (orientation >= 5 && orientation <= 8 ? h : w) + ox;
-}
+using me_orient::oriented_index;   // orient.h: where picture pixel (x, y) goes under apply_orientation(orientation)
 
 // the destination pixel of pass pixel (px, py) under orientation 1..8
 PNGDEC_FN int64_t dest_index(const Geom& g, const Pass& p, int32_t px, int32_t py, int orientation) {

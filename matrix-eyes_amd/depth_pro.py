@@ -442,41 +442,54 @@ class Context:
         return out
 
     @staticmethod
-    def jpeg_info(data: bytes):
-        """(width, height, exif_offset, exif_nbytes) of a JPEG file in memory (me_jpeg_info): the size as coded, before
-        any orientation, and the span of the TIFF-structured EXIF block inside `data` (0, 0: none).  No GPU."""
+    def _photo_info(symbol: str, data: bytes):
+        """me_jpeg_info / me_png_info: (width, height, exif_offset, exif_nbytes) of a file in memory"""
         lib = L.load_library()
         data = bytes(data)
         w, h, off, n = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
-        rc = lib.me_jpeg_info(data, len(data), C.byref(w), C.byref(h), C.byref(off), C.byref(n))
+        rc = getattr(lib, symbol)(data, len(data), C.byref(w), C.byref(h), C.byref(off), C.byref(n))
         if rc != L.ME_OK:
             msg = lib.me_last_error(None)
             raise L.MatrixEyesError(rc, msg.decode("utf-8", "replace") if msg else "")
         return w.value, h.value, off.value, n.value
 
+    def _decode_photo(self, kind: str, data: bytes, orientation: int = 1, out=None):
+        """me_jpeg_decode_rgb8 / me_png_decode_rgb8 (kind "jpeg" / "png") into `out` or a new numpy array"""
+        data = bytes(data)
+        w, h, _, _ = self._photo_info(f"me_{kind}_info", data)
+        if 5 <= int(orientation) <= 8:
+            w, h = h, w
+        po, out = _out(out, (h, w, 3), np.uint8)
+        self._check(getattr(self.lib, f"me_{kind}_decode_rgb8")(self._h, data, len(data), int(orientation), po, w, h))
+        return out
+
+    def _decode_photo_resized(self, kind: str, data: bytes, size, orientation: int = 1, out=None):
+        """me_jpeg_decode_resized_rgb8 / me_png_decode_resized_rgb8 (kind "jpeg" / "png") to size = (nw, nh)"""
+        data = bytes(data)
+        nw, nh = int(size[0]), int(size[1])
+        if nw <= 0 or nh <= 0:
+            raise L.MatrixEyesError(2, f"decode_{kind}_resized: target size {nw}x{nh}")
+        po, out = _out(out, (nh, nw, 3), np.uint8)
+        self._check(getattr(self.lib, f"me_{kind}_decode_resized_rgb8")(self._h, data, len(data), int(orientation), po, nw, nh))
+        return out
+
+    @staticmethod
+    def jpeg_info(data: bytes):
+        """(width, height, exif_offset, exif_nbytes) of a JPEG file in memory (me_jpeg_info): the size as coded, before
+        any orientation, and the span of the TIFF-structured EXIF block inside `data` (0, 0: none).  No GPU."""
+        return Context._photo_info("me_jpeg_info", data)
+
     def decode_jpeg(self, data: bytes, orientation: int = 1, out=None):
         """The picture of a JPEG file, oriented (me_jpeg_decode_rgb8): uint8 [h, w, 3], the C++ host decoder's bytes.
         out: a numpy array or a CUDA torch tensor of the oriented shape (a CUDA one is only queued on the context's
         stream); None: a new numpy array."""
-        data = bytes(data)
-        w, h, _, _ = self.jpeg_info(data)
-        if 5 <= int(orientation) <= 8:
-            w, h = h, w
-        po, out = _out(out, (h, w, 3), np.uint8)
-        self._check(self.lib.me_jpeg_decode_rgb8(self._h, data, len(data), int(orientation), po, w, h))
-        return out
+        return self._decode_photo("jpeg", data, orientation, out)
 
     def decode_jpeg_resized(self, data: bytes, size, orientation: int = 1, out=None):
         """decode_jpeg into context-owned device memory, then resize_lanczos3 to size = (nw, nh)
         (me_jpeg_decode_resized_rgb8, reconstruction.rs:95-113 in one call): only the resized picture leaves the device,
         or, with a CUDA `out`, nothing does."""
-        data = bytes(data)
-        nw, nh = int(size[0]), int(size[1])
-        if nw <= 0 or nh <= 0:
-            raise L.MatrixEyesError(2, f"decode_jpeg_resized: target size {nw}x{nh}")
-        po, out = _out(out, (nh, nw, 3), np.uint8)
-        self._check(self.lib.me_jpeg_decode_resized_rgb8(self._h, data, len(data), int(orientation), po, nw, nh))
-        return out
+        return self._decode_photo_resized("jpeg", data, size, orientation, out)
 
     def set_jpeg_entropy(self, where: str) -> None:
         """resolve_jpeg_entropy's "host" / "device" for this context's JPEG decodes (me_ctx_set_jpeg_entropy)"""
@@ -502,38 +515,19 @@ class Context:
     def png_info(data: bytes):
         """(width, height, exif_offset, exif_nbytes) of a PNG file in memory (me_png_info): IHDR's size, before any
         orientation, and the span of the last eXIf chunk's body inside `data` (0, 0: none).  No GPU."""
-        lib = L.load_library()
-        data = bytes(data)
-        w, h, off, n = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
-        rc = lib.me_png_info(data, len(data), C.byref(w), C.byref(h), C.byref(off), C.byref(n))
-        if rc != L.ME_OK:
-            msg = lib.me_last_error(None)
-            raise L.MatrixEyesError(rc, msg.decode("utf-8", "replace") if msg else "")
-        return w.value, h.value, off.value, n.value
+        return Context._photo_info("me_png_info", data)
 
     def decode_png(self, data: bytes, orientation: int = 1, out=None):
         """The picture of a PNG file, oriented (me_png_decode_rgb8): uint8 [h, w, 3], the C++ host decoder's bytes.
         out: a numpy array or a CUDA torch tensor of the oriented shape (a CUDA one is only queued on the context's
         stream); None: a new numpy array."""
-        data = bytes(data)
-        w, h, _, _ = self.png_info(data)
-        if 5 <= int(orientation) <= 8:
-            w, h = h, w
-        po, out = _out(out, (h, w, 3), np.uint8)
-        self._check(self.lib.me_png_decode_rgb8(self._h, data, len(data), int(orientation), po, w, h))
-        return out
+        return self._decode_photo("png", data, orientation, out)
 
     def decode_png_resized(self, data: bytes, size, orientation: int = 1, out=None):
         """decode_png into context-owned device memory, then resize_lanczos3 to size = (nw, nh)
         (me_png_decode_resized_rgb8, reconstruction.rs:95-113 in one call): only the resized picture leaves the device,
         or, with a CUDA `out`, nothing does."""
-        data = bytes(data)
-        nw, nh = int(size[0]), int(size[1])
-        if nw <= 0 or nh <= 0:
-            raise L.MatrixEyesError(2, f"decode_png_resized: target size {nw}x{nh}")
-        po, out = _out(out, (nh, nw, 3), np.uint8)
-        self._check(self.lib.me_png_decode_resized_rgb8(self._h, data, len(data), int(orientation), po, nw, nh))
-        return out
+        return self._decode_photo_resized("png", data, size, orientation, out)
 
     def last_png_timing(self):
         """[inflate (host), uploads, unfilter launches, finish kernel, download] of the last PNG decode, in ms"""

@@ -80,9 +80,7 @@ class SourceImage:                          # reconstruction.rs:74-81
             ctx = ctx() if callable(ctx) else ctx
             if kind == "jpeg":
                 ctx.set_jpeg_entropy(jpeg_entropy)
-            info, decode, decode_resized = ((ctx.jpeg_info, ctx.decode_jpeg, ctx.decode_jpeg_resized) if kind == "jpeg" else
-                                            (ctx.png_info, ctx.decode_png, ctx.decode_png_resized))
-            width, height, _, _ = info(data)
+            width, height, _, _ = ctx._photo_info(f"me_{kind}_info", data)
             orientation = 1
             try:                                  # header only: Pillow parses the EXIF block, not the scans
                 head = Image.open(io.BytesIO(data))
@@ -95,9 +93,9 @@ class SourceImage:                          # reconstruction.rs:74-81
                 orientation = 1
             original_size = (height, width) if orientation >= 5 else (width, height)
             if resampler == "device":
-                rgb = decode_resized(data, (size, size), orientation)               # :95-113 in one call
+                rgb = ctx._decode_photo_resized(kind, data, (size, size), orientation)   # :95-113 in one call
             else:
-                img = Image.fromarray(decode(data, orientation))
+                img = Image.fromarray(ctx._decode_photo(kind, data, orientation))
                 if img.size != (size, size):
                     img = img.resize((size, size), Image.LANCZOS)
                 rgb = np.ascontiguousarray(np.asarray(img, dtype=np.uint8))

@@ -11,6 +11,8 @@ import subprocess
 
 import numpy as np
 
+from orient_ref import orient  # noqa: F401  (J.orient: apply_orientation restated)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "matrix-eyes_amd")
 SELFTEST = os.path.join(PKG, "host_selftest")
@@ -169,22 +171,3 @@ def host_decode(data: bytes, tmp_dir, oriented=True, name="f"):
     if r.returncode != 0:
         return r.returncode, None, r.stderr
     return 0, read_ppm(dst), r.stderr
-
-
-def orient(img: np.ndarray, orientation: int) -> np.ndarray:
-    """apply_orientation of host/image_io.cpp (image_io.hpp:37-39) restated on arrays"""
-    if orientation == 2:
-        return img[:, ::-1]
-    if orientation == 3:
-        return img[::-1, ::-1]
-    if orientation == 4:
-        return img[::-1]
-    if orientation == 5:
-        return img.transpose(1, 0, 2)
-    if orientation == 6:
-        return img[::-1].transpose(1, 0, 2)
-    if orientation == 7:
-        return img[::-1, ::-1].transpose(1, 0, 2)
-    if orientation == 8:
-        return img[:, ::-1].transpose(1, 0, 2)
-    return img

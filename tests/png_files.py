@@ -13,6 +13,8 @@ import zlib
 
 import numpy as np
 
+from orient_ref import orient  # noqa: F401  (P.orient: apply_orientation restated)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "matrix-eyes_amd")
 SELFTEST = os.path.join(PKG, "host_selftest")
@@ -146,12 +148,6 @@ def with_exif(data: bytes, orientation, focal=None) -> bytes:
     """the file with an eXIf chunk behind IHDR (behind any it has: the last one counts)"""
     at = data.index(b"IDAT") - 4
     return data[:at] + chunk(b"eXIf", exif_block(orientation, focal)) + data[at:]
-
-
-def orient(img, o):
-    """apply_orientation (host/image_io.cpp) restated"""
-    return {1: img, 2: img[:, ::-1], 3: img[::-1, ::-1], 4: img[::-1], 5: img.transpose(1, 0, 2),
-            6: img.transpose(1, 0, 2)[:, ::-1], 7: img.transpose(1, 0, 2)[::-1, ::-1], 8: img.transpose(1, 0, 2)[::-1]}[o]
 
 
 def all_pairs():

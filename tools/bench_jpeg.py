@@ -6,6 +6,7 @@
   device_ms          (b) me_jpeg_decode_rgb8 into PINNED host memory: wall clock, the call ends in a stream synchronise
   legs_ms            (b) split (me_last_jpeg_timing): entropy decode on the host (wall clock), upload of the coefficients,
                      jpeg_idct_kernel, jpeg_finish_kernel, download -- the four device legs by HIP events
+  legs_ms_range      (b) the smallest and largest value of each leg over the repeats
   resized_ms         (c) me_jpeg_decode_resized_rgb8 into a 1536 x 1536 DEVICE buffer: wall clock around the call and a
                      context synchronise
   entropy_share      legs_ms.entropy / device_ms: what is left on the host
@@ -113,6 +114,8 @@ def main():
                    device_ms_max=round(max(db), 2),
                    legs_ms=dict(entropy=round(leg[0], 2), upload=round(leg[1], 3), idct=round(leg[2], 3),
                                 finish=round(leg[3], 3), download=round(leg[4], 3)),
+                   legs_ms_range={k: [round(min(v[i] for v in legs), 3), round(max(v[i] for v in legs), 3)]
+                                  for i, k in enumerate(("entropy", "upload", "idct", "finish", "download"))},
                    resized_ms=round(med(rc), 2), resized_to=f"{S}x{S}",
                    entropy_share=round(leg[0] / med(db), 3),
                    speedup_b=round(med(ha) / med(db), 2), speedup_c=round(med(ha) / med(rc), 2))

@@ -9,7 +9,7 @@
   device_host_ms     (b') the same into PINNED host memory: the call ends in a stream synchronise
   legs_ms            (b') split (me_last_png_timing): inflate on the host (wall clock, the uploads and launches are queued
                      from inside it), uploads, unfilter launches, finish kernel, download -- the four device legs by HIP
-                     events, summed over the bands
+                     events, summed over the bands; legs_ms_range: each leg's smallest and largest value over the repeats
   hidden             whether the unfilter launches hide under the inflate: device_ms - legs_ms.inflate is what is left
                      behind the inflate's end (tail_ms)
 
@@ -115,6 +115,8 @@ def main():
                    device_host_ms=round(med(dh), 2), device_host_ms_min=round(min(dh), 2), device_host_ms_max=round(max(dh), 2),
                    legs_ms=dict(inflate=round(leg[0], 2), uploads=round(leg[1], 3), unfilter=round(leg[2], 3),
                                 finish=round(leg[3], 3), download=round(leg[4], 3)),
+                   legs_ms_range={k: [round(min(v[i] for v in legs), 3), round(max(v[i] for v in legs), 3)]
+                                  for i, k in enumerate(("inflate", "uploads", "unfilter", "finish", "download"))},
                    tail_ms=round(tail, 2), hidden=bool(leg[2] > 2 * max(tail - leg[3], 0.0)),
                    device_recon_vs_host_recon=round((leg[2] + leg[3]) / max(med(ha) - med(hi), 1e-9), 3),
                    speedup=round(med(ha) / med(db), 2), speedup_to_host=round(med(ha) / med(dh), 2))
