@@ -1,7 +1,8 @@
 // extern "C" boundary of libmatrixeyes_hip.so (include/matrix_eyes_hip.h, matrix_eyes_hip_ops.h).
 // Every entry point converts internal me::Error into a status code + last_error text (model.h
-// ME_API_BEGIN / ME_API_END); nothing throws or aborts across the boundary.  The raster and file
-// entries of the output back end are in output_api.hip, the photo-input entries in input_api.hip.
+// ME_API_BEGIN / ME_API_END); nothing throws or aborts across the boundary.  The clamp, raster and file
+// entries of the output back end are in output_api.hip, its mesh entries in mesh_writer.hip (the write-behind
+// ones in file_write.hip), the photo-input entries in input_api.hip.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -873,83 +874,6 @@ int32_t me_ctx_set_graph(me_ctx* ctx, int32_t on) {
     ME_API_END(ctx)
 }
 int64_t me_graph_launch_count(const me_ctx* ctx) { return ctx ? ctx->graph_launches : 0; }
-
-// ---- output back end ---------------------------------------------------------------------
-int32_t me_depth_clamp_minmax(me_ctx* ctx, float* depth, int64_t count, float* min_out,
-                              float* max_out) {
-    ME_API_BEGIN(ctx)
-    OutputScope out_scope(ctx, depth);
-    ME_CHECK(depth && count > 0, ME_ERR_BAD_ARG, "me_depth_clamp_minmax: bad argument");
-    const bool dev = is_device_ptr(depth);
-    float* d = dev ? depth : (float*)site_buf(ctx, "out.depth", (size_t)count * 4);
-    if (!dev) ME_HIP(hipMemcpyAsync(d, depth, (size_t)count * 4, hipMemcpyHostToDevice, ctx->stream));
-    float* mm = (float*)site_buf(ctx, "out.minmax", 8);
-    depth_clamp_minmax_launch(d, count, mm, ctx->stream);
-    float host[2];
-    ME_HIP(hipMemcpyAsync(host, mm, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (!dev) ME_HIP(hipMemcpyAsync(depth, d, (size_t)count * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ME_HIP(hipStreamSynchronize(ctx->stream));
-    if (min_out) *min_out = host[0];
-    if (max_out) *max_out = host[1];
-    ME_API_END(ctx)
-}
-
-int32_t me_depth_clamp_minmax_async(me_ctx* ctx, float* depth, int64_t count, float* minmax_dev) {
-    ME_API_BEGIN(ctx)
-    OutputScope out_scope(ctx, depth);
-    ME_CHECK(depth && minmax_dev && count > 0, ME_ERR_BAD_ARG, "me_depth_clamp_minmax_async: bad argument");
-    ME_CHECK(is_device_ptr(depth) && is_device_ptr(minmax_dev), ME_ERR_BAD_ARG,
-             "me_depth_clamp_minmax_async: depth and minmax_dev must be device memory");
-    depth_clamp_minmax_launch(depth, count, minmax_dev, ctx->stream);
-    ME_API_END(ctx)
-}
-
-int32_t me_mesh_index(me_ctx* ctx, const float* depth, int32_t width, int32_t height,
-                      int32_t* vertex_index, int64_t* nvertices, int64_t* nfaces, int32_t* faces) {
-    ME_API_BEGIN(ctx)
-    OutputScope out_scope(ctx, depth);
-    ME_CHECK(depth && vertex_index && nvertices && nfaces, ME_ERR_BAD_ARG,
-             "me_mesh_index: null pointer");
-    ME_CHECK(width >= 2 && height >= 2, ME_ERR_BAD_SHAPE, "me_mesh_index: %dx%d", width, height);
-    const size_t nv = (size_t)width * height;
-    const size_t nt = 2 * (size_t)(width - 1) * (height - 1);
-    const float* d = (const float*)to_device(ctx, depth, nv * 4, "out.depth");
-    OutBuf ov = out_buf(ctx, vertex_index, nv * 4, "out.vindex");
-    OutBuf of;
-    if (faces) of = out_buf(ctx, faces, nt * 3 * 4, "out.faces");
-    mesh_index_run(d, width, height, (int32_t*)ov.dev, faces ? (int32_t*)of.dev : nullptr, nvertices,
-                   nfaces, site_buf(ctx, "out.mesh.ws", mesh_workspace_bytes(width, height)), ctx->stream);
-    finish(ctx, ov);
-    if (faces && of.staged) {  // only the kept triangles are defined
-        ME_HIP(hipMemcpyAsync(faces, of.dev, (size_t)*nfaces * 12, hipMemcpyDeviceToHost,
-                              ctx->stream));
-        ME_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    ME_API_END(ctx)
-}
-
-int32_t me_mesh_vertices(me_ctx* ctx, const float* depth, int32_t width, int32_t height,
-                         const int32_t* vertex_index, int64_t nvertices, uint32_t original_width,
-                         uint32_t original_height, float* uv, float* xyz) {
-    ME_API_BEGIN(ctx)
-    OutputScope out_scope(ctx, depth);
-    ME_CHECK(depth && vertex_index && nvertices >= 0, ME_ERR_BAD_ARG, "me_mesh_vertices: bad argument");
-    ME_CHECK(original_width > 0 && original_height > 0, ME_ERR_BAD_ARG, "original size 0");
-    const size_t nv = (size_t)width * height;
-    const float* d = (const float*)to_device(ctx, depth, nv * 4, "out.depth");
-    const int32_t* vi = (const int32_t*)to_device(ctx, vertex_index, nv * 4, "out.vindex");
-    // output.rs:222-225 (f32 division of the u32 sizes)
-    const uint32_t mx = original_width > original_height ? original_width : original_height;
-    const float xm = (float)original_width / (float)mx, ym = (float)original_height / (float)mx;
-    OutBuf ouv, oxyz;
-    if (uv) ouv = out_buf(ctx, uv, (size_t)nvertices * 8 + 8, "out.uv");
-    if (xyz) oxyz = out_buf(ctx, xyz, (size_t)nvertices * 12 + 12, "out.xyz");
-    mesh_vertices_launch(d, width, height, vi, xm, ym, uv ? (float*)ouv.dev : nullptr,
-                         xyz ? (float*)oxyz.dev : nullptr, ctx->stream);
-    if (uv && ouv.staged) from_device(ctx, uv, ouv.dev, (size_t)nvertices * 8);
-    if (xyz && oxyz.staged) from_device(ctx, xyz, oxyz.dev, (size_t)nvertices * 12);
-    ME_API_END(ctx)
-}
 
 // ---- kernel-level surface (matrix_eyes_hip_ops.h) -------------------------------------------
 static unsigned long long* g_stamps = nullptr;  // diagnostic builds (-DME_GEMM_STAMPS) only

@@ -273,8 +273,8 @@ struct me_ctx {
     int32_t ln_fallbacks = 0;     // steps re-run because of it (me_ln_fusion_state)
     std::string ln_fuse_note;     // logged once: why fusion went off
 
-    // Write-behind of OBJ files (me_ctx_set_write_behind): the text of mesh call i is written to its file by a host
-    // thread while the caller goes on to image i + 1.  One slot = a pinned host staging buffer (the OBJ text's D2H
+    // Write-behind of mesh files (me_ctx_set_write_behind; file_write.hip): the bytes of mesh call i are written to their
+    // file by a host thread while the caller goes on to image i + 1.  One slot = a pinned host staging buffer (the file's D2H
     // copy, mesh_writer.hip) + the write that reads it; slot 0 alone serves the synchronous form.  Slots are used in
     // turn, so at most `write_behind` writes are in flight.  A failed write is reported by the call that next waits
     // for it (a later me_output_mesh reusing the slot, or me_output_flush).
@@ -290,8 +290,9 @@ struct me_ctx {
     };
     std::vector<WriteSlot> write_slots = std::vector<WriteSlot>(1);
     int write_next = 0;
-    // legs of the last me_output_mesh(".obj") call, host wall clock: [0] mesh indexing + vertex kernels, [1] text
-    // formatting kernels, [2] D2H copy of the text, [3] file write (me_last_mesh_timing)
+    // legs of the last me_output_mesh call that made its file on the device (.obj or .ply), host wall clock: [0] mesh
+    // indexing + vertex kernels, [1] the kernels that format the text or pack the records, [2] D2H copy of the file,
+    // [3] file write, or handing it to the write-behind thread (me_last_mesh_timing)
     double mesh_ms[4] = {0, 0, 0, 0};
     int64_t mesh_bytes = 0;
 
@@ -542,6 +543,36 @@ DeviceFile png_encode_device(me_ctx* ctx, const uint8_t* rgb_dev, int32_t w, int
 void check_jpeg_encode_args(const char* who, int32_t w, int32_t h, int32_t quality, int32_t subsampling);
 DeviceFile jpeg_encode_device(me_ctx* ctx, const uint8_t* rgb_any, int32_t w, int32_t h, int32_t quality, int32_t subsampling);
 void free_jpeg_encode_scratch(me_ctx* ctx);
+
+// file_write.hip: files written from host memory.
+// A file serialised on the host: `head`, then each section's items in order; item(args, i, out) appends item i.  With
+// `threads`, chunks of 32 Ki items are serialised by up to 12 threads and written with pwrite (the sequential loop's bytes).
+typedef void (*AppendItem)(const void* args, int64_t i, std::string& out);
+struct FileSection {
+    int64_t count;
+    AppendItem item;
+    const void* args;
+    bool threads;
+};
+void write_sections(const std::string& path, const std::string& head, const FileSection* sections, int count);
+// a finished buffer into a new file, 8 MiB chunks by ME_WRITE_THREADS (default 2) threads
+void write_bytes_parallel(const std::string& path, const char* data, size_t bytes);
+// Buffers that follow the size of each image's file grow in 64 MiB steps, so that a sequence of images settles
+inline size_t grow_in_steps(size_t bytes) { return (bytes + ((size_t)64 << 20) - 1) / ((size_t)64 << 20) * ((size_t)64 << 20); }
+// The write slots of me_ctx (write-behind): slot k's pinned staging buffer of at least `bytes`; the wait for slot k's pending
+// write, whose failure is thrown here ("write-behind: ...")
+char* pinned_buf(me_ctx* ctx, size_t bytes, int slot);
+void join_pending_write(me_ctx* ctx, int slot);
+// A file whose bytes lie in slot `slot`'s pinned buffer, and a small text file written behind it (the .mtl; side_path
+// empty: none).  write_pinned_file writes both before it returns, or (behind) starts the slot's thread that does.
+struct PinnedFile {
+    std::string dest;
+    const char* data = nullptr;
+    size_t bytes = 0;
+    int slot = 0;
+    std::string side_path, side_text;
+};
+void write_pinned_file(me_ctx* ctx, const PinnedFile& file, bool behind);
 
 // calibrate.hip: the two fixed loops of bench.py's calibration leg (out[6])
 void calibrate(me_ctx* ctx, double* out);

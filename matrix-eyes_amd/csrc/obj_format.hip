@@ -11,7 +11,7 @@
 //            lengths and copied out as aligned 16-byte chunks (byte stores only at a workgroup's ragged ends).
 // Formatting twice costs ~200 integer instructions per number and saves a 200-byte slot per line in HBM.
 #include "model.h"
-#include "ryu_f64.h"
+#include "obj_format.h"
 #include "scan.h"
 
 namespace me {
@@ -19,64 +19,7 @@ namespace me {
 namespace {
 
 constexpr int kThreads = 128;
-// longest line of each section.  A number that came from an f32 (every coordinate; 1 - v is an exact f64 difference
-// of one) prints in at most 64 characters: sign, "0.", 44 zeros, 17 digits; a colour c / 255.0 in 20.
-constexpr int kSlotVt = 136;   // "vt " + 64 + ' ' + 64 + '\n'
-constexpr int kSlotV = 264;    // "v " + 3 x (64 + ' ') + 3 x (20 + ' ') + '\n'
-constexpr int kSlotF = 72;     // 'f' + 3 x (' ' + 10 + '/' + 10) + '\n'
-
-struct ObjArgs {
-    const float* uv;         // [count][2]  (vt)
-    const float* xyz;        // [count][3]  (v)
-    const uint8_t* colors;   // per vertex id [count][3], or null
-    const int32_t* faces;    // [count][3]  (f)
-    int64_t count;           // lines of this section
-    int tex;                 // f: "a/a" pairs
-};
-
 typedef __attribute__((address_space(3))) char lds_char;
-
-template <int SEC>
-__device__ __forceinline__ int format_line(const ObjArgs& a, int64_t i, char* out) {
-    int n = 0;
-    if constexpr (SEC == 0) {  // output.rs:592-602: vt u (1 - v), both widened to f64 first
-        out[0] = 'v', out[1] = 't', out[2] = ' ';
-        n = 3;
-        n += ryu::format_fixed((double)a.uv[2 * i], out + n);
-        out[n++] = ' ';
-        n += ryu::format_fixed(1.0 - (double)a.uv[2 * i + 1], out + n);
-    } else if constexpr (SEC == 1) {  // output.rs:566-590: v x -y -z [r g b]
-        out[0] = 'v', out[1] = ' ';
-        n = 2;
-        n += ryu::format_fixed((double)a.xyz[3 * i], out + n);
-        out[n++] = ' ';
-        n += ryu::format_fixed((double)(-a.xyz[3 * i + 1]), out + n);
-        out[n++] = ' ';
-        n += ryu::format_fixed((double)(-a.xyz[3 * i + 2]), out + n);
-        if (a.colors) {
-#pragma unroll 1
-            for (int c = 0; c < 3; ++c) {
-                out[n++] = ' ';
-                n += ryu::format_fixed((double)a.colors[3 * i + c] / 255.0, out + n);
-            }
-        }
-    } else {  // output.rs:604-620: f a/a b/b c/c, 1-based
-        out[0] = 'f';
-        n = 1;
-#pragma unroll 1
-        for (int k = 0; k < 3; ++k) {
-            const uint64_t idx = (uint64_t)a.faces[3 * i + k] + 1;
-            out[n++] = ' ';
-            n += ryu::format_u64(idx, out + n);
-            if (a.tex) {
-                out[n++] = '/';
-                n += ryu::format_u64(idx, out + n);
-            }
-        }
-    }
-    out[n++] = '\n';
-    return n;
-}
 
 // WRITE = false: block_bytes[first_block + blockIdx.x] = bytes of this workgroup's lines.
 // WRITE = true: the lines, packed, at text + block_off[first_block + blockIdx.x].

@@ -1,4 +1,4 @@
-// The raster and file entries of the output back end (include/matrix_eyes_hip.h): the stereogram and the colour map of
+// The clamp, raster and file entries of the output back end (include/matrix_eyes_hip.h): the stereogram and the colour map of
 // output.rs:123-193 as pictures, and RgbImage::save (:138, :192) of either, or of a caller's picture, to a PNG or JPEG file
 // encoded on the device.  Host code only: the kernels are those of output.hip, resample.hip, png_encode.hip and
 // jpeg_encode.hip, and every chain of them is spelled out once here.
@@ -79,6 +79,36 @@ void depthmap_rgb_impl(me_ctx* ctx, const float* depth, int64_t count, float min
 }  // namespace
 
 extern "C" {
+
+// ---- the clamp every output starts from (output.rs:51-62) ----------------------------------------------------------
+int32_t me_depth_clamp_minmax(me_ctx* ctx, float* depth, int64_t count, float* min_out,
+                              float* max_out) {
+    ME_API_BEGIN(ctx)
+    OutputScope out_scope(ctx, depth);
+    ME_CHECK(depth && count > 0, ME_ERR_BAD_ARG, "me_depth_clamp_minmax: bad argument");
+    const bool dev = is_device_ptr(depth);
+    float* d = dev ? depth : (float*)site_buf(ctx, "out.depth", (size_t)count * 4);
+    if (!dev) ME_HIP(hipMemcpyAsync(d, depth, (size_t)count * 4, hipMemcpyHostToDevice, ctx->stream));
+    float* mm = (float*)site_buf(ctx, "out.minmax", 8);
+    depth_clamp_minmax_launch(d, count, mm, ctx->stream);
+    float host[2];
+    ME_HIP(hipMemcpyAsync(host, mm, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (!dev) ME_HIP(hipMemcpyAsync(depth, d, (size_t)count * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ME_HIP(hipStreamSynchronize(ctx->stream));
+    if (min_out) *min_out = host[0];
+    if (max_out) *max_out = host[1];
+    ME_API_END(ctx)
+}
+
+int32_t me_depth_clamp_minmax_async(me_ctx* ctx, float* depth, int64_t count, float* minmax_dev) {
+    ME_API_BEGIN(ctx)
+    OutputScope out_scope(ctx, depth);
+    ME_CHECK(depth && minmax_dev && count > 0, ME_ERR_BAD_ARG, "me_depth_clamp_minmax_async: bad argument");
+    ME_CHECK(is_device_ptr(depth) && is_device_ptr(minmax_dev), ME_ERR_BAD_ARG,
+             "me_depth_clamp_minmax_async: depth and minmax_dev must be device memory");
+    depth_clamp_minmax_launch(depth, count, minmax_dev, ctx->stream);
+    ME_API_END(ctx)
+}
 
 int32_t me_stereogram(me_ctx* ctx, const float* depth, int32_t rows, int32_t cols, float min_depth,
                       float max_depth, int32_t out_w, int32_t out_h, float amplitude,

@@ -66,7 +66,5 @@ void load_weight_arena(me_ctx* ctx, const char* path, const char* source_path);
 std::string weight_cache_path(me_ctx* ctx, const char* checkpoint_path);
 // where: WeightSource
 void load_checkpoint_cached(me_ctx* ctx, const char* checkpoint_path, bool convert, int32_t* where);
-// mesh_writer.hip: its write_file_parallel
-void write_bytes_parallel(const std::string& path, const char* data, size_t bytes);
 
 }  // namespace me

@@ -499,3 +499,68 @@ def test_obj_text_on_device_equals_the_file_and_the_oracle(tmp_path, mode):
         vcol[vi[vi >= 0]] = flat[vi >= 0]
     assert nv > 1000 and len(faces) > 1000
     assert text.decode() == OO.obj_text(uv, xyz, faces, mode, "scene", vcol)
+
+
+# (name, n, seed of _depth, vertex mode, colours): scenes of tests/test_gpu_ply.py SCENES
+_OBJ_HOST_CASES = (("texture257", 257, 259, "texture", False), ("color257", 257, 259, "color", True), ("plain16", 16, 1, "plain", False))
+_OBJ_HOST_CHILD = """
+import ctypes as C, sys, numpy as np
+sys.path.insert(0, sys.argv[1])
+import matrix_eyes_amd as m
+z = np.load(sys.argv[2])
+ctx = m.Context(0, "f16", m.ModelConfig.tiny())
+for name, mode in zip(sys.argv[4::2], sys.argv[5::2]):
+    depth, colors = z[name + ".depth"], z[name + ".pixels"] if name + ".pixels" in z else None
+    n = depth.shape[0]
+    ctx._check(ctx.lib.me_output_mesh(ctx.handle, C.c_void_p(depth.ctypes.data), n, n, 3 * n, 2 * n,
+                                      (sys.argv[3] + "/" + name + ".obj").encode(), b"photos/in.jpg", int(mode),
+                                      C.c_void_p(colors.ctypes.data) if colors is not None else None))
+"""
+
+
+def test_obj_host_serialiser_writes_the_device_path_files(tmp_path):
+    """ME_OBJ_HOST_FORMAT=1 (a child process: the knob is read once): me_output_mesh(".obj") through the host serialiser
+    writes the files of the device path and of the oracle, the .mtl of a textured mesh included.  65407 vertices are two
+    32 Ki chunks of the vt and v sections and more of f, so several threads format and pwrite them; the 16 x 16 map's
+    sections are single chunks, written by the sequential loop."""
+    import ctypes as C
+    import subprocess
+    import sys
+    ctx = _ctx()
+    modes = {"plain": m.VertexMode.Plain, "color": m.VertexMode.Color, "texture": m.VertexMode.Texture}
+    arrays, want = {}, {}
+    (tmp_path / "host").mkdir()
+    (tmp_path / "device").mkdir()
+    for name, n, seed, mode, coloured in _OBJ_HOST_CASES:
+        dm = m.DepthMap(ctx, _depth(n, seed=seed), (3 * n, 2 * n))
+        pixels = np.random.default_rng(5).integers(0, 256, size=(n, n, 3), dtype=np.uint8) if coloured else None
+        arrays[name + ".depth"] = dm.data
+        if coloured:
+            arrays[name + ".pixels"] = pixels
+        vi, nv, faces = OO.mesh_index(dm.data)
+        uv, xyz = OO.mesh_vertices(dm.data, vi, nv, (3 * n, 2 * n))
+        assert nv == {257: 65407, 16: 66}[n] and (n == 16 or len(faces) > 2 * 32768)
+        vcol = None
+        if coloured:
+            vcol = np.zeros((nv, 3), np.uint8)
+            vcol[vi[vi >= 0]] = pixels.reshape(-1, 3)[vi >= 0]
+        want[name] = OO.obj_text(uv, xyz, faces, mode, name, vcol).encode()
+        ctx._check(ctx.lib.me_output_mesh(ctx.handle, C.c_void_p(dm.data.ctypes.data), n, n, 3 * n, 2 * n,
+                                          str(tmp_path / "device" / f"{name}.obj").encode(), b"photos/in.jpg", int(modes[mode]),
+                                          C.c_void_p(pixels.ctypes.data) if coloured else None))
+    np.savez(tmp_path / "in.npz", **arrays)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    argv = [a for name, _, _, mode, _ in _OBJ_HOST_CASES for a in (name, str(int(modes[mode])))]
+    r = subprocess.run([sys.executable, "-c", _OBJ_HOST_CHILD, root, str(tmp_path / "in.npz"), str(tmp_path / "host")] + argv,
+                       env=dict(os.environ, ME_OBJ_HOST_FORMAT="1"), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    for name, _, _, mode, _ in _OBJ_HOST_CASES:
+        host = (tmp_path / "host" / f"{name}.obj").read_bytes()
+        assert host == (tmp_path / "device" / f"{name}.obj").read_bytes(), name
+        assert host == want[name], name
+        for side in ("host", "device"):
+            mtl = tmp_path / side / f"{name}.mtl"
+            if mode == "texture":
+                assert mtl.read_text() == OO.mtl_text("photos/in.jpg"), (name, side)
+            else:
+                assert not mtl.exists(), (name, side)

@@ -7,7 +7,7 @@ line per (scene, vertex mode):
                in a child process that holds its own context on the same GPU and is asked for ONE call at a time:
                the two arms alternate, and never use the GPU at the same moment.
   device_ms    the whole call on the device path: mesh kernels, ply_format.hip, one D2H copy into pinned memory,
-               write_file_parallel.  mesh_ms / format_ms / d2h_ms / file_ms: the four legs of me_last_mesh_timing
+               write_bytes_parallel (file_write.hip).  mesh_ms / format_ms / d2h_ms / file_ms: the four legs of me_last_mesh_timing
                (medians over the same calls).
   copy_ms      a plain device-to-device copy of `bytes` bytes, wall clock around the copy and a synchronise like
                format_ms: what the packing kernel would cost if it only moved the file's bytes

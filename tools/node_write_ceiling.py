@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Host ceiling of the configs[4] chain per NODE: P processes -- one per GPU rank -- each writing OBJ-sized
-files to one tmpfs the way the library's write-behind threads do (mesh_writer.hip write_file_parallel: T threads of pwrite
+files to one tmpfs the way the library's write-behind threads do (file_write.hip write_bytes_parallel: T threads of pwrite
 over one file, from a buffer in host memory), no GPU involved.  Prints files/s and GB/s per process count.
 
     python3 tools/node_write_ceiling.py [dir=/dev/shm] [MB per file=110] [seconds per point=4]
