@@ -313,6 +313,45 @@ int32_t me_stereogram_dev_range(me_ctx* ctx, const float* depth, int32_t rows, i
                                 const float* minmax_dev, int32_t out_w, int32_t out_h, float amplitude,
                                 const uint8_t* noise, uint8_t* out);
 
+/* ---- keyed stereogram noise (csrc/chacha.h) ------------------------------------------------------- */
+
+/* "Keyed noise" maps a 32-byte key and a size to u8 [out_h,out_w,3]: pixel i = y * out_w + x takes word i & 15 of ChaCha12
+   block i >> 4 of the key's stream (64-bit block counter, zero nonce), and R, G, B are the word's three low bytes.  The
+   definition is this library's own (it stands in for the reference's rand::rng(), output.rs:163-171, and claims parity with
+   no other generator); the kernels and the host twin below share its one text and write the same bytes.
+
+   The key of a seed: eight steps of a 64-bit LCG, one xorshift-rotate output of four little-endian bytes per step.  Needs
+   neither a GPU nor a context (ctx-less errors: me_last_error(NULL)); a null pointer is ME_ERR_BAD_ARG. */
+int32_t me_noise_key_from_seed(uint64_t seed, uint8_t key[32]);
+/* 32 bytes from the operating system (getrandom); a failure of that call is ME_ERR_IO.  No GPU, no context. */
+int32_t me_noise_key_from_os(uint8_t key[32]);
+/* The CPU twin of me_stereogram_noise on the calling thread: out [out_h,out_w,3] in host memory.  No GPU, no context; a null
+   pointer is ME_ERR_BAD_ARG, a non-positive size ME_ERR_BAD_SHAPE. */
+int32_t me_stereogram_noise_host(const uint8_t key[32], int32_t out_w, int32_t out_h, uint8_t* out);
+/* The noise picture made on the GPU, one ChaCha block per lane: key 32 bytes of HOST memory (it travels as kernel
+   arguments); out [out_h,out_w,3], a host or device pointer; enqueued on the context's stream: a device out is not
+   synchronised, a host out is.  Sizes as me_stereogram: out_w > 16384 or a non-positive size is ME_ERR_BAD_SHAPE; a null
+   key or out is ME_ERR_BAD_ARG.  Needs a context, not finalised weights. */
+int32_t me_stereogram_noise(me_ctx* ctx, const uint8_t key[32], int32_t out_w, int32_t out_h, uint8_t* out);
+/* me_stereogram with the noise made from `key` on the device: equal, byte for byte, to me_stereogram fed
+   me_stereogram_noise_host(key, out_w, out_h), without that buffer existing on the host.  Two launches on the same stream:
+   the fill kernel of me_stereogram_noise into context-owned device memory (it grows to the high-water mark), then the
+   stereogram kernel (a kernel that made each row's words in place did not beat the pair and was not kept).
+   Arguments, refusals and stream as me_stereogram -- a refused call launches nothing; key is HOST memory and travels as
+   kernel arguments, so a captured graph replays it. */
+int32_t me_stereogram_keyed(me_ctx* ctx, const float* depth, int32_t rows, int32_t cols, float min_depth,
+                            float max_depth, int32_t out_w, int32_t out_h, float amplitude,
+                            const uint8_t key[32], uint8_t* out);
+/* me_stereogram_dev_range with the noise made from `key`. */
+int32_t me_stereogram_keyed_dev_range(me_ctx* ctx, const float* depth, int32_t rows, int32_t cols,
+                                      const float* minmax_dev, int32_t out_w, int32_t out_h, float amplitude,
+                                      const uint8_t key[32], uint8_t* out);
+/* The context's last keyed-noise launch.  report: [0] the path taken (1: the fill kernel into the destination of
+   me_stereogram_noise; 2: the fill kernel into the context's scratch behind a keyed stereogram entry; there is no fused or
+   fallback path), [1] the noise words generated (16 per ChaCha block).  *kernel_ms: the fill kernel's HIP event time.
+   Synchronises the context's streams; ME_ERR_NOT_READY before the first such launch. */
+int32_t me_last_stereogram_noise(me_ctx* ctx, int64_t report[2], double* kernel_ms);
+
 /* output.rs:123-131 + 633-714 map_depth: depth [count] -> rgb [count,3] (before the Lanczos
    resize, which is the identity at the native size). */
 int32_t me_depthmap_rgb(me_ctx* ctx, const float* depth, int64_t count, float min_depth,
@@ -371,6 +410,10 @@ int32_t me_output_depth_map_png(me_ctx* ctx, const float* depth, int32_t data_wi
 int32_t me_output_stereogram_png(me_ctx* ctx, const float* depth, int32_t rows, int32_t cols, float min_depth,
                                  float max_depth, int32_t out_w, int32_t out_h, float amplitude,
                                  const uint8_t* noise, const char* destination_path);
+/* The same with the noise made from `key` (me_stereogram_keyed): arguments, refusals and stream as me_output_stereogram_png. */
+int32_t me_output_stereogram_png_keyed(me_ctx* ctx, const float* depth, int32_t rows, int32_t cols, float min_depth,
+                                       float max_depth, int32_t out_w, int32_t out_h, float amplitude,
+                                       const uint8_t key[32], const char* destination_path);
 
 /* ---- JPEG encoding on the device (RgbImage::save to ".jpg" / ".jpeg") -------------------------------------------------- */
 
@@ -400,6 +443,12 @@ int32_t me_output_stereogram_jpeg(me_ctx* ctx, const float* depth, int32_t rows,
                                   float max_depth, int32_t out_w, int32_t out_h, float amplitude,
                                   const uint8_t* noise, int32_t quality, int32_t subsampling,
                                   const char* destination_path);
+/* The same with the noise made from `key` (me_stereogram_keyed): arguments, refusals and stream as
+   me_output_stereogram_jpeg. */
+int32_t me_output_stereogram_jpeg_keyed(me_ctx* ctx, const float* depth, int32_t rows, int32_t cols, float min_depth,
+                                        float max_depth, int32_t out_w, int32_t out_h, float amplitude,
+                                        const uint8_t key[32], int32_t quality, int32_t subsampling,
+                                        const char* destination_path);
 
 /* ---- JPEG decoding on the device (reconstruction.rs:95-113: ImageReader::open(..).decode(), apply_orientation) --------- */
 

@@ -277,6 +277,11 @@ int32_t me_op_weight_pack(me_ctx* ctx, int32_t kind, int32_t dup, const int64_t*
    dimensions that do not fit the kind (-3). */
 int32_t me_op_weight_pack_host(int32_t dtype, int32_t kind, int32_t dup, const int64_t* dims, int32_t ndim, const void* src,
                                int32_t src_dtype, void* dst);
+/* The legacy stereogram noise of the C++ host layer (host/matrix_eyes.cpp DepthMap::output_stereogram: std::mt19937(seed),
+   four little-endian bytes per draw) into out [nbytes]: the same loop compiled into the library, so that
+   tools/bench_stereogram_noise.py can time it in one process beside the keyed noise.  HOST memory, no GPU, no context; a
+   null pointer or a negative size is ME_ERR_BAD_ARG. */
+int32_t me_op_legacy_noise_host(uint32_t seed, int64_t nbytes, uint8_t* out);
 /* Names of the GEMM tile configurations (for reports). */
 int32_t me_op_gemm_config_count(void);
 const char* me_op_gemm_config_name(int32_t cfg);

@@ -112,6 +112,13 @@ extern "C" {
     pub fn me_depth_clamp_minmax_async(ctx: *mut MeCtx, depth: *mut f32, count: i64, minmax_dev: *mut f32) -> i32;
     pub fn me_stereogram(ctx: *mut MeCtx, depth: *const f32, rows: i32, cols: i32, min_depth: f32, max_depth: f32, out_w: i32, out_h: i32, amplitude: f32, noise: *const u8, out: *mut u8) -> i32;
     pub fn me_stereogram_dev_range(ctx: *mut MeCtx, depth: *const f32, rows: i32, cols: i32, minmax_dev: *const f32, out_w: i32, out_h: i32, amplitude: f32, noise: *const u8, out: *mut u8) -> i32;
+    pub fn me_noise_key_from_seed(seed: u64, key: *mut u8) -> i32;
+    pub fn me_noise_key_from_os(key: *mut u8) -> i32;
+    pub fn me_stereogram_noise_host(key: *const u8, out_w: i32, out_h: i32, out: *mut u8) -> i32;
+    pub fn me_stereogram_noise(ctx: *mut MeCtx, key: *const u8, out_w: i32, out_h: i32, out: *mut u8) -> i32;
+    pub fn me_stereogram_keyed(ctx: *mut MeCtx, depth: *const f32, rows: i32, cols: i32, min_depth: f32, max_depth: f32, out_w: i32, out_h: i32, amplitude: f32, key: *const u8, out: *mut u8) -> i32;
+    pub fn me_stereogram_keyed_dev_range(ctx: *mut MeCtx, depth: *const f32, rows: i32, cols: i32, minmax_dev: *const f32, out_w: i32, out_h: i32, amplitude: f32, key: *const u8, out: *mut u8) -> i32;
+    pub fn me_last_stereogram_noise(ctx: *mut MeCtx, report: *mut i64, kernel_ms: *mut f64) -> i32;
     pub fn me_depthmap_rgb(ctx: *mut MeCtx, depth: *const f32, count: i64, min_depth: f32, max_depth: f32, rgb: *mut u8) -> i32;
     pub fn me_depthmap_rgb_dev_range(ctx: *mut MeCtx, depth: *const f32, count: i64, minmax_dev: *const f32, rgb: *mut u8) -> i32;
     pub fn me_resize_lanczos3_rgb8(ctx: *mut MeCtx, src: *const u8, w: i32, h: i32, dst: *mut u8, nw: i32, nh: i32) -> i32;
@@ -130,10 +137,12 @@ extern "C" {
     pub fn me_output_png(ctx: *mut MeCtx, rgb: *const u8, w: i32, h: i32, destination_path: *const c_char) -> i32;
     pub fn me_output_depth_map_png(ctx: *mut MeCtx, depth: *const f32, data_width: i32, data_height: i32, min_depth: f32, max_depth: f32, minmax_dev: *const f32, out_w: i32, out_h: i32, destination_path: *const c_char) -> i32;
     pub fn me_output_stereogram_png(ctx: *mut MeCtx, depth: *const f32, rows: i32, cols: i32, min_depth: f32, max_depth: f32, out_w: i32, out_h: i32, amplitude: f32, noise: *const u8, destination_path: *const c_char) -> i32;
+    pub fn me_output_stereogram_png_keyed(ctx: *mut MeCtx, depth: *const f32, rows: i32, cols: i32, min_depth: f32, max_depth: f32, out_w: i32, out_h: i32, amplitude: f32, key: *const u8, destination_path: *const c_char) -> i32;
     pub fn me_jpeg_encode_rgb8(ctx: *mut MeCtx, rgb: *const u8, w: i32, h: i32, quality: i32, subsampling: i32, jpg_dev: *mut *const u8, nbytes: *mut i64) -> i32;
     pub fn me_output_jpeg(ctx: *mut MeCtx, rgb: *const u8, w: i32, h: i32, quality: i32, subsampling: i32, destination_path: *const c_char) -> i32;
     pub fn me_output_depth_map_jpeg(ctx: *mut MeCtx, depth: *const f32, data_width: i32, data_height: i32, min_depth: f32, max_depth: f32, minmax_dev: *const f32, out_w: i32, out_h: i32, quality: i32, subsampling: i32, destination_path: *const c_char) -> i32;
     pub fn me_output_stereogram_jpeg(ctx: *mut MeCtx, depth: *const f32, rows: i32, cols: i32, min_depth: f32, max_depth: f32, out_w: i32, out_h: i32, amplitude: f32, noise: *const u8, quality: i32, subsampling: i32, destination_path: *const c_char) -> i32;
+    pub fn me_output_stereogram_jpeg_keyed(ctx: *mut MeCtx, depth: *const f32, rows: i32, cols: i32, min_depth: f32, max_depth: f32, out_w: i32, out_h: i32, amplitude: f32, key: *const u8, quality: i32, subsampling: i32, destination_path: *const c_char) -> i32;
     pub fn me_mesh_index(ctx: *mut MeCtx, depth: *const f32, width: i32, height: i32, vertex_index: *mut i32, nvertices: *mut i64, nfaces: *mut i64, faces: *mut i32) -> i32;
     pub fn me_mesh_vertices(ctx: *mut MeCtx, depth: *const f32, width: i32, height: i32, vertex_index: *const i32, nvertices: i64, original_width: u32, original_height: u32, uv: *mut f32, xyz: *mut f32) -> i32;
     pub fn me_mesh_obj_text(ctx: *mut MeCtx, depth: *const f32, width: i32, height: i32, original_width: u32, original_height: u32, stem: *const c_char, vertex_mode: i32, vertex_colors: *const u8, text_dev: *mut *const u8, nbytes: *mut i64) -> i32;

@@ -82,6 +82,15 @@ SIGNATURES = {
     "me_depth_clamp_minmax_async": (_i32, [_vp, _vp, _i64, _vp]),
     "me_stereogram": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _i32, _i32, _f32, _vp, _vp]),
     "me_stereogram_dev_range": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _f32, _vp, _vp]),
+    "me_noise_key_from_seed": (_i32, [C.c_uint64, _vp]),
+    "me_noise_key_from_os": (_i32, [_vp]),
+    "me_stereogram_noise_host": (_i32, [_vp, _i32, _i32, _vp]),
+    "me_stereogram_noise": (_i32, [_vp, _vp, _i32, _i32, _vp]),
+    "me_stereogram_keyed": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _i32, _i32, _f32, _vp, _vp]),
+    "me_stereogram_keyed_dev_range": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _f32, _vp, _vp]),
+    "me_last_stereogram_noise": (_i32, [_vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
+    "me_output_stereogram_png_keyed": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _i32, _i32, _f32, _vp, C.c_char_p]),
+    "me_output_stereogram_jpeg_keyed": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _i32, _i32, _f32, _vp, _i32, _i32, C.c_char_p]),
     "me_depthmap_rgb_dev_range": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "me_depthmap_rgb": (_i32, [_vp, _vp, _i64, _f32, _f32, _vp]),
     "me_resize_lanczos3_rgb8": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _i32]),
@@ -175,6 +184,7 @@ SIGNATURES = {
     "me_last_jpeg_encode": (_i32, [_vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
     "me_op_weight_pack": (_i32, [_vp, _i32, _i32, C.POINTER(_i64), _i32, _vp, _i32, _vp]),
     "me_op_weight_pack_host": (_i32, [_i32, _i32, _i32, C.POINTER(_i64), _i32, _vp, _i32, _vp]),
+    "me_op_legacy_noise_host": (_i32, [_u32, _i64, _vp]),
     "me_op_gemm_config_count": (_i32, []),
     "me_op_gemm_config_name": (C.c_char_p, [_i32]),
 }

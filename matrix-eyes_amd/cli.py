@@ -118,7 +118,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     from ._lib import MatrixEyesError
     from .depth_pro import (DepthProModelLoader, resolve_jpeg_decoder, resolve_jpeg_encoder, resolve_jpeg_entropy,
                             resolve_jpeg_quality, resolve_jpeg_subsampling, resolve_png_decoder, resolve_png_encoder,
-                            resolve_resampler, resolve_weight_packer)
+                            resolve_noise_source, resolve_resampler, resolve_weight_packer)
     from .reconstruction import extract_depth
     try:
         resolve_resampler()                  # MATRIX_EYES_RESAMPLER = pillow | device
@@ -146,9 +146,9 @@ def main(argv: Optional[List[str]] = None) -> int:
         print(f"MATRIX_EYES_JPEG_ENTROPY: {err.message}", file=sys.stderr)
         return 2
     # MATRIX_EYES_WEIGHT_PACKER = host | device; MATRIX_EYES_JPEG_ENCODER = pillow | host | device, _QUALITY = 1..100,
-    # _SUBSAMPLING = 4:4:4 | 4:2:2 | 4:2:0
+    # _SUBSAMPLING = 4:4:4 | 4:2:2 | 4:2:0; MATRIX_EYES_NOISE = legacy | host | device
     for name, resolve in (("MATRIX_EYES_WEIGHT_PACKER", resolve_weight_packer), ("MATRIX_EYES_JPEG_ENCODER", resolve_jpeg_encoder), ("MATRIX_EYES_JPEG_QUALITY", resolve_jpeg_quality),
-                          ("MATRIX_EYES_JPEG_SUBSAMPLING", resolve_jpeg_subsampling)):
+                          ("MATRIX_EYES_JPEG_SUBSAMPLING", resolve_jpeg_subsampling), ("MATRIX_EYES_NOISE", resolve_noise_source)):
         try:
             resolve()
         except MatrixEyesError as err:

@@ -312,6 +312,7 @@ void me_ctx_destroy(me_ctx* ctx) {
     me::free_resample_tables(ctx);
     me::free_jpeg_scratch(ctx);
     me::free_png_scratch(ctx);
+    me::free_stereogram_noise_scratch(ctx);
     me::free_weight_pack(ctx);
     if (ctx->arena) (void)hipFree(ctx->arena);
     if (ctx->arena8) (void)hipFree(ctx->arena8);

@@ -403,6 +403,8 @@ void fov_final_launch(const void* x16 /*NHWC [B][k][k][C]*/, const float* w /*[k
 void depth_clamp_minmax_launch(float* depth, int64_t count, float* minmax_dev /*[2]*/,
                                hipStream_t stream);
 // range_dev: device {min, max} (from depth_clamp_minmax_launch) used instead of the scalars when not null
+// the sizes every stereogram entry accepts (ME_ERR_BAD_SHAPE otherwise); stereogram_launch starts with it
+void stereogram_check_shape(int32_t rows, int32_t cols, int32_t out_w, int32_t out_h);
 void stereogram_launch(const float* depth, int32_t rows, int32_t cols, float min_depth,
                        float max_depth, const float* range_dev, int32_t out_w, int32_t out_h, float amplitude,
                        const uint8_t* noise, uint8_t* out, hipStream_t stream);

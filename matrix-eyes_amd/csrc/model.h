@@ -402,6 +402,12 @@ struct me_ctx {
     int32_t png_timed_bands = 0;
     bool png_timed = false, png_timed_download = false;
     double png_inflate_ms = 0.0;
+    // The keyed stereogram noise (stereogram_noise.hip; me_last_stereogram_noise), behind the photo fields for the same
+    // reason: who asked for the last fill (0 nobody yet, 1 me_stereogram_noise, 2 a keyed stereogram entry), the words it
+    // generated and the marks around the kernel
+    int32_t stereo_noise_path = 0;
+    int64_t stereo_noise_words = 0;
+    me::LegMarks stereo_noise_marks;
 
     // geometry helpers
     int g() const { return cfg.grid; }
@@ -543,6 +549,15 @@ DeviceFile png_encode_device(me_ctx* ctx, const uint8_t* rgb_dev, int32_t w, int
 void check_jpeg_encode_args(const char* who, int32_t w, int32_t h, int32_t quality, int32_t subsampling);
 DeviceFile jpeg_encode_device(me_ctx* ctx, const uint8_t* rgb_any, int32_t w, int32_t h, int32_t quality, int32_t subsampling);
 void free_jpeg_encode_scratch(me_ctx* ctx);
+// stereogram_noise.hip: the keyed noise (chacha.h) on ctx->stream, device pointers.  The fill writes [out_h][out_w][3]
+// (path: what me_last_stereogram_noise reports, 1 the noise entry, 2 a keyed entry); the keyed launch is stereogram_launch
+// (its checks first) with the 32-byte key in place of the noise buffer: the fill into the context's "out.noise", then that.
+void stereogram_noise_fill_launch(me_ctx* ctx, const uint8_t key[32], int32_t out_w, int32_t out_h, uint8_t* out_dev,
+                                  int32_t path);
+void stereogram_keyed_launch(me_ctx* ctx, const float* depth_dev, int32_t rows, int32_t cols, float min_depth, float max_depth,
+                             const float* range_dev, int32_t out_w, int32_t out_h, float amplitude, const uint8_t key[32],
+                             uint8_t* out_dev);
+void free_stereogram_noise_scratch(me_ctx* ctx);
 
 // file_write.hip: files written from host memory.
 // A file serialised on the host: `head`, then each section's items in order; item(args, i, out) appends item i.  With

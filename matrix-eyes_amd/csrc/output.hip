@@ -424,9 +424,7 @@ void depth_clamp_minmax_launch(float* depth, int64_t count, float* minmax_dev, h
     ME_HIP(hipGetLastError());
 }
 
-void stereogram_launch(const float* depth, int32_t rows, int32_t cols, float min_depth,
-                       float max_depth, const float* range_dev, int32_t out_w, int32_t out_h, float amplitude,
-                       const uint8_t* noise, uint8_t* out, hipStream_t stream) {
+void stereogram_check_shape(int32_t rows, int32_t cols, int32_t out_w, int32_t out_h) {
     ME_CHECK(out_w > 0 && out_h > 0 && rows > 0 && cols > 0, ME_ERR_BAD_SHAPE,
              "stereogram: %dx%d from %dx%d", out_w, out_h, rows, cols);
     ME_CHECK(out_w <= 16384, ME_ERR_BAD_SHAPE, "stereogram: width %d > 16384", out_w);
@@ -436,6 +434,12 @@ void stereogram_launch(const float* depth, int32_t rows, int32_t cols, float min
              "stereogram: a %dx%d depth map (rows x cols) has more columns than rows: the reference's sampler indexes "
              "data[cols * y + x] past the end of such a map and panics (output.rs:79); rows >= cols is required",
              rows, cols);
+}
+
+void stereogram_launch(const float* depth, int32_t rows, int32_t cols, float min_depth,
+                       float max_depth, const float* range_dev, int32_t out_w, int32_t out_h, float amplitude,
+                       const uint8_t* noise, uint8_t* out, hipStream_t stream) {
+    stereogram_check_shape(rows, cols, out_w, out_h);
     int rounds = 1;
     while ((1 << rounds) < out_w) ++rounds;
     const size_t lds = (size_t)out_w * 2 * sizeof(int);

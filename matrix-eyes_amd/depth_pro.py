@@ -160,6 +160,38 @@ def resolve_weight_packer(weight_packer=None) -> str:
     return _resolve_choice(weight_packer, "MATRIX_EYES_WEIGHT_PACKER", "host", WEIGHT_PACKERS, "weight packer")
 
 
+NOISE_SOURCES = ("legacy", "host", "device")
+
+
+def resolve_noise_source(noise_source=None) -> str:
+    """Where a stereogram's noise comes from when the caller passes none: "legacy" (the default: numpy's PCG64 seeded with
+    MATRIX_EYES_SEED or the OS, today's bytes), "host" (the keyed ChaCha12 noise of DESIGN.md §4.41 made by
+    me_stereogram_noise_host on one core, then today's calls) or "device" (the keyed entries: the noise is made by a fill
+    kernel in device scratch, no noise buffer exists on the host).  "host" and "device" write the same pixels for the same key.
+    None reads MATRIX_EYES_NOISE; anything but the three names is an argument error."""
+    return _resolve_choice(noise_source, "MATRIX_EYES_NOISE", "legacy", NOISE_SOURCES, "noise source")
+
+
+def noise_key(lib, key=None) -> bytes:
+    """The 32-byte key of the keyed noise: `key` itself, or -- None -- MATRIX_EYES_SEED as a full unsigned 64-bit decimal
+    expanded by me_noise_key_from_seed; unset: 32 bytes from the OS (os.urandom)."""
+    if key is not None:
+        key = bytes(key)
+        if len(key) != 32:
+            raise L.MatrixEyesError(1, f"noise key: 32 bytes expected, got {len(key)}")
+        return key
+    seed = os.environ.get("MATRIX_EYES_SEED")
+    if not seed:
+        return os.urandom(32)
+    if not (seed.isascii() and seed.isdigit()) or int(seed) >= 1 << 64:
+        raise L.MatrixEyesError(1, f"MATRIX_EYES_SEED={seed}: expected an unsigned 64-bit decimal number")
+    buf = (C.c_uint8 * 32)()
+    rc = lib.me_noise_key_from_seed(int(seed), buf)
+    if rc != L.ME_OK:
+        raise L.MatrixEyesError(rc, "me_noise_key_from_seed")
+    return bytes(buf)
+
+
 class _DevMem:
     """`nbytes` of device memory at `ptr`, as torch.as_tensor takes it"""
 

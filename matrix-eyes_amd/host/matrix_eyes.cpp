@@ -1,5 +1,7 @@
 #include "matrix_eyes.hpp"
 
+#include <cctype>
+#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -50,6 +52,31 @@ bool env_host_or_device(const char* name, bool fallback) {
     return false;
 }
 
+// MATRIX_EYES_NOISE=legacy | host | device; unset: legacy
+NoiseSource env_noise_source() {
+    const char* value = std::getenv("MATRIX_EYES_NOISE");
+    if (!value || std::strcmp(value, "legacy") == 0) return NoiseSource::Legacy;
+    if (std::strcmp(value, "host") == 0) return NoiseSource::Host;
+    if (std::strcmp(value, "device") == 0) return NoiseSource::Device;
+    throw ModelError(ME_ERR_BAD_ARG, std::string("MATRIX_EYES_NOISE=") + value + ": expected legacy, host or device");
+}
+
+// The key of the keyed noise: MATRIX_EYES_SEED as a full unsigned 64-bit decimal, expanded by me_noise_key_from_seed;
+// unset: 32 bytes from the operating system
+void noise_key(uint8_t key[32]) {
+    const char* seed = std::getenv("MATRIX_EYES_SEED");
+    if (!seed) {
+        if (me_noise_key_from_os(key) != ME_OK) throw output::OutputError(me_last_error(nullptr));
+        return;
+    }
+    char* end = nullptr;
+    errno = 0;
+    const unsigned long long v = std::strtoull(seed, &end, 10);
+    if (!std::isdigit((unsigned char)seed[0]) || *end != 0 || errno == ERANGE)
+        throw output::OutputError(std::string("MATRIX_EYES_SEED=") + seed + ": expected an unsigned 64-bit decimal number");
+    me_noise_key_from_seed((uint64_t)v, key);
+}
+
 // save_image for the output methods: its ImageError is their OutputError
 void save_or_throw(const RgbImage& image, const std::string& path) {
     try {
@@ -77,6 +104,7 @@ Device::Device() {
     device_jpeg_decoder_ = env_host_or_device("MATRIX_EYES_JPEG_DECODER", false);
     device_png_decoder_ = env_host_or_device("MATRIX_EYES_PNG_DECODER", false);
     device_jpeg_encoder_ = env_host_or_device("MATRIX_EYES_JPEG_ENCODER", false);
+    noise_source_ = env_noise_source();
     try {  // MATRIX_EYES_JPEG_QUALITY, MATRIX_EYES_JPEG_SUBSAMPLING: refused here, not at the first ".jpg" written
         jpeg_params_ = jpeg_output_params();
     } catch (const ImageError& err) {
@@ -260,14 +288,44 @@ void DepthMap::output_stereogram(const std::string& destination_path, std::optio
         w = round_u32((float)original_width_ * *resize_scale);
         h = round_u32((float)original_height_ * *resize_scale);
     }
+    const bool to_png = device_.device_png_encoder() && ends_with_ci(destination_path, ".png");
+    const bool to_jpeg = device_.device_jpeg_encoder() && is_jpeg_name(destination_path);
+    if (device_.noise_source() == NoiseSource::Device) {
+        // the keyed entries: the noise is made on the GPU, in device scratch; no noise buffer exists here
+        uint8_t key[32];
+        noise_key(key);
+        if (to_png) {
+            check_output(device_.ctx(), me_output_stereogram_png_keyed(device_.ctx(), data_.data(), (int32_t)data_width_, (int32_t)data_height_,
+                                                                       min_, max_, (int32_t)w, (int32_t)h, amplitude, key, destination_path.c_str()));
+            return;
+        }
+        if (to_jpeg) {
+            const JpegOutputParams& p = device_.jpeg_params();
+            check_output(device_.ctx(), me_output_stereogram_jpeg_keyed(device_.ctx(), data_.data(), (int32_t)data_width_, (int32_t)data_height_,
+                                                                        min_, max_, (int32_t)w, (int32_t)h, amplitude, key, p.quality,
+                                                                        p.subsampling, destination_path.c_str()));
+            return;
+        }
+        RgbImage out(w, h);
+        check_output(device_.ctx(), me_stereogram_keyed(device_.ctx(), data_.data(), (int32_t)data_width_, (int32_t)data_height_, min_, max_,
+                                                        (int32_t)w, (int32_t)h, amplitude, key, out.data.data()));
+        return save_or_throw(out, destination_path);
+    }
     RgbImage noise(w, h), out(w, h);
-    // output.rs:165-171: rand::rng() fills one [u8; 3] per pixel, row by row.  MATRIX_EYES_SEED makes a
-    // run repeatable (the reference is not).
-    const char* seed = std::getenv("MATRIX_EYES_SEED");
-    std::mt19937 rng(seed ? (unsigned)std::strtoul(seed, nullptr, 10) : std::random_device{}());
-    for (size_t i = 0; i < noise.data.size(); i += 4) {
-        const uint32_t v = rng();
-        for (size_t k = 0; k < 4 && i + k < noise.data.size(); ++k) noise.data[i + k] = (uint8_t)(v >> (8 * k));
+    if (device_.noise_source() == NoiseSource::Host) {
+        // the same bytes from the CPU twin, on this thread
+        uint8_t key[32];
+        noise_key(key);
+        if (me_stereogram_noise_host(key, (int32_t)w, (int32_t)h, noise.data.data()) != ME_OK) throw OutputError(me_last_error(nullptr));
+    } else {
+        // output.rs:165-171: rand::rng() fills one [u8; 3] per pixel, row by row.  MATRIX_EYES_SEED makes a
+        // run repeatable (the reference is not).
+        const char* seed = std::getenv("MATRIX_EYES_SEED");
+        std::mt19937 rng(seed ? (unsigned)std::strtoul(seed, nullptr, 10) : std::random_device{}());
+        for (size_t i = 0; i < noise.data.size(); i += 4) {
+            const uint32_t v = rng();
+            for (size_t k = 0; k < 4 && i + k < noise.data.size(); ++k) noise.data[i + k] = (uint8_t)(v >> (8 * k));
+        }
     }
     if (device_.device_png_encoder() && ends_with_ci(destination_path, ".png")) {
         check_output(device_.ctx(), me_output_stereogram_png(device_.ctx(), data_.data(), (int32_t)data_width_, (int32_t)data_height_,

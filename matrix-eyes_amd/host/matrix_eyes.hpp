@@ -42,6 +42,14 @@ struct ProgressListener {  // mod.rs:366-372
 
 // reconstruction::init_device(): the MI355X back end has one kind of device; MATRIX_EYES_DEVICE picks the
 // GPU ordinal, MATRIX_EYES_DTYPE=bf16 the MFMA operand type (default f16: the fp16 checkpoint bit for bit).
+// Where output_stereogram's noise comes from (MATRIX_EYES_NOISE): Legacy (the default) is std::mt19937 seeded with
+// MATRIX_EYES_SEED or the OS, today's bytes; Host is the keyed ChaCha12 noise of DESIGN.md §4.41 made by its CPU twin
+// (me_stereogram_noise_host) and handed to today's calls; Device is the same noise made on the GPU by a fill
+// kernel (me_stereogram_keyed and its file forms), with no noise buffer on the host.  Host and Device write the same
+// pixels for the same MATRIX_EYES_SEED (a full unsigned 64-bit decimal; unset: a key from the OS), and so does the
+// Python mirror.  Any other value fails the Device constructor.
+enum class NoiseSource { Legacy, Host, Device };
+
 class Device {
 public:
     Device();
@@ -70,6 +78,7 @@ public:
     // MATRIX_EYES_JPEG_SUBSAMPLING ("4:2:0"); any other value of the three variables fails the constructor.
     bool device_jpeg_encoder() const { return device_jpeg_encoder_; }
     const JpegOutputParams& jpeg_params() const { return jpeg_params_; }
+    NoiseSource noise_source() const { return noise_source_; }
     // ImageReader::open(..).decode() of a JPEG photo (reconstruction.rs:95-106): with MATRIX_EYES_JPEG_DECODER=device the
     // entropy-coded segments are decoded on the host and the picture is reconstructed and oriented on the GPU
     // (me_jpeg_decode_rgb8), chained there with the resize when the device resampler is on (me_jpeg_decode_resized_rgb8:
@@ -96,6 +105,7 @@ private:
     bool device_png_encoder_ = false;
     bool device_jpeg_encoder_ = false;
     JpegOutputParams jpeg_params_;
+    NoiseSource noise_source_ = NoiseSource::Legacy;
     bool device_jpeg_decoder_ = false;
     bool device_png_decoder_ = false;
     mutable bool weights_loaded_ = false;

@@ -9,8 +9,8 @@ from typing import Optional
 import numpy as np
 
 from . import _lib as L
-from .depth_pro import (Context, _device_file, _in_ptr, resolve_jpeg_encoder, resolve_jpeg_quality, resolve_jpeg_subsampling,
-                        resolve_png_encoder, resolve_resampler)
+from .depth_pro import (Context, _device_file, _in_ptr, noise_key, resolve_jpeg_encoder, resolve_jpeg_quality,
+                        resolve_jpeg_subsampling, resolve_noise_source, resolve_png_encoder, resolve_resampler)
 
 
 class VertexMode(enum.IntEnum):   # output.rs:33-38
@@ -89,26 +89,40 @@ class DepthMap:
             return w, h
         return self.original_width, self.original_height
 
-    def _stereogram_noise(self, resize_scale, noise):
-        """(out_w, out_h, the noise's pointer, its keepalive) of the stereogram methods; noise as for `stereogram`"""
+    def _stereogram_noise(self, resize_scale, noise, noise_source=None, key=None):
+        """(out_w, out_h, the noise's pointer or None, the key's buffer or None, a keepalive) of the stereogram methods;
+        noise, noise_source and key as for `stereogram`.  Exactly one of the pointer and the key is set: the key with
+        noise_source "device", which takes the keyed entries."""
         w, h = self.stereogram_size(resize_scale)
         if noise is None:
-            noise = _noise_rng().integers(0, 256, size=(h, w, 3), dtype=np.uint8)
+            source = resolve_noise_source(noise_source)
+            if source == "legacy":
+                noise = _noise_rng().integers(0, 256, size=(h, w, 3), dtype=np.uint8)
+            else:
+                kbuf = (C.c_uint8 * 32).from_buffer_copy(noise_key(self.ctx.lib, key))
+                if source == "device":
+                    return w, h, None, kbuf, None
+                noise = np.empty((h, w, 3), np.uint8)
+                rc = self.ctx.lib.me_stereogram_noise_host(kbuf, w, h, C.c_void_p(noise.ctypes.data))
+                if rc != L.ME_OK:
+                    L.check(self.ctx.lib, None, rc)
         pn, keep = _in_ptr(noise, np.uint8)
         if tuple(noise.shape) != (h, w, 3):
             raise L.MatrixEyesError(2, f"noise must be [{h},{w},3]")
-        return w, h, pn, keep
+        return w, h, pn, None, keep
 
-    def stereogram(self, resize_scale: Optional[float], amplitude: float, noise=None) -> np.ndarray:
+    def stereogram(self, resize_scale: Optional[float], amplitude: float, noise=None, noise_source=None, key=None) -> np.ndarray:
         """output.rs:141-193 -> u8 [out_h, out_w, 3].  noise u8 [out_h, out_w, 3] stands in for the
-        reference's rand::rng() stream (row by row, pixel by pixel); drawn from os.urandom-seeded
-        numpy when omitted."""
-        w, h, pn, keep = self._stereogram_noise(resize_scale, noise)
+        reference's rand::rng() stream (row by row, pixel by pixel).  When omitted it comes from noise_source
+        (depth_pro.resolve_noise_source): "legacy" draws it from numpy seeded with MATRIX_EYES_SEED or the OS; "host" and
+        "device" make the keyed noise of `key` (32 bytes; None: depth_pro.noise_key) on the CPU or on the GPU."""
+        w, h, pn, kbuf, keep = self._stereogram_noise(resize_scale, noise, noise_source, key)
         mn, mx = self._range
         out = np.empty((h, w, 3), np.uint8)
-        self.ctx._check(self.ctx.lib.me_stereogram(
+        entry = self.ctx.lib.me_stereogram if kbuf is None else self.ctx.lib.me_stereogram_keyed
+        self.ctx._check(entry(
             self.ctx.handle, C.c_void_p(self.data.ctypes.data), self.data_width, self.data_height, mn, mx,
-            w, h, amplitude, pn, C.c_void_p(out.ctypes.data)))
+            w, h, amplitude, pn if kbuf is None else kbuf, C.c_void_p(out.ctypes.data)))
         return out
 
     def mesh_index(self, want_faces=True):
@@ -151,13 +165,16 @@ class DepthMap:
             self.ctx.handle, C.c_void_p(self.data.ctypes.data), self.data_width, self.data_height, mn, mx, None,
             self.original_width, self.original_height, str(destination_path).encode()))
 
-    def output_stereogram_png(self, destination_path: str, resize_scale: Optional[float], amplitude: float, noise=None):
-        """output.rs:141-193 whole, on the GPU (me_output_stereogram_png); noise as for `stereogram`"""
-        w, h, pn, keep = self._stereogram_noise(resize_scale, noise)
+    def output_stereogram_png(self, destination_path: str, resize_scale: Optional[float], amplitude: float, noise=None,
+                              noise_source=None, key=None):
+        """output.rs:141-193 whole, on the GPU (me_output_stereogram_png, or its _keyed form); noise, noise_source and key
+        as for `stereogram`"""
+        w, h, pn, kbuf, keep = self._stereogram_noise(resize_scale, noise, noise_source, key)
         mn, mx = self._range
-        self.ctx._check(self.ctx.lib.me_output_stereogram_png(
+        entry = self.ctx.lib.me_output_stereogram_png if kbuf is None else self.ctx.lib.me_output_stereogram_png_keyed
+        self.ctx._check(entry(
             self.ctx.handle, C.c_void_p(self.data.ctypes.data), self.data_width, self.data_height, mn, mx,
-            w, h, amplitude, pn, str(destination_path).encode()))
+            w, h, amplitude, pn if kbuf is None else kbuf, str(destination_path).encode()))
 
     def output_depth_map_jpeg(self, destination_path: str, quality: int = 75, subsampling: int = 2):
         """output.rs:123-139 whole, on the GPU (me_output_depth_map_jpeg): colour map, Lanczos3 resize, JPEG file"""
@@ -167,23 +184,27 @@ class DepthMap:
             self.original_width, self.original_height, int(quality), int(subsampling), str(destination_path).encode()))
 
     def output_stereogram_jpeg(self, destination_path: str, resize_scale: Optional[float], amplitude: float, noise=None,
-                               quality: int = 75, subsampling: int = 2):
-        """output.rs:141-193 whole, on the GPU (me_output_stereogram_jpeg); noise as for `stereogram`"""
-        w, h, pn, keep = self._stereogram_noise(resize_scale, noise)
+                               quality: int = 75, subsampling: int = 2, noise_source=None, key=None):
+        """output.rs:141-193 whole, on the GPU (me_output_stereogram_jpeg, or its _keyed form); noise, noise_source and key
+        as for `stereogram`"""
+        w, h, pn, kbuf, keep = self._stereogram_noise(resize_scale, noise, noise_source, key)
         mn, mx = self._range
-        self.ctx._check(self.ctx.lib.me_output_stereogram_jpeg(
+        entry = self.ctx.lib.me_output_stereogram_jpeg if kbuf is None else self.ctx.lib.me_output_stereogram_jpeg_keyed
+        self.ctx._check(entry(
             self.ctx.handle, C.c_void_p(self.data.ctypes.data), self.data_width, self.data_height, mn, mx,
-            w, h, amplitude, pn, int(quality), int(subsampling), str(destination_path).encode()))
+            w, h, amplitude, pn if kbuf is None else kbuf, int(quality), int(subsampling), str(destination_path).encode()))
 
     def output_image(self, destination_path: str, source_path: str, image_format: ImageOutputFormat,
                      vertex_mode: VertexMode, noise=None, resampler=None, png_encoder=None, jpeg_encoder=None,
-                     jpeg_quality=None, jpeg_subsampling=None):
-        """output.rs:100-121: dispatch on the destination suffix.  resampler: depth_pro.resolve_resampler;
+                     jpeg_quality=None, jpeg_subsampling=None, noise_source=None):
+        """output.rs:100-121: dispatch on the destination suffix.  noise_source: depth_pro.resolve_noise_source, for a
+        stereogram without `noise`; resampler: depth_pro.resolve_resampler;
         png_encoder: depth_pro.resolve_png_encoder; jpeg_encoder, jpeg_quality, jpeg_subsampling:
         depth_pro.resolve_jpeg_encoder / _quality / _subsampling (they act on a ".jpg" / ".jpeg" destination only)."""
         resampler = resolve_resampler(resampler)
         png_encoder = resolve_png_encoder(png_encoder)
         jpeg_encoder = resolve_jpeg_encoder(jpeg_encoder)
+        noise_source = resolve_noise_source(noise_source)
         low = destination_path.lower()
         if low.endswith(".ply") or low.endswith(".obj"):
             return self.output_mesh(destination_path, source_path, vertex_mode, resampler=resampler)
@@ -199,7 +220,8 @@ class DepthMap:
                                               else (self.output_stereogram_png, self.output_depth_map_png, self.ctx.output_png))
             native = self.original_width == self.original_height == self.data_width == self.data_height
             if image_format.kind != "depthmap":
-                return stereogram(destination_path, image_format.resize_scale, image_format.amplitude, noise, *jpeg_args)
+                return stereogram(destination_path, image_format.resize_scale, image_format.amplitude, noise, *jpeg_args,
+                                  noise_source=noise_source)
             if resampler == "device" or native:   # (the resize is the identity at the native size)
                 return depth_map(destination_path, *jpeg_args)
             img = Image.fromarray(self.depth_map_rgb()).resize((self.original_width, self.original_height), Image.LANCZOS)
@@ -213,8 +235,8 @@ class DepthMap:
                 img = img.resize(size, Image.LANCZOS)
             img.save(destination_path, **save_args)
         else:
-            Image.fromarray(self.stereogram(image_format.resize_scale, image_format.amplitude,
-                                            noise)).save(destination_path, **save_args)
+            Image.fromarray(self.stereogram(image_format.resize_scale, image_format.amplitude, noise,
+                                            noise_source=noise_source)).save(destination_path, **save_args)
 
     def output_mesh(self, destination_path: str, source_path: str, vertex_mode: VertexMode, resampler=None):
         """output.rs:195-261 with ObjWriter / PlyWriter."""
@@ -319,14 +341,22 @@ class DeviceDepthMap:
             C.byref(ptr), C.byref(n)))
         return _device_file(ptr, n, self.data)
 
-    def stereogram(self, amplitude: float, noise, out=None):
-        """noise: CUDA u8 [out_h, out_w, 3]"""
+    def stereogram(self, amplitude: float, noise=None, out=None, key=None, size=None):
+        """noise: CUDA u8 [out_h, out_w, 3]; or key=: the 32 bytes of the keyed noise, made on the
+        device for a picture of size = (out_w, out_h) (default: the original size) -- me_stereogram_keyed_dev_range"""
         import torch
-        h, w = noise.shape[0], noise.shape[1]
+        if (noise is None) == (key is None):
+            raise L.MatrixEyesError(1, "DeviceDepthMap.stereogram: pass either noise or key")
+        if key is None:
+            h, w = noise.shape[0], noise.shape[1]
+            entry, source = self.ctx.lib.me_stereogram_dev_range, C.c_void_p(noise.data_ptr())
+        else:
+            w, h = size if size is not None else (self.original_width, self.original_height)
+            entry = self.ctx.lib.me_stereogram_keyed_dev_range
+            source = (C.c_uint8 * 32).from_buffer_copy(noise_key(self.ctx.lib, key))
         if out is None:
             out = torch.empty((h, w, 3), dtype=torch.uint8, device=self.data.device)
-        self.ctx._check(self.ctx.lib.me_stereogram_dev_range(
+        self.ctx._check(entry(
             self.ctx.handle, C.c_void_p(self.data.data_ptr()), self.data_width, self.data_height,
-            C.c_void_p(self.range_dev.data_ptr()), w, h, amplitude, C.c_void_p(noise.data_ptr()),
-            C.c_void_p(out.data_ptr())))
+            C.c_void_p(self.range_dev.data_ptr()), w, h, amplitude, source, C.c_void_p(out.data_ptr())))
         return out
