@@ -185,6 +185,28 @@ int32_t me_op_linear_fp8_residual_layernorm(me_ctx* ctx, int32_t M, int32_t N, i
    block scales; heads even): the bytes me_op_quantize_fp8 gives for me_op_attention's 16-bit output. */
 int32_t me_op_attention_fp8(me_ctx* ctx, const void* qkv16, uint8_t* out8, uint8_t* out8_scale, int32_t windows,
                             int32_t tokens, int32_t heads);
+/* me_op_attention (prescaled = 0) / me_op_attention_prescaled (1) over the row space of the encoder's merged ViT launches
+   (pipeline.hip MergedVit, common.h RowSegs): qkv16 [rows_total][3*heads*64]; windows are `tokens` rows apart INSIDE a
+   segment -- windows [0, win0) start at row 0, [win0, win0 + win1) at seg1, the rest at seg2 (seg2 == 0: two segments, and
+   windows == win0 + win1; seg1 == 0: none, the windows back to back from row 0).  ONE of out16 [rows_total][heads*64] and
+   out8 [rows_total][heads*64] e4m3 bytes + out8_scale, one e8m0 byte per 32 columns in the activation layout with
+   ceil(rows_total / 128) tiles of 128 rows (heads even) -- what an ME_DTYPE_FP8 context's attention hands to the
+   projection.  Rows that belong to no window are neither read nor written.  Refused before any launch: a null pointer,
+   both or neither output, an odd head count with out8, segment starts out of order (ME_ERR_BAD_ARG); windows that do
+   not fit their segment -- win0 * tokens > seg1, the middle segment's reaching past seg2 (rows_total without a third), the
+   last segment's past rows_total (ME_ERR_BAD_SHAPE). */
+int32_t me_op_attention_segments(me_ctx* ctx, const void* qkv16, void* out16, uint8_t* out8, uint8_t* out8_scale,
+                                 int32_t windows, int32_t tokens, int32_t heads, int32_t prescaled, int64_t rows_total,
+                                 int64_t seg1, int64_t seg2, int32_t win0, int32_t win1);
+/* me_op_layernorm / me_op_layernorm_fp8 over up to three row segments with their own weights, as the merged ViT launches
+   run them: rows [0, seg1) use weight[0] / bias[0], [seg1, seg2) the [1] set, [seg2, rows) the [2] set; seg2 == 0: two
+   segments, seg1 == 0: one.  The boundaries may be any rows (the kernels choose per row).  ONE output form: y16 and/or
+   y32 [rows][dim] (dim in {64, 128, 256, 512, 1024}), or y8 + yscale as me_op_layernorm_fp8 writes them (dim in {256, 512,
+   1024}).  Refused before any launch: a null pointer or a segment without weights, both or neither output form, segment
+   starts out of order or beyond `rows` (ME_ERR_BAD_ARG); a dim outside the set (ME_ERR_BAD_SHAPE). */
+int32_t me_op_layernorm_segments(me_ctx* ctx, const float* x32, const float* const weight[3], const float* const bias[3],
+                                 int64_t seg1, int64_t seg2, void* y16, float* y32, uint8_t* y8, uint8_t* yscale,
+                                 int64_t rows, int32_t dim, float eps);
 /* The number formatter of the device OBJ writer (csrc/ryu_f64.h, obj_format.hip) on its own: values[i] (DEVICE f64)
    printed as Rust's `{}` prints an f64 -- shortest round-trip digits, positional notation -- into the `stride`-byte
    slot i of `text` (stride >= 344), its length into lengths[i]. */

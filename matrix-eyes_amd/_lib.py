@@ -158,6 +158,9 @@ SIGNATURES = {
     "me_op_linear_fp8": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "me_op_linear_fp8_segments": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, C.POINTER(_vp), C.POINTER(_vp),
                                          C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, _vp]),
+    "me_op_attention_segments": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _i32]),
+    "me_op_layernorm_segments": (_i32, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i32,
+                                        _f32]),
     "me_op_linear_segments": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                      _vp, _vp, _i32, _i32]),
     "me_op_linear_residual_layernorm": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),

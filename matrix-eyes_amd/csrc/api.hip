@@ -1271,6 +1271,60 @@ int32_t me_op_linear_segments(me_ctx* ctx, int32_t M, int32_t N, int32_t K, cons
     ME_API_END(ctx)
 }
 
+// me_op_attention_segments and me_op_layernorm_segments: the row-segmented forms of the merged ViT launches (pipeline.hip
+// MergedVit, common.h RowSegs).  The kernels trust the row map, so a layout that does not fit its buffers is refused here.
+int32_t me_op_attention_segments(me_ctx* ctx, const void* qkv16, void* out16, uint8_t* out8, uint8_t* out8_scale, int32_t windows,
+                                 int32_t tokens, int32_t heads, int32_t prescaled, int64_t rows_total, int64_t seg1, int64_t seg2,
+                                 int32_t win0, int32_t win1) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(qkv16 && (out16 || out8), ME_ERR_BAD_ARG, "me_op_attention_segments: null pointer");
+    ME_CHECK(!(out16 && out8), ME_ERR_BAD_ARG, "me_op_attention_segments: ONE of out16 and out8");
+    ME_CHECK(!out8 || out8_scale, ME_ERR_BAD_ARG, "me_op_attention_segments: out8 without its scales");
+    ME_CHECK(!out8 || heads % 2 == 0, ME_ERR_BAD_ARG, "me_op_attention_segments: fp8 output with %d heads (an odd number)", heads);
+    ME_CHECK(windows > 0 && tokens > 0 && heads > 0 && rows_total > 0, ME_ERR_BAD_SHAPE,
+             "me_op_attention_segments: windows=%d tokens=%d heads=%d rows=%lld", windows, tokens, heads, (long long)rows_total);
+    ME_CHECK(seg1 >= 0 && seg2 >= 0 && win0 >= 0 && win1 >= 0 && seg1 <= rows_total && seg2 <= rows_total &&
+                 (seg2 == 0 || (seg1 > 0 && seg2 > seg1)),
+             ME_ERR_BAD_ARG, "me_op_attention_segments: segments %lld / %lld of %lld rows, %d / %d windows", (long long)seg1,
+             (long long)seg2, (long long)rows_total, win0, win1);
+    const int64_t T = tokens, last = (int64_t)windows - win0 - win1;  // windows of the last segment
+    bool fits;
+    if (seg1 == 0) fits = windows * T <= rows_total;
+    else if (seg2 == 0) fits = win0 * T <= seg1 && last == 0 && seg1 + win1 * T <= rows_total;
+    else fits = win0 * T <= seg1 && seg1 + win1 * T <= seg2 && last >= 0 && seg2 + last * T <= rows_total;
+    ME_CHECK(fits, ME_ERR_BAD_SHAPE, "me_op_attention_segments: %d windows of %d rows (%d / %d in the first segments) do not fit "
+             "segments %lld / %lld of %lld rows", windows, tokens, win0, win1, (long long)seg1, (long long)seg2, (long long)rows_total);
+    RowSegs segs;
+    segs.seg1 = seg1, segs.seg2 = seg2, segs.win0 = win0, segs.win1 = win1;
+    attention_launch(qkv16, out16, windows, tokens, heads, ctx->dtype, ctx->stream, &segs, out8, out8_scale,
+                     out8 ? cdiv(rows_total, 128) : 0, prescaled != 0);
+    ME_API_END(ctx)
+}
+
+int32_t me_op_layernorm_segments(me_ctx* ctx, const float* x32, const float* const weight[3], const float* const bias[3],
+                                 int64_t seg1, int64_t seg2, void* y16, float* y32, uint8_t* y8, uint8_t* yscale, int64_t rows,
+                                 int32_t dim, float eps) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(x32 && weight && bias && (y16 || y32 || y8), ME_ERR_BAD_ARG, "me_op_layernorm_segments: null pointer");
+    ME_CHECK(!(y8 && (y16 || y32)), ME_ERR_BAD_ARG, "me_op_layernorm_segments: ONE of y16 / y32 and y8");
+    ME_CHECK(!y8 || yscale, ME_ERR_BAD_ARG, "me_op_layernorm_segments: y8 without its scales");
+    ME_CHECK(rows > 0, ME_ERR_BAD_SHAPE, "me_op_layernorm_segments: %lld rows", (long long)rows);
+    ME_CHECK(seg1 >= 0 && seg2 >= 0 && seg1 <= rows && seg2 <= rows && (seg2 == 0 || (seg1 > 0 && seg2 > seg1)), ME_ERR_BAD_ARG,
+             "me_op_layernorm_segments: segments %lld / %lld of %lld rows", (long long)seg1, (long long)seg2, (long long)rows);
+    const int nseg = seg1 == 0 ? 1 : (seg2 == 0 ? 2 : 3);
+    for (int i = 0; i < nseg; ++i)
+        ME_CHECK(weight[i] && bias[i], ME_ERR_BAD_ARG, "me_op_layernorm_segments: row segment %d without weights", i);
+    const bool wide = dim == 256 || dim == 512 || dim == 1024;
+    ME_CHECK(wide || (!y8 && (dim == 64 || dim == 128)), ME_ERR_BAD_SHAPE, "me_op_layernorm_segments: dim %d", dim);
+    RowSegs segs;
+    segs.seg1 = seg1, segs.seg2 = seg2;
+    if (nseg > 1) segs.w1 = weight[1], segs.b1 = bias[1];
+    if (nseg > 2) segs.w2 = weight[2], segs.b2 = bias[2];
+    if (y8) layernorm_fp8_launch(x32, weight[0], bias[0], y8, yscale, rows, dim, eps, ctx->stream, &segs);
+    else layernorm_launch(x32, weight[0], bias[0], y16, y32, rows, dim, eps, ctx->dtype, ctx->stream, &segs);
+    ME_API_END(ctx)
+}
+
 namespace {
 // xn8 != nullptr: the normalised rows as MX fp8 + activation-layout scales (ceil(M / 128) tiles) instead of 16-bit
 void linear_residual_layernorm_impl(me_ctx* ctx, const char* who, int32_t M, int32_t N, int32_t K, const void* A16, int32_t seg1,

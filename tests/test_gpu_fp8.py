@@ -11,44 +11,11 @@ import torch
 import torch.nn.functional as F
 
 import matrix_eyes_amd as m
+from mx_ref import dequant as _dequant, quantize_ref as _quantize_ref, read_scales as _read_scales, scale_bytes as _scale_bytes
 from util import ctx_for, ptr, rel_l2
 
 pytestmark = pytest.mark.gpu
 E4M3 = torch.float8_e4m3fn
-
-
-def _scale_bytes(blocks_amax):
-    """the rule of csrc/mx_fp8.h mx_scale_byte: exponent of amax - 8, one more when the significand is >= 1.75, so
-    that no scaled element exceeds e4m3's 448"""
-    bits = blocks_amax.float().contiguous().view(torch.int32).to(torch.int64) & 0x7fffffff
-    e = (bits + 0x200000) >> 23
-    return torch.clamp(e - 8, 0, 254).to(torch.uint8)
-
-
-def _quantize_ref(x):
-    """x [rows, K] f32 -> (e4m3 tensor [rows, K], scale bytes [rows, K/32])"""
-    rows, K = x.shape
-    b = x.float().reshape(rows, K // 32, 32)
-    sb = _scale_bytes(b.abs().amax(dim=2))
-    inv = torch.where(sb == 0, torch.tensor(1.7014118e38), torch.pow(2.0, 127.0 - sb.float()))
-    q = (b * inv.unsqueeze(2)).to(E4M3)
-    return q.reshape(rows, K), sb
-
-
-def _dequant(q8, sb):
-    rows, K = q8.shape
-    return (q8.float().reshape(rows, K // 32, 32).double() * torch.pow(2.0, sb.double() - 127.0).unsqueeze(2)).reshape(rows, K)
-
-
-def _read_scales(ctx, packed, rows, K, weight_layout):
-    """packed scale bytes (device) -> [rows, K/32] via me_op_scale_index"""
-    host = packed.cpu().numpy()
-    fn = ctx.lib.me_op_scale_index
-    out = np.empty((rows, K // 32), np.uint8)
-    for r in range(rows):
-        for kb in range(K // 32):
-            out[r, kb] = host[fn(r, kb, rows, weight_layout)]
-    return torch.from_numpy(out)
 
 
 def _quantize_gpu(ctx, x16, weight_layout):
@@ -233,17 +200,30 @@ def test_linear_fp8_at_the_step_shapes_with_cold_caches(N, K, form):
 
 
 def test_layernorm_fp8():
+    _layernorm_fp8_case(700, 1024)
+
+
+@pytest.mark.parametrize("dim", [256, 512])
+def test_layernorm_fp8_narrow_dims(dim):
+    """the other two instantiations of layernorm_fp8_kernel (one and two passes of four elements per lane), same bounds; row
+    counts that end inside a workgroup's four rows"""
+    for rows in (700, 1, 3, 5, 1001):
+        _layernorm_fp8_case(rows, dim)
+
+
+def _layernorm_fp8_case(rows, dim):
     ctx = ctx_for("tiny", "f16")
     g = torch.Generator().manual_seed(9)
-    rows, dim = 700, 1024
     x = (torch.randn(rows, dim, generator=g) * 3 + 0.5)
     x[:, 17] += 40.0                      # an outlier channel, as DINOv2 has
     w, b = torch.randn(dim, generator=g) * 0.1 + 1, torch.randn(dim, generator=g) * 0.1
-    y8 = torch.empty(rows, dim, dtype=torch.uint8, device="cuda")
+    y8 = torch.full((rows + 1, dim), 0xA5, dtype=torch.uint8, device="cuda")      # a guard row behind the output
     ys = torch.zeros((rows + 127) // 128 * 128 * dim // 32, dtype=torch.uint8, device="cuda")
     xd, wd, bd = x.cuda(), w.cuda(), b.cuda()          # kept alive until the kernel has run
     ctx._check(ctx.lib.me_op_layernorm_fp8(ctx.handle, ptr(xd), ptr(wd), ptr(bd), ptr(y8), ptr(ys), rows, dim, 1e-5))
     ctx.synchronize()
+    assert bool((y8[rows] == 0xA5).all())
+    y8 = y8[:rows]
     ref = F.layer_norm(x.double(), (dim,), w.double(), b.double(), 1e-5)
     sb = _read_scales(ctx, ys, rows, dim, 0)
     diff = (sb.int() - _scale_bytes(ref.float().abs().reshape(rows, dim // 32, 32).amax(2)).int()).abs()

@@ -8,6 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import layernorm_rows as LR
 from util import (TORCH16, bordered, ctx_for, dev16, max_abs_rel, max_err_over_max, pack_conv, pack_convt, ptr,
                   rel_l2)
 
@@ -604,21 +605,59 @@ def test_attention_large_scores(dtype):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("dim", [128, 1024])
+@pytest.mark.parametrize("dim", [64, 128, 256, 512, 1024])
 def test_layernorm(dtype, dim):
+    """every instantiation of layernorm_kernel (one, four -- dim 256 alone -- and eight elements per lane and pass), at row
+    counts that end inside a workgroup's four rows; a guard row behind both outputs stays untouched"""
     ctx = ctx_for("tiny", dtype)
-    rows = 1001
     g = torch.Generator().manual_seed(dim)
-    x = (torch.randn(rows, dim, generator=g) * 3 + 0.5).cuda()
+    x = (torch.randn(1001, dim, generator=g) * 3 + 0.5).cuda()
     w = (1 + 0.02 * torch.randn(dim, generator=g)).cuda()
     b = (0.02 * torch.randn(dim, generator=g)).cuda()
-    y32 = torch.empty_like(x)
-    y16 = torch.empty(rows, dim, dtype=TORCH16[dtype], device="cuda")
-    _check(ctx, ctx.lib.me_op_layernorm(ctx.handle, ptr(x), ptr(w), ptr(b), ptr(y16), ptr(y32), rows, dim, 1e-5))
-    ctx.synchronize()
     ref = F.layer_norm(x.double(), (dim,), w.double(), b.double(), 1e-5)
-    assert float((y32.double() - ref).abs().max()) < 2e-5
-    assert float((y16.double() - ref).abs().max()) < 4 * OUT_EPS[dtype] * 2
+    for rows in (1001, 1, 3, 5):
+        y32 = torch.full((rows + 1, dim), 7.0, dtype=torch.float32, device="cuda")
+        y16 = torch.full((rows + 1, dim), 7.0, dtype=TORCH16[dtype], device="cuda")
+        torch.cuda.synchronize()
+        _check(ctx, ctx.lib.me_op_layernorm(ctx.handle, ptr(x), ptr(w), ptr(b), ptr(y16), ptr(y32), rows, dim, 1e-5))
+        ctx.synchronize()
+        assert bool((y32[rows] == 7.0).all()) and bool((y16[rows] == 7.0).all()), rows
+        assert float((y32[:rows].double() - ref[:rows]).abs().max()) < 2e-5, rows
+        assert float((y16[:rows].double() - ref[:rows]).abs().max()) < 4 * OUT_EPS[dtype] * 2, rows
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dim", LR.HARD_DIMS)
+def test_layernorm_hard_rows(dtype, dim):
+    """Rows that punish a careless variance (tests/layernorm_rows.py): constant rows (variance 0: the output is the bias
+    exactly, in f32 and rounded once in 16 bit), rows whose mean of 100 dwarfs their spread of 1, a row with an outlier channel
+    of +40.  Bound: HARD_ROW_FACTOR x the error an f32 two-pass restatement of the kernel has against fp64 on these very
+    rows (measured on the CPU, re-measured by test_row_segments_cpu.py) -- the factor is for the wave reduction's summation
+    order, which the restatement does not copy; the 16-bit copy adds its one rounding."""
+    ctx = ctx_for("tiny", dtype)
+    x, w, b = LR.hard_rows(dim)
+    rows = x.shape[0]
+    ref = LR.reference(x, w, b)
+    xd, wd, bd = x.cuda(), w.cuda(), b.cuda()
+    y32 = torch.full((rows + 1, dim), 7.0, dtype=torch.float32, device="cuda")
+    y16 = torch.full((rows + 1, dim), 7.0, dtype=TORCH16[dtype], device="cuda")
+    torch.cuda.synchronize()
+    _check(ctx, ctx.lib.me_op_layernorm(ctx.handle, ptr(xd), ptr(wd), ptr(bd), ptr(y16), ptr(y32), rows, dim, LR.EPS))
+    ctx.synchronize()
+    y32, y16 = y32.cpu(), y16.cpu()
+    assert bool((y32[rows] == 7.0).all()) and bool((y16[rows] == 7.0).all())
+    assert bool(torch.isfinite(y32).all()) and bool(torch.isfinite(y16.float()).all())
+    for r in range(LR.N_CONST):
+        assert torch.equal(y32[r], b), r
+        assert torch.equal(y16[r], b.to(TORCH16[dtype])), r
+    bound = LR.HARD_ROW_FACTOR * LR.HARD_ROW_ERR
+    err32 = (y32[:rows].double() - ref).abs()
+    err16 = (y16[:rows].double() - ref).abs() - OUT_EPS[dtype] * ref.abs() - 2.0 ** -24   # one rounding (f16: or half a subnormal step)
+    for name, lo, hi in (("mean 100", LR.N_CONST, LR.N_CONST + LR.N_MEAN), ("outlier", LR.N_CONST + LR.N_MEAN, rows)):
+        print(name, dim, dtype, "f32 error", float(err32[lo:hi].max()), "16-bit error beyond its rounding", float(err16[lo:hi].max()),
+              "bound", bound)
+        assert float(err32[lo:hi].max()) < bound, name
+        assert float(err16[lo:hi].max()) < bound, name
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
