@@ -82,6 +82,25 @@ int32_t me_op_conv_transpose2x2_forms(me_ctx* ctx, const void* in16, int32_t B, 
                                       int32_t Cin, const void* w16, int32_t Cout, const float* bias,
                                       float* out32, void* out16, int32_t border16, int32_t act16,
                                       int32_t out_split, int32_t pixel_stride, int32_t lo_off, int32_t tile_cfg);
+/* me_op_conv_transpose2x2_forms on operand rows whose last part repeats their first ([hi | lo | hi] against weights stored
+   [W_hi | W_hi | W_lo]): the rows are stored a_wrap channels wide (a multiple of 64, at least Cin / 2) and channels
+   a_wrap .. Cin - 1 are read from the row's start -- the same K order, the repeated part neither stored nor read.
+   a_wrap 0: me_op_conv_transpose2x2_forms itself. */
+int32_t me_op_conv_transpose2x2_forms_wrap(me_ctx* ctx, const void* in16, int32_t B, int32_t H, int32_t W,
+                                           int32_t Cin, int32_t a_wrap, const void* w16, int32_t Cout, const float* bias,
+                                           float* out32, void* out16, int32_t border16, int32_t act16,
+                                           int32_t out_split, int32_t pixel_stride, int32_t lo_off, int32_t tile_cfg);
+/* Two ConvTranspose2d(2,2,stride 2) over the same [B][H][W] grid onto the same [B][2H][2W][Cout] map, summed in ONE accumulator
+   by one launch (csrc/gemm_core.h gemm_pp_kernel<..., CHAIN>): the K loop of (in16_a [B*H*W][Cin_a], w16_a) from zero, then
+   out16 = act16(acc) (zero-bordered when border16) from the accumulators -- the 16-bit output of
+   me_op_conv_transpose2x2_forms on set a alone, bit for bit --, then the K loop of (in16_b, w16_b) on top and
+   out32 = acc + bias_b.  Cin_b is the K set b walks, a_wrap_b as in me_op_conv_transpose2x2_forms_wrap.  Cin_a, Cin_b:
+   multiples of 64, at least 128.  grid_cap: at most that many workgroups (a multiple of 8; 0: no cap).  tile_cfg: only
+   configuration 0 (256x256x64/8w-pp) has the chained form; any other answers ME_ERR_BAD_ARG. */
+int32_t me_op_conv_transpose2x2_pair(me_ctx* ctx, int32_t B, int32_t H, int32_t W, int32_t Cout, const void* in16_a, int32_t Cin_a,
+                                     const void* w16_a, const void* in16_b, int32_t Cin_b, int32_t a_wrap_b, const void* w16_b,
+                                     const float* bias_b, float* out32, void* out16, int32_t border16, int32_t act16, int32_t grid_cap,
+                                     int32_t tile_cfg);
 /* Patch embed + pos (vit.rs:287-295; gemm_core.h EPI_PATCH_EMBED): patches16 [windows * P][768] . W16 [C][768]^T + bias
    + pos[1 + p] -> rows 1 .. P of each window of tokens32 [windows][P + 1][C]; the cls rows are not written
    (me_op_cls_rows writes them). */

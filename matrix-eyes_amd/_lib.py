@@ -138,6 +138,10 @@ SIGNATURES = {
     "me_op_linear_split": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32]),
     "me_op_conv_transpose2x2_forms": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp,
                                              _i32, _i32, _i32, _i32, _i32, _i32]),
+    "me_op_conv_transpose2x2_forms_wrap": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp,
+                                                  _i32, _i32, _i32, _i32, _i32, _i32]),
+    "me_op_conv_transpose2x2_pair": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
+                                            _i32, _i32, _i32, _i32]),
     "me_op_patch_embed": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32]),
     "me_op_bilinear": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32]),
     "me_op_patchify": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32]),

@@ -654,6 +654,13 @@ void extract_depth_impl(me_ctx* ctx, const float* img_dev, int32_t batch, const 
     // Unjoined).  ME_OVERLAP_TAIL=1 switches it on for the A/B.
     static const bool overlap_env = env_flag("ME_OVERLAP_TAIL");
     const bool overlap = overlap_env && ctx->overlap_tail && ctx->side_stream && !ctx->progress && !profiler().enabled;
+    // the whole path, nobody asks for encoding 0 or level 1's features themselves: decoder level 0 may take their sum from one
+    // chained ConvTranspose launch (pipeline.hip enc0_sum_applies); the stage-wise entries never see the flag set
+    struct Enc0Sum {
+        me_ctx* c;
+        ~Enc0Sum() { c->enc0_sum = false, c->enc0_last_in = nullptr; }
+    } enc0_sum{ctx};
+    ctx->enc0_sum = enc0_sum_applies(ctx, batch);
     OutBuf ofov;
     if (overlap) {
         stage_encoder_trunk(ctx, img_dev, batch, f_norm == nullptr);
@@ -1007,11 +1014,16 @@ int32_t me_op_linear_split(me_ctx* ctx, int32_t M, int32_t N, int32_t K, const v
     ME_API_END(ctx)
 }
 
-int32_t me_op_conv_transpose2x2_forms(me_ctx* ctx, const void* in16, int32_t B, int32_t H, int32_t W,
-                                      int32_t Cin, const void* w16, int32_t Cout, const float* bias,
-                                      float* out32, void* out16, int32_t border16, int32_t act16,
-                                      int32_t out_split, int32_t pixel_stride, int32_t lo_off, int32_t tile_cfg) {
-    ME_API_BEGIN(ctx)
+// a_wrap > 0: the operand rows are stored a_wrap channels wide and channels a_wrap .. Cin - 1 are read from the row's start
+static void check_a_wrap(const char* who, int32_t Cin, int32_t a_wrap) {
+    ME_CHECK(a_wrap >= 0 && a_wrap % 64 == 0 && (a_wrap == 0 || (a_wrap < Cin && Cin - a_wrap <= a_wrap)), ME_ERR_BAD_SHAPE,
+             "%s: a_wrap=%d of %d channels", who, a_wrap, Cin);
+}
+
+static void conv_transpose2x2_forms(me_ctx* ctx, const void* in16, int32_t B, int32_t H, int32_t W,
+                                    int32_t Cin, int32_t a_wrap, const void* w16, int32_t Cout, const float* bias,
+                                    float* out32, void* out16, int32_t border16, int32_t act16,
+                                    int32_t out_split, int32_t pixel_stride, int32_t lo_off, int32_t tile_cfg) {
     ME_CHECK(in16 && w16 && (out32 || out16), ME_ERR_BAD_ARG, "me_op_conv_transpose2x2_forms: null pointer");
     ME_CHECK(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cout % 8 == 0, ME_ERR_BAD_SHAPE,
              "me_op_conv_transpose2x2_forms: %d x %d x %d, %d -> %d", B, H, W, Cin, Cout);
@@ -1023,9 +1035,49 @@ int32_t me_op_conv_transpose2x2_forms(me_ctx* ctx, const void* in16, int32_t B, 
     ME_CHECK(pixel_stride >= 0 && pixel_stride % 8 == 0 && lo % 8 == 0 && (!out_split || lo >= Cout) &&
                  (!pixel_stride || pixel_stride >= lo + Cout),
              ME_ERR_BAD_SHAPE, "me_op_conv_transpose2x2_forms: pixel_stride=%d lo_off=%d for %d channels", pixel_stride, lo_off, Cout);
-    gemm_launch(convt_params(in16, B, H, W, Cin, w16, Cout, bias, out32, out16, border16 != 0, pixel_stride, act16, false, out_split != 0,
-                             lo_off),
-                A_PLAIN, EPI_CONVT, ctx->dtype, ctx->stream, tile_cfg);
+    check_a_wrap("me_op_conv_transpose2x2_forms_wrap", Cin, a_wrap);
+    GemmParams p = convt_params(in16, B, H, W, Cin, w16, Cout, bias, out32, out16, border16 != 0, pixel_stride, act16, false, out_split != 0,
+                                lo_off);
+    if (a_wrap) set_a_wrap(p, a_wrap);
+    gemm_launch(p, A_PLAIN, EPI_CONVT, ctx->dtype, ctx->stream, tile_cfg);
+}
+
+int32_t me_op_conv_transpose2x2_forms(me_ctx* ctx, const void* in16, int32_t B, int32_t H, int32_t W,
+                                      int32_t Cin, const void* w16, int32_t Cout, const float* bias,
+                                      float* out32, void* out16, int32_t border16, int32_t act16,
+                                      int32_t out_split, int32_t pixel_stride, int32_t lo_off, int32_t tile_cfg) {
+    ME_API_BEGIN(ctx)
+    conv_transpose2x2_forms(ctx, in16, B, H, W, Cin, 0, w16, Cout, bias, out32, out16, border16, act16, out_split, pixel_stride, lo_off, tile_cfg);
+    ME_API_END(ctx)
+}
+
+int32_t me_op_conv_transpose2x2_forms_wrap(me_ctx* ctx, const void* in16, int32_t B, int32_t H, int32_t W,
+                                           int32_t Cin, int32_t a_wrap, const void* w16, int32_t Cout, const float* bias,
+                                           float* out32, void* out16, int32_t border16, int32_t act16,
+                                           int32_t out_split, int32_t pixel_stride, int32_t lo_off, int32_t tile_cfg) {
+    ME_API_BEGIN(ctx)
+    conv_transpose2x2_forms(ctx, in16, B, H, W, Cin, a_wrap, w16, Cout, bias, out32, out16, border16, act16, out_split, pixel_stride, lo_off,
+                            tile_cfg);
+    ME_API_END(ctx)
+}
+
+int32_t me_op_conv_transpose2x2_pair(me_ctx* ctx, int32_t B, int32_t H, int32_t W, int32_t Cout, const void* in16_a, int32_t Cin_a,
+                                     const void* w16_a, const void* in16_b, int32_t Cin_b, int32_t a_wrap_b, const void* w16_b,
+                                     const float* bias_b, float* out32, void* out16, int32_t border16, int32_t act16, int32_t grid_cap,
+                                     int32_t tile_cfg) {
+    ME_API_BEGIN(ctx)
+    ME_CHECK(in16_a && w16_a && in16_b && w16_b && out32 && out16, ME_ERR_BAD_ARG, "me_op_conv_transpose2x2_pair: null pointer");
+    ME_CHECK(B > 0 && H > 0 && W > 0 && Cin_a > 0 && Cin_b > 0 && Cout > 0 && Cout % 8 == 0, ME_ERR_BAD_SHAPE,
+             "me_op_conv_transpose2x2_pair: %d x %d x %d, %d + %d -> %d", B, H, W, Cin_a, Cin_b, Cout);
+    ME_CHECK(act16 == ME_ACT_NONE || act16 == ME_ACT_RELU, ME_ERR_BAD_ARG, "me_op_conv_transpose2x2_pair: act16=%d", act16);
+    ME_CHECK(grid_cap >= 0, ME_ERR_BAD_ARG, "me_op_conv_transpose2x2_pair: grid_cap=%d", grid_cap);
+    check_a_wrap("me_op_conv_transpose2x2_pair", Cin_b, a_wrap_b);
+    const GemmParams first = convt_params(in16_a, B, H, W, Cin_a, w16_a, Cout, nullptr, nullptr, out16, border16 != 0, 0, act16);
+    GemmParams second = convt_params(in16_b, B, H, W, Cin_b, w16_b, Cout, bias_b, nullptr, nullptr, false, 0, ACT_NONE);
+    if (a_wrap_b) set_a_wrap(second, a_wrap_b);
+    GemmParams p = chain_convt(first, second, out32);
+    p.grid_cap = grid_cap;
+    gemm_launch(p, A_PLAIN, EPI_CONVT, ctx->dtype, ctx->stream, tile_cfg);
     ME_API_END(ctx)
 }
 

@@ -273,6 +273,19 @@ struct GemmParams {
     // Word 32 x: next-tile ticket of XCD x (x < 8), word 256: exited workgroups -- one 128-byte line each
     // (on one line the 512 prologue draws of a launch serialise in a single L2 channel).
     unsigned* queue;
+    // (the members below stand behind everything older kernels read: their kernel-argument offsets stay what they were)
+    // A_PLAIN rows whose last part repeats their first ([hi | lo | hi] operands, gemm_params.h set_a_parts): K slabs
+    // kt >= a_wrap are read from slab kt - a_wrap of the row, which is then stored a_wrap * 64 elements wide.  0: no wrap.
+    // EPI_CONVT only (the one consumer of such operands).
+    int32_t a_wrap;
+    // Chained second operand set (gemm_core.h gemm_pp_kernel<..., CHAIN>; the 256x256 two-group tile, EPI_CONVT, gemm_params.h
+    // chain_convt): a tile runs the K loop of (A, W, K), stores the 16-bit output act(acc + bias) from the accumulators, runs
+    // the K loop of (A2, W2, K2) on the SAME accumulators and stores out32 = acc + bias2 -- two ConvTransposes over one input
+    // grid summed in one accumulator.  A2 == null: an ordinary launch.
+    const void *A2, *W2;
+    int64_t lda2;
+    int32_t K2, a_wrap2, flop_k2;
+    const float* bias2;
 };
 constexpr int kGemmQueueWords = 9 * 32;
 

@@ -80,7 +80,8 @@ const TileKnobs& tile_knobs() {
 }
 
 static TileProblem tile_problem(const GemmParams& p, AMode amode, EpiKind epi) {
-    return {p.M, p.N, p.K, p.seg1, p.seg2, amode, epi, p.KH, p.KW, p.stride, p.out_H, p.out_W, p.Cin, p.tap_bias != nullptr, p.ln_out16 != nullptr};
+    return {p.M, p.N, p.K, p.seg1, p.seg2, amode, epi, p.KH, p.KW, p.stride, p.out_H, p.out_W, p.Cin, p.tap_bias != nullptr, p.ln_out16 != nullptr,
+            p.A2 != nullptr};
 }
 
 template <typename T>
@@ -227,8 +228,21 @@ void gemm_launch(const GemmParams& p_in, AMode amode, EpiKind epi, int32_t dtype
         ME_CHECK(p.out_H > 0 && p.out_W > 0 && p.M % (p.out_H * p.out_W) == 0, ME_ERR_BAD_SHAPE,
                  "conv: M=%d is not a multiple of %dx%d", p.M, p.out_H, p.out_W);
     } else {
-        ME_CHECK(p.lda % 8 == 0 && p.lda >= p.K, ME_ERR_BAD_SHAPE, "gemm: lda=%lld K=%d",
+        // (a_wrap: the row ends where the wrapped slabs start over)
+        ME_CHECK(p.a_wrap >= 0 && p.a_wrap < p.K / 64 && (p.a_wrap == 0 || (epi == EPI_CONVT && p.K - p.a_wrap * 64 <= p.a_wrap * 64)),
+                 ME_ERR_BAD_ARG, "gemm: a_wrap=%d of %d slabs", p.a_wrap, p.K / 64);
+        ME_CHECK(p.lda % 8 == 0 && p.lda >= (p.a_wrap ? p.a_wrap * 64 : p.K), ME_ERR_BAD_SHAPE, "gemm: lda=%lld K=%d",
                  (long long)p.lda, p.K);
+    }
+    if (p.A2) {
+        // a chained operand set: what the kernel's two passes assume (which tile: tile_choice.h config_refusal, below)
+        ME_CHECK(p.W2 && p.out16 && p.out32 && !p.bias && !p.lo_off16 && p.seg1 == 0 && p.act != ACT_GELU, ME_ERR_BAD_ARG,
+                 "gemm: a chained operand set takes an unbiased first set with a plain 16-bit output, and an f32 output");
+        ME_CHECK(p.K2 > 0 && p.K2 % 64 == 0 && p.a_wrap2 >= 0 && p.a_wrap2 < p.K2 / 64 &&
+                     (p.a_wrap2 == 0 || p.K2 - p.a_wrap2 * 64 <= p.a_wrap2 * 64) && p.lda2 % 8 == 0 &&
+                     p.lda2 >= (p.a_wrap2 ? p.a_wrap2 * 64 : p.K2),
+                 ME_ERR_BAD_SHAPE, "gemm: chained operand set K=%d lda=%lld a_wrap=%d", p.K2, (long long)p.lda2, p.a_wrap2);
+        p.queue = nullptr;  // (static tile order: a pass is not a tile the queue could hand out)
     }
     if (epi == EPI_HEAD_FINAL) ME_CHECK(p.N <= 32, ME_ERR_BAD_SHAPE, "head: N=%d > 32", p.N);
     if (p.tap_bias)  // the epilogue needs the output pixel's coordinates: the bordered 16-bit output has them
@@ -263,18 +277,20 @@ void gemm_launch(const GemmParams& p_in, AMode amode, EpiKind epi, int32_t dtype
     static const bool head_halo_on = env_on("ME_HEAD_HALO");
     const bool head_halo = epi == EPI_HEAD_FINAL && amode == A_CONV && force_cfg < 0 && head_halo_on && head_final_halo_fits(p);
     if (log_launches())
-        fprintf(stderr, "gemm_launch %s %s M=%d N=%d K=%d k=%dx%d/s%d cfg=%s res32=%d out32=%d out16=%d border=%d lo=%d hi2=%d ln=%d\n",
+        fprintf(stderr, "gemm_launch %s %s M=%d N=%d K=%d k=%dx%d/s%d cfg=%s res32=%d out32=%d out16=%d border=%d lo=%d hi2=%d ln=%d wrap=%d K2=%d\n",
                 amode == A_PLAIN ? "plain" : "conv", kEpi[epi], p.M, p.N, p.K, p.KH, p.KW, p.stride, gemm_config_name(cfg),
                 p.res32 != nullptr, p.out32 != nullptr, p.out16 != nullptr, p.out16_border, (int)p.lo_off16, (int)p.hi2_off16,
-                p.ln_out16 != nullptr);
+                p.ln_out16 != nullptr, p.a_wrap, p.A2 ? p.K2 : 0);
     // algorithmic bytes of the launch (every operand once): what an HBM-bound launch is priced against in bench.py's
     // kernels[] (the MFMA fraction misstates the residual launches and the ConvTransposes)
     double launch_bytes = 0.0;
     {
         const double MN = (double)p.M * p.N;
-        launch_bytes += amode == A_PLAIN ? (double)p.M * p.K * 2                                              // activation rows
+        // (a wrapped row is read as far as it is stored; a chained launch reads both operand sets)
+        launch_bytes += amode == A_PLAIN ? (double)p.M * (p.a_wrap ? p.a_wrap * 64 : p.K) * 2                 // activation rows
                                          : (double)p.M * (p.stride > 0 ? p.stride * p.stride : 1) * p.Cin * 2;  // input pixels, once
         launch_bytes += (double)p.N * p.K * 2;
+        if (p.A2) launch_bytes += (double)p.M * (p.a_wrap2 ? p.a_wrap2 * 64 : p.K2) * 2 + (double)p.N * p.K2 * 2;
         if (epi == EPI_HEAD_FINAL) launch_bytes += (double)p.M * 4;
         else {
             if (p.out16) launch_bytes += MN * 2 * (1 + (p.lo_off16 ? 1 : 0) + (p.hi2_off16 ? 1 : 0));
@@ -289,7 +305,8 @@ void gemm_launch(const GemmParams& p_in, AMode amode, EpiKind epi, int32_t dtype
                    std::string("gemm_kernel<") + (dtype == ME_DTYPE_F16 ? "f16" : "bf16") + "," +
                        (head_halo ? "12x16px-x32/8w-halo" : (epi == EPI_HEAD_FINAL ? "256x32x64/4w" : gemm_config_name(cfg))) + "," +
                        (amode == A_PLAIN ? "plain" : "conv") + "," + kEpi[epi] + ">",
-                   2.0 * (p.flop_rows ? p.flop_rows : p.M) * p.N * (p.flop_k ? p.flop_k : p.K), launch_bytes);
+                   2.0 * (p.flop_rows ? p.flop_rows : p.M) * p.N * ((p.flop_k ? p.flop_k : p.K) + (p.A2 ? (p.flop_k2 ? p.flop_k2 : p.K2) : 0)),
+                   launch_bytes);
     if (head_halo) {
         head_final_halo_launch(p, dtype, stream);
         return;

@@ -247,6 +247,13 @@ struct SlabWalk {
     }
     __device__ __forceinline__ int64_t next(const GemmParams& p, int kt) const { return a_off(p, kt); }
 };
+// GemmParams::a_wrap: the A slab that K slab kt of a launch is read from (rows whose last part repeats their first).  Compiled
+// into the EPI_CONVT instantiations only -- the one epilogue whose launches take such operands; the others keep their code.
+template <int EPI>
+__device__ __forceinline__ int wrapped_slab(int kt, int wrap) {
+    if constexpr (EPI == EPI_CONVT) return wrap > 0 && kt >= wrap ? kt - wrap : kt;
+    else return kt;
+}
 
 // Row tiles of a launch whose tile height does not divide the row-segment boundaries (the 352-row tile): every segment is
 // tiled from its own first row, a tile never straddles a boundary, and the rows a segment's last tile has beyond the
@@ -511,9 +518,11 @@ __device__ __forceinline__ void epilogue_granule(const GemmParams& p, const EpiR
         // checks in the granule (uniform branches, but branches: the granules' LDS reads and stores cannot be moved
         // across them) a store-heavy launch pays for them: the head's ConvTranspose 231 us, the same GEMM with a
         // row-major store through the run-time path 261 us, through the constant path 182 us.
+        // MODE 8: the 16-bit output alone, with the launch's activation -- the mid epilogue of a chained launch (gemm_pp_kernel<...,
+        // CHAIN>), whose f32 output belongs to the final one (mode 5)
         const bool w32 = MODE == 0 ? p.out32 != nullptr : (MODE == 5 || MODE == 6);
-        const bool w16 = MODE == 0 ? p.out16 != nullptr : (MODE == 4 || MODE == 6 || MODE == 7);
-        const bool relu = MODE == 0 ? p.act == ACT_RELU : false;
+        const bool w16 = MODE == 0 ? p.out16 != nullptr : (MODE == 4 || MODE == 6 || MODE == 7 || MODE == 8);
+        const bool relu = (MODE == 0 || MODE == 8) ? p.act == ACT_RELU : false;
         const bool lo = MODE == 0 ? p.lo_off16 != 0 : MODE == 7;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -550,8 +559,10 @@ __device__ __forceinline__ void epilogue_granule(const GemmParams& p, const EpiR
 // TILE2D (the halo convolution kernel below): the tile is a 16 x 16 block of output pixels instead of 256
 // consecutive rows -- m0 is then the TILE index (image-major, tile rows, tile columns) and row t of the tile is pixel
 // (t >> 4, t & 15) of it; everything downstream sees the pixel's linear row index and coordinates as before.
+// CHAIN_PART (EPI_CONVT, a chained launch: GemmParams::A2): 0 the mid epilogue -- the 16-bit output act(acc) alone, the
+// accumulators left as they are for the second K loop --, 1 the final one -- out32 = acc + bias2 alone; -1: an ordinary launch.
 template <typename T, int EPI, int MI, int NI, int TM, int TN, int MI_CH, bool PIN_CONSTS = false,
-          typename Hook = NoHook, int OUT8 = 0, bool TILE2D = false, int TILE_H = 16, bool CF_ALLOWED = true>
+          typename Hook = NoHook, int OUT8 = 0, bool TILE2D = false, int TILE_H = 16, bool CF_ALLOWED = true, int CHAIN_PART = -1>
 __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[MI][NI], int m0, int n0,
                                               int wm, int wn, int lane, char* epi_lds,
                                               Hook after_loads = Hook(), int m_lim = -1) {
@@ -681,7 +692,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
         }
         if (n_ok) {
             const int seg = row_segment(p, m0);
-            const float* bias = seg == 0 ? p.bias : (seg == 1 ? p.bias_s1 : p.bias_s2);
+            const float* bias = CHAIN_PART >= 0 ? (CHAIN_PART == 1 ? p.bias2 : nullptr) : (seg == 0 ? p.bias : (seg == 1 ? p.bias_s1 : p.bias_s2));
             if (bias) {
                 lc.bias[0] = *reinterpret_cast<const float4*>(bias + lc.co);
                 if (hi_ok) lc.bias[1] = *reinterpret_cast<const float4*>(bias + lc.co + 4);
@@ -1007,6 +1018,10 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
             }
             else
                 run(std::integral_constant<int, 0>());
+        } else if constexpr (EPI == EPI_CONVT && CHAIN_PART == 0) {
+            run(std::integral_constant<int, 8>());
+        } else if constexpr (EPI == EPI_CONVT && CHAIN_PART == 1) {
+            run(std::integral_constant<int, 5>());
         } else if constexpr (EPI == EPI_CONVT) {
             const bool plain = p.act == ACT_NONE;
             if (plain && p.out16 && !p.out32 && !p.lo_off16)
@@ -1431,7 +1446,7 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void gemm_kernel(const GemmParams p
     // Staging of slab kt of tile t into LDS buffer buf (slabs are staged in order: kt = 0 rewinds the taps)
     SlabWalk<AMODE> walk;
     walk.init(p);
-    auto stage_a_offset = [&](int kt) -> int64_t { return walk.next(p, kt); };
+    auto stage_a_offset = [&](int kt) -> int64_t { return walk.next(p, wrapped_slab<EPI>(kt, p.a_wrap)); };
     auto stage_piece = [&](const TileSrc& t, int piece, int64_t a_koff, int64_t w_koff, int buf) {
         char* la = smem + buf * STAGE_BYTES;
         if (piece < A_ITERS)
@@ -1662,9 +1677,16 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void gemm_kernel(const GemmParams p
 // slab with a counted vmcnt (its newest DMA group may stay in flight), group 0 with vmcnt(0).
 // Requires K >= 128.
 // LNF: the residual epilogue also writes the LayerNorm of the rows it updates (resid_ln_epilogue above)
-template <typename T, int BM, int BN, int WM, int WN, int AMODE, int EPI, int WSLOTS = 3, bool LNF = false>
+// CHAIN (the 256x256 tile's ConvTranspose form; GemmParams::A2): every tile is TWO passes of the loop below on one set of
+// accumulators -- pass 0 walks (A, W, K) from zero and ends in the mid epilogue (the 16-bit output, accumulators untouched),
+// pass 1 walks (A2, W2, K2) on top and ends in the final one (out32 = acc + bias2).  To the K stream a pass is what a tile is
+// to the unchained kernel: pass 1's first slabs are requested under pass 0's last slabs and its epilogue, the next tile's
+// under pass 1's; the same two rings, the same scratch slots, one barrier behind each epilogue, no wait on another workgroup.
+template <typename T, int BM, int BN, int WM, int WN, int AMODE, int EPI, int WSLOTS = 3, bool LNF = false, bool CHAIN = false>
 __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
     static_assert(!LNF || (BM > 256 && EPI == EPI_RESID_SCALE), "LayerNorm fusion: the 352-row tile's residual epilogue");
+    static_assert(!CHAIN || (BM == 256 && BN == 256 && AMODE == A_PLAIN && EPI == EPI_CONVT && WSLOTS == 3 && !LNF),
+                  "chained operand sets: the 256x256 tile's ConvTranspose form");
     static_assert(WSLOTS == 3 || WSLOTS == 2, "weight ring of three slots (two slabs ahead) or two (one ahead)");
     static_assert(WM * WN == 8, "two groups of four waves");
     static_assert(BM / WM >= BN / WN, "the first k-substep's MI groups prefetch the NI weight fragments");
@@ -1710,6 +1732,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
     const int srow = lane >> 3, sslot = lane & 7;
     struct Src {
         int m0, n0, m_lim, row_tile;
+        int part;  // CHAIN: which operand set this pass walks
         // this wave's DMA sources, activation rows (group 0) or weight rows (group 1): a uniform base (the
         // tile's first row) and per-lane 32-bit byte offsets from it -- the kernel has no VGPR to spare
         // for 64-bit pointers
@@ -1717,7 +1740,13 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
         unsigned s[TALL ? 2 : IT];  // TALL: {offset of the first piece, largest offset that stays inside the operand}
     };
     auto pixel_of = [&](int gm) -> int64_t { return conv_pixel(p, gm); };
-    auto setup = [&](Src& t, int vb) {
+    // the operand set of a pass (CHAIN; otherwise the launch's only one)
+    auto set_A = [&](int part) { return (const char*)(CHAIN && part ? p.A2 : p.A); };
+    auto set_W = [&](int part, int m0) { return CHAIN && part ? (const char*)p.W2 : segment_weights(p, m0); };
+    auto set_lda = [&](int part) { return CHAIN && part ? p.lda2 : p.lda; };
+    auto set_K = [&](int part) { return CHAIN && part ? p.K2 : p.K; };
+    auto setup = [&](Src& t, int vb, int part = 0) {
+        t.part = part;
         if constexpr (LNF) {
             t.row_tile = lnf_row_tile(vb);
             t.n0 = ((vb >> 3) % lnf_nbn) * BN;
@@ -1747,10 +1776,10 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
         if (group == 0) {
             int64_t base_el;  // element offset of the tile's first row (uniform)
             if constexpr (AMODE == A_PLAIN)
-                base_el = (int64_t)t.m0 * p.lda;
+                base_el = (int64_t)t.m0 * set_lda(part);
             else
                 base_el = pixel_of(t.m0) * p.Cin;
-            t.base = (const char*)p.A + base_el * 2;
+            t.base = set_A(part) + base_el * 2;
 #pragma unroll
             for (int i = 0; i < A_IT; ++i) {
                 const int row = (i * HW + gw) * 8 + srow;
@@ -1759,31 +1788,32 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
                 gm = gm < p.M ? gm : p.M - 1;
                 int64_t el;
                 if constexpr (AMODE == A_PLAIN)
-                    el = (int64_t)gm * p.lda;
+                    el = (int64_t)gm * set_lda(part);
                 else
                     el = pixel_of(gm) * p.Cin;
                 t.s[i] = (unsigned)((el - base_el) * 2) + chunk * 16;
             }
         } else {
-            t.base = segment_weights(p, t.m0) + (int64_t)t.n0 * p.K * 2;
+            t.base = set_W(part, t.m0) + (int64_t)t.n0 * set_K(part) * 2;
 #pragma unroll
             for (int i = 0; i < B_IT; ++i) {
                 const int row = (i * HW + gw) * 8 + srow;
                 const int chunk = sslot ^ ((row >> 1) & 7);
                 int gn = t.n0 + row;
                 gn = gn < p.N ? gn : p.N - 1;
-                t.s[i] = (unsigned)((int64_t)(gn - t.n0) * p.K * 2) + chunk * 16;
+                t.s[i] = (unsigned)((int64_t)(gn - t.n0) * set_K(part) * 2) + chunk * 16;
             }
         }
     };
 
-    const int nk = p.K / 64;
     SlabWalk<AMODE> walk;
     walk.init(p);
-    auto stage_a_offset = [&](int kt) -> int64_t { return walk.next(p, kt); };
+    auto stage_a_offset = [&](const Src& t, int kt) -> int64_t {
+        return walk.next(p, wrapped_slab<EPI>(kt, CHAIN && t.part ? p.a_wrap2 : p.a_wrap));
+    };
     const unsigned smem_base = __builtin_amdgcn_readfirstlane(lds_address(smem));
     auto stage_T = [&](const Src& t, int kt, int slot) {  // group 0
-        const char* base = uniform_ptr(t.base + stage_a_offset(kt));
+        const char* base = uniform_ptr(t.base + stage_a_offset(t, kt));
         const unsigned dst = smem_base + slot * A_BYTES + gw * 1024;
         if constexpr (TALL) {
             const unsigned step = (unsigned)(HW * 8) * (unsigned)(p.lda * 2);
@@ -1827,7 +1857,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
     int vb = blockIdx.x;
     Src cur, nxt;
     setup(cur, vb);
-    const bool dyn = WSLOTS == 3 && p.queue != nullptr && ntiles > (int)gridDim.x;  // dynamic tile order (TileQueue)
+    const bool dyn = WSLOTS == 3 && !CHAIN && p.queue != nullptr && ntiles > (int)gridDim.x;  // dynamic tile order (TileQueue)
     TileQueue tq;
     tq.init(p.queue, ntiles);
     int next_vb = vb + (int)gridDim.x;
@@ -1879,14 +1909,26 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
 #endif
     ME_STAMP();
 
+    const int nk_set0 = p.K / 64;
+    f32x4 acc_passes[CHAIN ? MI : 1][CHAIN ? NI : 1];  // CHAIN: the accumulators outlive a pass of the loop
     while (true) {
-        const bool has_next = next_vb >= 0 && next_vb < ntiles && (!LNF || lnf_row_tile(next_vb) < lnf_nbm);
-        if (has_next) setup(nxt, next_vb);
-        f32x4 acc[MI][NI];
+        // what follows this pass in the K stream: the next tile -- or (CHAIN, pass 0) the same tile's second operand set
+        const bool to_part1 = CHAIN && cur.part == 0;
+        const bool has_next = to_part1 || (next_vb >= 0 && next_vb < ntiles && (!LNF || lnf_row_tile(next_vb) < lnf_nbm));
+        if (to_part1) setup(nxt, vb, 1);
+        else if (has_next) setup(nxt, next_vb);
+        f32x4 acc_tile[CHAIN ? 1 : MI][CHAIN ? 1 : NI];
+        f32x4 (&acc)[MI][NI] = *[&]() {
+            if constexpr (CHAIN) return &acc_passes;
+            else return &acc_tile;
+        }();
+        if (!CHAIN || cur.part == 0) {
 #pragma unroll
-        for (int i = 0; i < MI; ++i)
+            for (int i = 0; i < MI; ++i)
 #pragma unroll
-            for (int j = 0; j < NI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int j = 0; j < NI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        const int nk = CHAIN ? set_K(cur.part) / 64 : nk_set0;
 
         for (int kt = 0; kt < nk; ++kt) {
             ME_PHASE(-1);
@@ -1978,6 +2020,11 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
                 static_assert(HW * SCR + BM * (WN * 8 + 8) <= A_BYTES, "row statistics beside the epilogue scratch");
                 resid_ln_epilogue<T, MI, NI, TM, TN, BM>(p, acc, cur.m0, cur.n0, wm, wn, lane, tid, scr, scratch0 + HW * SCR,
                                                          cur.m_lim, cur.row_tile);
+            } else if constexpr (CHAIN) {
+                if (cur.part == 0)
+                    gemm_epilogue<T, EPI, MI, NI, TM, TN, MI_CH, true, NoHook, 0, false, 16, true, 0>(p, acc, cur.m0, cur.n0, wm, wn, lane, scr);
+                else
+                    gemm_epilogue<T, EPI, MI, NI, TM, TN, MI_CH, true, NoHook, 0, false, 16, true, 1>(p, acc, cur.m0, cur.n0, wm, wn, lane, scr);
             } else
             gemm_epilogue<T, EPI, MI, NI, TM, TN, MI_CH, true>(p, acc, cur.m0, cur.n0, wm, wn, lane, scr, [&]() {
                 if (dyn && has_next && tid == 0) drawn = tq.draw();
@@ -1998,6 +2045,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
         __builtin_amdgcn_s_barrier();  // the scratch slots are restaged by the next tile's first slab
         asm volatile("" ::: "memory");
         cur = nxt;
+        if (to_part1) continue;  // the same tile: vb / next_vb stay
         vb = next_vb;
         if (dyn) {
             next_vb = __builtin_amdgcn_readfirstlane(*reinterpret_cast<volatile int*>(scratch0));
@@ -2012,12 +2060,13 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
 #undef ME_STAMP
 #undef ME_PHASE
 
-template <typename T, int BM, int BN, int WM, int WN, int AMODE, int EPI, int WSLOTS = 3, bool LNF = false>
+template <typename T, int BM, int BN, int WM, int WN, int AMODE, int EPI, int WSLOTS = 3, bool LNF = false, bool CHAIN = false>
 void gemm_launch_pp(const GemmParams& p, hipStream_t stream) {
     constexpr int smem = (2 * BM + WSLOTS * BN) * 128;
     static_assert(smem <= 160 * 1024, "the tile's rings exceed a CU's LDS");
     ME_CHECK(p.K >= 128, ME_ERR_BAD_SHAPE, "gemm: the two-group kernel needs K >= 128 (K = %d)", p.K);
-    auto kern = gemm_pp_kernel<T, BM, BN, WM, WN, AMODE, EPI, WSLOTS, LNF>;
+    if (CHAIN) ME_CHECK(p.K2 >= 128, ME_ERR_BAD_SHAPE, "gemm: the two-group kernel needs K >= 128 (chained K = %d)", p.K2);
+    auto kern = gemm_pp_kernel<T, BM, BN, WM, WN, AMODE, EPI, WSLOTS, LNF, CHAIN>;
     static PerDeviceOnce once;
     int64_t ntiles = (BM > 256 ? (int64_t)seg_row_tiles<BM>(p.M, p.seg1, p.seg2) : cdiv(p.M, BM)) * cdiv(p.N, BN);
     if (LNF) ntiles = cdiv((int64_t)seg_row_tiles<BM>(p.M, p.seg1, p.seg2), 8) * 8 * cdiv(p.N, BN);  // the kernel's padded walk
@@ -2571,7 +2620,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_ring_kernel(const GemmParams
     const int nk = p.K / 64;
     SlabWalk<AMODE> walk;
     walk.init(p);
-    auto stage_a_offset = [&](int kt) -> int64_t { return walk.next(p, kt); };
+    auto stage_a_offset = [&](int kt) -> int64_t { return walk.next(p, wrapped_slab<EPI>(kt, p.a_wrap)); };
     const unsigned smem_base = __builtin_amdgcn_readfirstlane(lds_address(smem));
     auto stage = [&](int kt, int slot) {
         const char* ab = uniform_ptr(a_base + stage_a_offset(kt));
@@ -2672,7 +2721,8 @@ void gemm_dispatch(const GemmParams& p, int cfg, hipStream_t stream);
     template <>                                                                                                         \
     void gemm_dispatch<T, AMODE, EPI>(const GemmParams& p, int cfg, hipStream_t stream) {                               \
         constexpr int kAMode = AMODE, kEpi = EPI; /* (what ME_TILE_ARM asks the table about) */                         \
-        switch (cfg) {                                                                                                  \
+        const bool chained = p.A2 != nullptr; /* (its arm stands behind the switch: see above) */                       \
+        switch (chained ? -1 : cfg) {                                                                                   \
             ME_TILE_ARM(CFG_PP256, gemm_launch_pp<T, 256, 256, 2, 4, AMODE, EPI>(p, stream))                            \
             ME_TILE_ARM(CFG_128, if constexpr (EPI == EPI_STORE) {                                                      \
                 if (p.split_k > 1) {                                                                                    \
@@ -2701,6 +2751,13 @@ void gemm_dispatch(const GemmParams& p, int cfg, hipStream_t stream);
                 }                                                                                                       \
             } gemm_launch_pp<T, 352, 256, 2, 4, AMODE, EPI, 2>(p, stream))                                              \
             ME_TILE_ARM(CFG_8PH, gemm_launch_8ph<T, EPI>(p, stream))                                                    \
+        }                                                                                                               \
+        /* a chained operand set (GemmParams::A2): the 256x256 two-group tile's ConvTranspose form and nothing else */  \
+        if constexpr (AMODE == A_PLAIN && EPI == EPI_CONVT) {                                                           \
+            if (chained && cfg == CFG_PP256) {                                                                          \
+                gemm_launch_pp<T, 256, 256, 2, 4, AMODE, EPI, 3, false, true>(p, stream);                               \
+                return;                                                                                                 \
+            }                                                                                                           \
         }                                                                                                               \
         fail(ME_ERR_BAD_ARG, "gemm: tile config %d is not compiled for (A-mode %d, epilogue %d)", cfg, (int)AMODE, (int)EPI); \
     }

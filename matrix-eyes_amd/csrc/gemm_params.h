@@ -24,7 +24,14 @@ inline GemmParams linear_params(int64_t M, int N, int K, const void* A, const vo
 }
 // Split operands (model.h SplitStage).  The A rows hold `parts` K-wide parts ([hi | lo], [hi | lo | hi]) against weights
 // stored [W | W (| W)]: the kernel walks parts * K, the layer's FLOPs stay those of K
-inline void set_a_parts(GemmParams& p, int parts) { p.flop_k = p.K, p.K *= parts, p.lda = p.K; }
+// wrap_third ([hi | lo | hi] only): the rows are stored two parts wide and the kernel reads the third part from the first
+// (GemmParams::a_wrap) -- the same K order against the same weights, a third of the operand's bytes neither written nor read
+inline void set_a_wrap(GemmParams& p, int stored_k) { p.lda = stored_k, p.a_wrap = stored_k / 64; }
+inline void set_a_parts(GemmParams& p, int parts, bool wrap_third = false) {
+    const int part_k = p.K;
+    p.flop_k = part_k, p.K *= parts, p.lda = p.K;
+    if (parts == 3 && wrap_third) set_a_wrap(p, 2 * part_k);
+}
 // ... and the 16-bit output is written as rows / pixels of `parts` C-wide parts
 inline void set_out16_parts(GemmParams& p, int64_t C, int parts) {
     if (parts >= 2) p.ldc16 = parts * C, p.lo_off16 = (int32_t)C;
@@ -90,18 +97,30 @@ inline GemmParams conv_params(const void* in16b, int B, int Hin, int Win, int Ci
 // ConvTranspose2d(2,2,stride 2) of an unbordered NHWC operand [B*H*W][Cin] -> [B][2H][2W][Cout] (EPI_CONVT)
 // pixel_stride: channels per pixel of out16 when it is a slice of a wider map (0: Cout, or 2 Cout when split);
 // out_split: out16 pixels are [hi | lo], the lo part lo_off channels after the hi part (0: Cout);
-// k_copies > 0: A rows hold this many Cin-wide parts ([hi | lo | hi] = 3)
+// k_copies > 0: A rows hold this many Cin-wide parts ([hi | lo | hi] = 3; wrap_third: stored [hi | lo], set_a_parts)
 inline GemmParams convt_params(const void* in16, int B, int H, int W_, int Cin, const void* W, int Cout, const float* bias,
                                float* out32, void* out16, bool border16, int64_t pixel_stride, int act16, bool a_split = false,
-                               bool out_split = false, int64_t lo_off = 0, int k_copies = 0) {
+                               bool out_split = false, int64_t lo_off = 0, int k_copies = 0, bool wrap_third = false) {
     GemmParams p = linear_params((int64_t)B * H * W_, 4 * Cout, Cin, in16, W, bias, out16, out32, act16);
-    set_a_parts(p, k_copies > 0 ? k_copies : (a_split ? 2 : 1));
+    set_a_parts(p, k_copies > 0 ? k_copies : (a_split ? 2 : 1), wrap_third);
     // the composed deconv o out_conv (k_copies == 3) stands for two layers of SURVEY App. B: ConvT (Cin x 4 Cout per
     // input pixel) and the 1x1 conv at 4x the pixels (Cout x Cout each) -- twice the ConvT's FLOPs when Cin == Cout
     if (k_copies == 3) p.flop_k = 2 * Cin;
     p.out_H = H, p.out_W = W_, p.Cout = Cout, p.out16_border = border16 ? 1 : 0, p.ldc = Cout;
     if (out_split) p.lo_off16 = (int32_t)(lo_off ? lo_off : Cout);
     if (out_split || pixel_stride) p.ldc16 = pixel_stride ? pixel_stride : 2 * Cout;
+    return p;
+}
+
+// Two ConvTransposes over the SAME input grid onto the same [B][2H][2W][Cout] map as one launch (GemmParams::A2; the 256x256
+// two-group tile): `first` (no bias) keeps its 16-bit output (activation, border) and gives up its f32 one, `second` gives the
+// launch its operands as the chained set; out32 = (sum over K of first + sum over K of second) + second's bias, summed in one
+// accumulator.
+inline GemmParams chain_convt(const GemmParams& first, const GemmParams& second, float* out32) {
+    GemmParams p = first;
+    p.out32 = out32;
+    p.A2 = second.A, p.W2 = second.W, p.lda2 = second.lda, p.K2 = second.K, p.a_wrap2 = second.a_wrap, p.bias2 = second.bias;
+    p.flop_k2 = second.flop_k ? second.flop_k : second.K;
     return p;
 }
 

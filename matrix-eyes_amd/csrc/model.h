@@ -252,6 +252,12 @@ struct me_ctx {
     size_t head_fused_off = 0;   // 0: not composed
     size_t feat_fused_off = 0;   // 0: not composed
     bool features_pre = false;   // "features.16b" holds out_conv's INPUT (stage_decoder_levels with the composed head[0])
+    // Decoder level 0 takes x0 + x1 from ONE chained ConvTranspose launch (pipeline.hip enc0_sum_applies): set by
+    // extract_depth for the length of a call, never by the stage-wise entries.  The latent0 chain then stops before its last
+    // ConvTranspose and leaves that launch's operand (enc0_last_in, a side x side map), level 1 does not launch its composed one.
+    bool enc0_sum = false;
+    const void* enc0_last_in = nullptr;
+    int enc0_last_side = 0;
     std::map<std::string, std::vector<float>> factor_keep;
     // me_ctx_set_weight_packer: 0 the host packer (load_weight's loops on one core, a synchronous upload per tensor),
     // 1 the device packer (weight_pack.hip: raw bytes through a pinned ring, one pack kernel per tensor on the stream)
@@ -477,6 +483,8 @@ void stage_encoder(me_ctx* ctx, const float* img32, int B, bool with_fov);
 void stage_encoder_trunk(me_ctx* ctx, const float* img32, int B, bool with_fov);
 void stage_encoder_latents(me_ctx* ctx, int B);
 void stage_decoder(me_ctx* ctx, int B, bool want_features32);
+// whether a whole extract_depth call of this batch may sum decoder level 0's two ConvTransposes in one launch (me_ctx::enc0_sum)
+bool enc0_sum_applies(const me_ctx* ctx, int B);
 // decoder levels `first` down to `last` (4 = lowest resolution ... 0); stage_decoder = levels 4 to 0
 void stage_decoder_levels(me_ctx* ctx, int B, bool want_features32, int first, int last);
 void stage_fov_vit(me_ctx* ctx, int B, hipStream_t s);

@@ -104,9 +104,9 @@ void conv(me_ctx* ctx, const void* in16b, int B, int Hin, int Win, int Cin, cons
 void convt(me_ctx* ctx, const void* in16, int B, int H, int W_, int Cin, const void* W, int Cout,
            const float* bias, float* out32, void* out16, bool border16, int64_t pixel_stride,
            int act16, hipStream_t s, bool a_split = false, bool out_split = false, int64_t lo_off = 0,
-           int k_copies = 0) {
+           int k_copies = 0, bool wrap_third = false) {
     GemmParams p = convt_params(in16, B, H, W_, Cin, W, Cout, bias, out32, out16, border16, pixel_stride, act16, a_split,
-                                out_split, lo_off, k_copies);
+                                out_split, lo_off, k_copies, wrap_third);
     p.grid_cap = ctx->grid_cap;
     gemm_launch(p, A_PLAIN, EPI_CONVT, ctx->dtype, s);
 }
@@ -116,10 +116,11 @@ size_t bordered_bytes(int B, int H, int W, int C) { return (size_t)B * (H + 2) *
 // encoder.rs:210-216 forward_seq over an upsample block: 1x1 conv (no bias) then ConvT x n.
 // The last ConvT writes the caller's outputs.  With SPLIT_UPSAMPLE the input and every intermediate are
 // [hi | lo] operands; last_split / last_lo_off say whether (and where) the last 16-bit output is split too.
+// skip_last (me_ctx::enc0_sum): the chain stops before its last ConvT and leaves that launch's operand in the context
 void run_upsample(me_ctx* ctx, const std::string& tag, const void* in16, int B, int H,
                   const UpsampleW& u, float* last32, void* last16, bool last_border,
                   int64_t last_pixel_stride, int last_act16, hipStream_t s, bool last_split = false,
-                  int64_t last_lo_off = 0) {
+                  int64_t last_lo_off = 0, bool skip_last = false) {
     const int C = ctx->C();
     const bool sp = ctx->split(SPLIT_UPSAMPLE);
     const int64_t M = (int64_t)B * H * H;
@@ -131,7 +132,9 @@ void run_upsample(me_ctx* ctx, const std::string& tag, const void* in16, int B, 
     const int n = (int)u.convt.size();
     for (int i = 0; i < n; ++i) {
         const bool last = i == n - 1;
-        if (last) {
+        if (last && skip_last) {
+            ctx->enc0_last_in = cur, ctx->enc0_last_side = h;
+        } else if (last) {
             convt(ctx, cur, B, h, h, u.cin[i], u.convt[i], u.cout[i], nullptr, last32, last16,
                   last_border, last_pixel_stride, last_act16, s, sp, last_split, last_lo_off);
         } else {
@@ -547,10 +550,38 @@ void stage_encoder_latents(me_ctx* ctx, int B) {
     void* enc1 = site_buf(ctx, "enc1.16b", bordered_bytes(B, H1, H1, e0) * wide_dec);
     run_upsample(ctx, "up_latent1", lat1, B, side0, ctx->w.up_latent1, nullptr, enc1, true, 0,
                  ACT_NONE, s, sp_dec);
-    float* enc0_32 = (float*)site_buf(ctx, "enc0.f32", (size_t)B * H0 * H0 * dec * 4);
+    // (me_ctx::enc0_sum: the f32 encoding is never formed -- decoder level 0 takes its sum with level 1's features from the
+    // launch that also writes "enc0.r16b")
+    float* enc0_32 = ctx->enc0_sum ? nullptr : (float*)site_buf(ctx, "enc0.f32", (size_t)B * H0 * H0 * dec * 4);
     void* enc0_r16 = site_buf(ctx, "enc0.r16b", bordered_bytes(B, H0, H0, dec));
     run_upsample(ctx, "up_latent0", lat0, B, side0, ctx->w.up_latent0, enc0_32, enc0_r16, true, 0,
-                 ACT_RELU, s);
+                 ACT_RELU, s, false, 0, ctx->enc0_sum);
+}
+
+// [hi | lo | hi] operands of the composed ConvTransposes stored as [hi | lo], the third part read from the first
+// (GemmParams::a_wrap): bit for bit the same sums.  ME_A_WRAP=0: the three parts stored.
+static bool a_wrap_on() {
+    static const bool on = env_on("ME_A_WRAP");
+    return on;
+}
+
+// Decoder level 0 adds two maps that are each written once and read once: x1 = the last ConvTranspose of the latent0 chain and
+// x0 = level 1's composed out_conv o deconv ConvTranspose, both 2x2 stride-2 over the same grid onto the same map.  Chained
+// (gemm_params.h chain_convt) they are ONE accumulator over K1 + K2 and one f32 map less is written and read.  Applies to a
+// whole extract_depth call when level 1 has its composed weights, the chain's last layer has the decoder's width and both
+// launches would run on the 256x256 two-group tile at this shape anyway; ME_ENC0_SUM=0: the two launches.
+bool enc0_sum_applies(const me_ctx* ctx, int B) {
+    static const bool on = env_on("ME_ENC0_SUM");
+    const UpsampleW& u = ctx->w.up_latent0;
+    const FusionW& fw = ctx->w.fusions[1];
+    const int dec = ctx->cfg.dec_dim, h = 16 * ctx->g();
+    if (!on || !(ctx->split(SPLIT_FUSION_OUT) && fw.deconv && fw.fused_w) || u.convt.empty() || u.cout.back() != dec) return false;
+    const int K1 = u.cin.back() * (ctx->split(SPLIT_UPSAMPLE) ? 2 : 1), K2 = 3 * dec;
+    for (const int K : {K1, K2}) {
+        const TileProblem q = {B * h * h, 4 * dec, K, 0, 0, A_PLAIN, EPI_CONVT, 0, 0, 0, h, h, 0, false, false};
+        if (K % 64 || K < 128 || resolve_config(q, -1, tile_knobs()) != CFG_PP256) return false;
+    }
+    return true;
 }
 
 void stage_encoder_trunk(me_ctx* ctx, const float* img32, int B, bool fov_async /* = with_fov */) {
@@ -667,7 +698,23 @@ void stage_decoder_levels(me_ctx* ctx, int B, bool want_features32, int first, i
         // features_i = convs[i-1](encoding) (3x3, no bias); level 0 uses the encoding as is
         float* x1_32;
         void* x1_r16;
-        if (i == 0) {
+        if (i == 0 && ctx->enc0_sum) {
+            // x0 + x1 from one launch: the latent0 chain's last ConvTranspose (its ReLU'd bordered 16-bit output from the
+            // accumulators after its own K loop) and level 1's composed one on top, + out_conv's bias
+            const UpsampleW& u = ctx->w.up_latent0;
+            const FusionW& f1 = ctx->w.fusions[1];
+            ME_CHECK(ctx->enc0_last_in && ctx->enc0_last_side * 2 == h, ME_ERR_BAD_ARG, "decoder: the latent0 chain left no operand for level 0");
+            x1_32 = (float*)site_buf(ctx, "dec0.x01.f32", n32);
+            x1_r16 = (void*)enc;
+            feat32 = nullptr;
+            const GemmParams first = convt_params(ctx->enc0_last_in, B, h / 2, h / 2, u.cin.back(), u.convt.back(), dec, nullptr, nullptr, x1_r16,
+                                                  true, 0, ACT_RELU, ctx->split(SPLIT_UPSAMPLE));
+            const GemmParams second = convt_params(ctx->bufs.at("dec1.v16").p, B, h / 2, h / 2, dec, f1.fused_w, dec, f1.out_b, nullptr, nullptr,
+                                                   false, 0, ACT_NONE, false, false, 0, 3, a_wrap_on());
+            GemmParams p = chain_convt(first, second, x1_32);
+            p.grid_cap = ctx->grid_cap;
+            gemm_launch(p, A_PLAIN, EPI_CONVT, ctx->dtype, s, CFG_PP256);
+        } else if (i == 0) {
             x1_32 = (float*)ctx->bufs.at("enc0.f32").p;
             x1_r16 = (void*)enc;
         } else {
@@ -706,7 +753,8 @@ void stage_decoder_levels(me_ctx* ctx, int B, bool want_features32, int first, i
         // the operands of deconv and out_conv have no residual path beside them: [hi | lo] under SPLIT_FUSION_OUT,
         // [hi | lo | hi] where the two are composed into one ConvTranspose (FusionW::fused_w)
         const bool fused = spf && fw.deconv && fw.fused_w;
-        const size_t wf = fused ? 3 : (spf ? 2 : 1);
+        const bool wrap = fused && a_wrap_on();  // [hi | lo | hi] stored as [hi | lo]
+        const size_t wf = fused && !wrap ? 3 : (spf ? 2 : 1);
         if (i == 0) {
             // decoder.rs:101 out_conv + mod.rs:326 head[0] as ONE convolution (weights.hip compose_features): this level's last
             // convolution writes out_conv's INPUT as head[0]'s zero-bordered operand, the 1x1 launch and the feature map between
@@ -726,11 +774,13 @@ void stage_decoder_levels(me_ctx* ctx, int B, bool want_features32, int first, i
         o4.out16 = v16, o4.res32 = out32, o4.parts16 = (int)wf;
         conv(ctx, t2_r16, B, h, h, dec, fw.resnet2.w[1], dec, 3, 1, fw.resnet2.b[1], o4, s);
         if (fused) {
+            // (me_ctx::enc0_sum: level 0's chained launch reads this level's "dec1.v16" itself)
+            if (i == 1 && ctx->enc0_sum) continue;
             // out_conv(deconv(v)) as ONE launch: f32 features of the next level straight from the pixel shuffle
             const int64_t Mo = (int64_t)B * 4 * h * h;
             feat32 = (float*)site_buf(ctx, L + ".feat.f32", (size_t)Mo * dec * 4);
             convt(ctx, v16, B, h, h, dec, fw.fused_w, dec, fw.out_b, feat32, nullptr, false, 0, ACT_NONE, s, false, false,
-                  0, 3);
+                  0, 3, wrap);
             continue;
         }
         // deconv (levels 1-4) then out_conv 1x1 (+bias)

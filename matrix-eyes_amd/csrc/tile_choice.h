@@ -90,6 +90,7 @@ struct TileProblem {
     int32_t KH, KW, stride, out_H, out_W, Cin;  // A_CONV
     bool tap_bias;   // GemmParams::tap_bias is set: the launch needs the tap-bias epilogue mode
     bool ln_out16;   // GemmParams::ln_out16 is set: the launch is the fused residual + LayerNorm
+    bool chained = false;  // GemmParams::A2 is set: two ConvTransposes summed in one accumulator (gemm_core.h gemm_pp_kernel<..., CHAIN>)
 };
 
 // The environment knobs the decisions read, as the .hip side found them (the header never asks the environment).
@@ -190,6 +191,8 @@ struct TileRefusal {
     const char* why;
 };
 inline TileRefusal config_refusal(const TileProblem& q, int cfg) {
+    if (q.chained && !(cfg == CFG_PP256 && q.amode == A_PLAIN && q.epi == EPI_CONVT))
+        return {TILE_BAD_ARG, "a chained operand set takes the 256x256 two-group tile's ConvTranspose form"};
     if (q.ln_out16 && !(cfg == CFG_PP352 && q.amode == A_PLAIN && q.epi == EPI_RESID_SCALE))
         return {TILE_BAD_ARG, "the fused LayerNorm takes the 352-row tile's residual epilogue (K >= 128)"};
     if (cfg == CFG_HALO && !halo_fits(q, 16, 256))
