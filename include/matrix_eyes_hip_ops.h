@@ -6,6 +6,14 @@
  * the dominant kernel against its roofline.  All pointers are DEVICE pointers; 16-bit operands
  * are in the context's dtype (ME_DTYPE_F16 / ME_DTYPE_BF16); work is enqueued on the context's
  * stream and not synchronised.
+ *
+ * The extents contract (tests/test_gpu_redzone.py holds every entry below to it, each pointer between guard regions of
+ * NaN and of zero): no entry's result depends on bytes outside the extents its comment gives for an operand -- a kernel
+ * may clamp, mask or over-read inside its tile, but what it reads out there must not reach an output; no entry writes
+ * outside the extents of its outputs; and the elements an output's comment documents as not written (the border of a
+ * zero-bordered map, the cls rows of me_op_patch_embed, rows of no window in the _segments entries, the foreign
+ * channels of a pixel_stride slice, the first header_bytes of me_op_ply_pack, the scale bytes of the rows behind the
+ * last one in an activation-layout scale tile) are not touched.
  */
 #ifndef MATRIX_EYES_HIP_OPS_H
 #define MATRIX_EYES_HIP_OPS_H
@@ -57,7 +65,8 @@ int32_t me_op_head_final(me_ctx* ctx, const void* in16b, int32_t B, int32_t H, i
                          int32_t Cmid, const float* bias, const float* w2, const float* b2, const float* f_norm,
                          float clamp_lo, float clamp_hi, float* out32, int32_t tile_cfg);
 /* ConvTranspose2d(2,2,stride 2): in16 NHWC [B*H*W][Cin]; w16 packed [(dy*2+dx)*Cout + co][Cin];
-   out32 [B][2H][2W][Cout] and/or out16 (zero-bordered when border16). */
+   out32 [B][2H][2W][Cout] and/or out16 (zero-bordered when border16).  Cout: any multiple of 4 (every store is four
+   channels of one sub-pixel; ME_ERR_BAD_SHAPE otherwise). */
 int32_t me_op_conv_transpose2x2(me_ctx* ctx, const void* in16, int32_t B, int32_t H, int32_t W,
                                 int32_t Cin, const void* w16, int32_t Cout, const float* bias,
                                 float* out32, void* out16, int32_t border16, int32_t tile_cfg);

@@ -1025,7 +1025,9 @@ static void conv_transpose2x2_forms(me_ctx* ctx, const void* in16, int32_t B, in
                                     float* out32, void* out16, int32_t border16, int32_t act16,
                                     int32_t out_split, int32_t pixel_stride, int32_t lo_off, int32_t tile_cfg) {
     ME_CHECK(in16 && w16 && (out32 || out16), ME_ERR_BAD_ARG, "me_op_conv_transpose2x2_forms: null pointer");
-    ME_CHECK(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cout % 8 == 0, ME_ERR_BAD_SHAPE,
+    // (Cout = 8 k + 4 runs: the epilogue's run-time mode splits the granules that straddle a sub-pixel; pixel_stride and lo_off
+    // stay multiples of 8, so a split output of such a Cout takes both explicitly)
+    ME_CHECK(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cout % 4 == 0, ME_ERR_BAD_SHAPE,
              "me_op_conv_transpose2x2_forms: %d x %d x %d, %d -> %d", B, H, W, Cin, Cout);
     ME_CHECK(act16 == ME_ACT_NONE || act16 == ME_ACT_RELU, ME_ERR_BAD_ARG, "me_op_conv_transpose2x2_forms: act16=%d", act16);
     ME_CHECK((!out_split && !pixel_stride && !lo_off) || out16, ME_ERR_BAD_ARG,

@@ -244,6 +244,15 @@ void gemm_launch(const GemmParams& p_in, AMode amode, EpiKind epi, int32_t dtype
                  ME_ERR_BAD_SHAPE, "gemm: chained operand set K=%d lda=%lld a_wrap=%d", p.K2, (long long)p.lda2, p.a_wrap2);
         p.queue = nullptr;  // (static tile order: a pass is not a tile the queue could hand out)
     }
+    // The ConvTranspose epilogue places an 8-column granule by the sub-pixel and channel of its first column (gemm_core.h EpiLane
+    // q / co).  With Cout = 8 k + 4 every other sub-pixel boundary falls inside a granule: the run-time epilogue mode places such a
+    // granule's halves separately (tests/test_gpu_redzone.py found the unsplit granule: bias read from behind the vector, four
+    // channels in the neighbouring pixel, the sub-pixel's first four never written).  The chained launch has compiled-in modes
+    // only and keeps whole granules; a half-granule (four columns, the unit of every store here) may not straddle anything.
+    if (epi == EPI_CONVT) {
+        ME_CHECK(p.Cout > 0 && p.Cout % 4 == 0, ME_ERR_BAD_SHAPE, "convt: Cout=%d is not a multiple of 4", p.Cout);
+        ME_CHECK(!p.A2 || p.Cout % 8 == 0, ME_ERR_BAD_SHAPE, "convt: a chained launch takes Cout in multiples of 8, not %d", p.Cout);
+    }
     if (epi == EPI_HEAD_FINAL) ME_CHECK(p.N <= 32, ME_ERR_BAD_SHAPE, "head: N=%d > 32", p.N);
     if (p.tap_bias)  // the epilogue needs the output pixel's coordinates: the bordered 16-bit output has them
         ME_CHECK(amode == A_CONV && epi == EPI_STORE && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.out16 && p.out16_border && p.bias &&

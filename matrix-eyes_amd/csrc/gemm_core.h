@@ -524,13 +524,27 @@ __device__ __forceinline__ void epilogue_granule(const GemmParams& p, const EpiR
         const bool w16 = MODE == 0 ? p.out16 != nullptr : (MODE == 4 || MODE == 6 || MODE == 7 || MODE == 8);
         const bool relu = (MODE == 0 || MODE == 8) ? p.act == ACT_RELU : false;
         const bool lo = MODE == 0 ? p.lo_off16 != 0 : MODE == 7;
+        // Cout = 8 k + 4 (MODE 0 only: the dispatch sends such a launch here): the granule whose first half ends sub-pixel q has
+        // its second half in channels 0 .. 3 of sub-pixel q + 1 -- another output pixel, placed on its own (its bias half was
+        // loaded from bias[0 .. 3]: the per-lane constants).  Behind a wave-uniform test, so that a Cout of 8 k skips it.
+        bool straddle = false;
+        int add32b = 0, add16b = 0;
+        if constexpr (MODE == 0) {
+            if ((p.Cout & 7) != 0 && hi_ok && lc.co + 4 == p.Cout) {
+                const int q1 = lc.q + 1;
+                const int ld16 = (int)(p.ldc16 ? p.ldc16 : p.ldc), w16px = 2 * p.out_W + (p.out16_border ? 2 : 0);
+                straddle = true;
+                add32b = ((q1 >> 1) * 2 * p.out_W + (q1 & 1)) * p.ldc;
+                add16b = ((q1 >> 1) * w16px + (q1 & 1)) * ld16;
+            }
+        }
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             if (h == 1 && !hi_ok) break;
             const float x0 = v[h][0] + lc.bias[h].x, x1 = v[h][1] + lc.bias[h].y;
             const float x2 = v[h][2] + lc.bias[h].z, x3 = v[h][3] + lc.bias[h].w;
             if (w32) {
-                const int64_t o = r.o32 + lc.add32 + 4 * h;
+                const int64_t o = r.o32 + (h == 1 && straddle ? add32b : lc.add32 + 4 * h);
                 *reinterpret_cast<float4*>(p.out32 + o) = make_float4(x0, x1, x2, x3);
             }
             a[4 * h] = relu ? fmaxf(x0, 0.f) : x0, a[4 * h + 1] = relu ? fmaxf(x1, 0.f) : x1;
@@ -539,8 +553,19 @@ __device__ __forceinline__ void epilogue_granule(const GemmParams& p, const EpiR
         if (w16) {
             const int64_t o = r.o16 + lc.add16;
             track_amax16<T>(amax16, a, hi_ok);
-            store_16bit<T>((T*)p.out16 + o, a, hi_ok);
-            if (lo) store_16bit_lo<T>((T*)p.out16 + o + p.lo_off16, a, hi_ok);
+            if (straddle) {  // two half-granule stores
+                const float a2[8] = {a[4], a[5], a[6], a[7], 0.f, 0.f, 0.f, 0.f};
+                const int64_t o2 = r.o16 + add16b;
+                store_16bit<T>((T*)p.out16 + o, a, false);
+                store_16bit<T>((T*)p.out16 + o2, a2, false);
+                if (lo) {
+                    store_16bit_lo<T>((T*)p.out16 + o + p.lo_off16, a, false);
+                    store_16bit_lo<T>((T*)p.out16 + o2 + p.lo_off16, a2, false);
+                }
+            } else {
+                store_16bit<T>((T*)p.out16 + o, a, hi_ok);
+                if (lo) store_16bit_lo<T>((T*)p.out16 + o + p.lo_off16, a, hi_ok);
+            }
         }
     }
 }
@@ -695,7 +720,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
             const float* bias = CHAIN_PART >= 0 ? (CHAIN_PART == 1 ? p.bias2 : nullptr) : (seg == 0 ? p.bias : (seg == 1 ? p.bias_s1 : p.bias_s2));
             if (bias) {
                 lc.bias[0] = *reinterpret_cast<const float4*>(bias + lc.co);
-                if (hi_ok) lc.bias[1] = *reinterpret_cast<const float4*>(bias + lc.co + 4);
+                // (EPI_CONVT with Cout = 8 k + 4: the second half of a granule that ends a sub-pixel is channels 0 .. 3 of the next)
+                const int co_hi = EPI == EPI_CONVT && lc.co + 4 == p.Cout ? 0 : lc.co + 4;
+                if (hi_ok) lc.bias[1] = *reinterpret_cast<const float4*>(bias + co_hi);
             }
             if constexpr (EPI == EPI_STORE) {
                 // GemmParams::qcols (the qkv linear): this wave's columns are Q columns -- wave-uniform, qcols being a
@@ -1023,7 +1050,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
         } else if constexpr (EPI == EPI_CONVT && CHAIN_PART == 1) {
             run(std::integral_constant<int, 5>());
         } else if constexpr (EPI == EPI_CONVT) {
-            const bool plain = p.act == ACT_NONE;
+            const bool plain = p.act == ACT_NONE && (p.Cout & 7) == 0;  // (Cout = 8 k + 4: granules straddle sub-pixels, mode 0 splits them)
             if (plain && p.out16 && !p.out32 && !p.lo_off16)
                 run(std::integral_constant<int, 4>());
             else if (plain && p.out32 && !p.out16)
