@@ -130,7 +130,17 @@ void me_ctx_destroy(me_ctx* ctx);
 const char* me_last_error(const me_ctx* ctx);
 int32_t me_ctx_set_progress(me_ctx* ctx, me_progress_fn fn, void* user);
 /* Run on a caller-owned hipStream_t (e.g. the framework's current stream) instead of the
-   context's own; NULL restores the own stream. */
+   context's own; NULL restores the own stream.  The ordering contract (DESIGN.md "Stream order"):
+   every launch, copy and memset of a call with DEVICE pointers is queued on that stream, or on a
+   stream of the context forked behind it and joined in front of the call's last launches, so the
+   call reads what the caller queued on the stream before it and whatever the caller queues on the
+   stream behind it sees its results -- no host wait on either side, eagerly, while the step is
+   captured and when it is replayed.  (The first call of a shape allocates its workspaces and waits
+   for the stream; later ones do not.)  The call itself waits for the work queued on the stream it
+   leaves, and a captured step is dropped: the next call is eager again.  NULL cannot name the
+   legacy default stream (handle 0, what a framework calls its default stream): pass a stream the
+   caller created.  The caller keeps the stream alive until another one is set or the context is
+   destroyed. */
 int32_t me_ctx_set_stream(me_ctx* ctx, void* hip_stream);
 int32_t me_ctx_synchronize(me_ctx* ctx);
 /* Status bits raised by the kernels since the last call (ME_STATUS_*), read and cleared; synchronises the stream.
@@ -573,7 +583,14 @@ int32_t me_ctx_set_write_behind(me_ctx* ctx, int32_t files_in_flight);
    therefore queue image i + 1's me_extract_depth first and then make image i's output calls: the GPU works on the next
    depth map while the host waits for this image's mesh counts, OBJ text and its copy to the host.  The next
    me_extract_depth that writes a buffer waits (on the GPU) for the output calls still reading it.  me_ctx_synchronize
-   and me_output_flush wait for both streams.  Results are unchanged.  0 (the default): one stream, the reference's order. */
+   and me_output_flush wait for both streams.  Results are unchanged.  0 (the default): one stream, the reference's order.
+   The ordering contract with on = 1 (also on a caller's stream, me_ctx_set_stream): an output call reads its inputs
+   behind the step that wrote the depth buffer or, for a buffer no step of this context wrote, behind everything queued
+   on the context's stream when the call is made, and output calls follow one another; but what they WRITE to device
+   memory (me_depth_clamp_minmax_async's range, a device rgb / stereogram) is written on the second stream, which the
+   context's stream is NOT ordered behind: work the caller queues behind the call does not see it.  The caller reads such
+   a result after me_ctx_synchronize or me_output_flush, and only a later output call of this context may consume it
+   without that wait.  With on = 0 the results are ordered on the context's stream like any other call's. */
 int32_t me_ctx_set_output_overlap(me_ctx* ctx, int32_t on);
 int32_t me_output_flush(me_ctx* ctx);
 

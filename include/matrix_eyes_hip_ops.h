@@ -263,6 +263,12 @@ int32_t me_op_cast_to32(me_ctx* ctx, const void* src16, float* dst, int64_t coun
    {"kernel", "launches", "total_ms", "flops", "bytes"} (algorithmic work, summed over launches). */
 int32_t me_profile_enable(me_ctx* ctx, int32_t on);
 int32_t me_profile_report(me_ctx* ctx, char* json, int64_t capacity);
+/* Read-only, a diagnostic counter in the manner of matrix_eyes_hip.h's me_graph_launch_count (kept in this header: the
+   integration binding does not need it): how many me_extract_depth[_u8] steps this context has enqueued -- eagerly or
+   into a capture -- with the side branch forked (ME_OVERLAP_TAIL=1, csrc/api.hip extract_depth_impl: decoder levels 4 - 2
+   and the FOV tail on a second stream, joined in front of level 1).  A replay of a captured step enqueues nothing and
+   does not count; 0 for ever when the switch is unset, a progress callback is installed or me_profile_enable is on. */
+int64_t me_side_branch_count(const me_ctx* ctx);
 /* The per-axis table of image 0.25.10 imageops/sample.rs (vertical_sample / horizontal_sample with the Lanczos3
    kernel) that me_resize_lanczos3_rgb8 runs on: for each output index o of an axis resampled from len_in to len_out
    samples, left[o], count[o] and, packed one index after the other in `weights`, its count[o] normalised weights

@@ -180,6 +180,7 @@ SIGNATURES = {
     "me_op_cast_to16": (_i32, [_vp, _vp, _vp, _i64]),
     "me_op_cast_to32": (_i32, [_vp, _vp, _vp, _i64]),
     "me_profile_enable": (_i32, [_vp, _i32]),
+    "me_side_branch_count": (_i64, [_vp]),
     "me_profile_report": (_i32, [_vp, C.c_char_p, _i64]),
     "me_op_lanczos3_table": (_i64, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32), _i64]),
     "me_op_jpeg_decode_host": (_i32, [_vp, _i64, _vp, _i32, _i32]),

@@ -686,6 +686,7 @@ void extract_depth_impl(me_ctx* ctx, const float* img_dev, int32_t batch, const 
         stage_encoder_latents(ctx, batch);
         ctx->grid_cap = 0;
         ME_HIP(hipStreamWaitEvent(main_stream, ctx->ev_join, 0));
+        ++ctx->side_branch_steps;
         stage_decoder_levels(ctx, batch, false, 1, 0);
     } else {
         {
@@ -882,6 +883,7 @@ int32_t me_ctx_set_graph(me_ctx* ctx, int32_t on) {
     ME_API_END(ctx)
 }
 int64_t me_graph_launch_count(const me_ctx* ctx) { return ctx ? ctx->graph_launches : 0; }
+int64_t me_side_branch_count(const me_ctx* ctx) { return ctx ? ctx->side_branch_steps : 0; }
 
 // ---- kernel-level surface (matrix_eyes_hip_ops.h) -------------------------------------------
 static unsigned long long* g_stamps = nullptr;  // diagnostic builds (-DME_GEMM_STAMPS) only

@@ -414,6 +414,8 @@ struct me_ctx {
     int32_t stereo_noise_path = 0;
     int64_t stereo_noise_words = 0;
     me::LegMarks stereo_noise_marks;
+    // steps enqueued (eagerly or into a capture) with the side branch forked (me_side_branch_count); a replay enqueues nothing
+    int64_t side_branch_steps = 0;
 
     // geometry helpers
     int g() const { return cfg.grid; }

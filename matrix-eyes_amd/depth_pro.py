@@ -307,7 +307,14 @@ class Context:
         """extract_depth calls replayed from the captured hipGraph so far (matrix_eyes_hip.h)."""
         return int(self.lib.me_graph_launch_count(self._h))
 
+    @property
+    def side_branch_count(self) -> int:
+        """extract_depth steps enqueued with the side branch forked (matrix_eyes_hip_ops.h me_side_branch_count)."""
+        return int(self.lib.me_side_branch_count(self._h))
+
     def set_stream(self, hip_stream: Optional[int]):
+        """Run on a caller-owned stream (its handle, e.g. torch.cuda.Stream().cuda_stream); None: the context's own.
+        Handle 0, the legacy default stream, cannot be named (matrix_eyes_hip.h me_ctx_set_stream)."""
         self._check(self.lib.me_ctx_set_stream(self._h, C.c_void_p(hip_stream or 0)))
 
     def set_progress(self, fn):

@@ -140,6 +140,7 @@ def test_captured_graph_replays_the_eager_step(dtype):
     out = torch.empty(2, S, S, dtype=torch.float32, device="cuda")
     for f_norm in (None, torch.tensor([0.8, 1.3], device="cuda")):
         rgb.copy_(structured)
+        torch.cuda.synchronize()                             # torch's copy is on torch's stream, the step on the context's
         n0 = ctx.graph_launch_count
         ctx.extract_depth(rgb, f_norm, out=out)              # first sight of this call: eager
         ctx.synchronize()
@@ -147,11 +148,13 @@ def test_captured_graph_replays_the_eager_step(dtype):
         assert ctx.graph_launch_count == n0
         for i in range(3):                                   # captured and launched, then replayed
             out.zero_()
+            torch.cuda.synchronize()
             ctx.extract_depth(rgb, f_norm, out=out)
             ctx.synchronize()
             assert ctx.graph_launch_count == n0 + i + 1
             assert torch.equal(out, eager)
         rgb.copy_(noise)                                     # same pointers, new pixels: the graph reads them
+        torch.cuda.synchronize()
         ctx.extract_depth(rgb, f_norm, out=out)
         ctx.synchronize()
         assert ctx.graph_launch_count == n0 + 4 and not torch.equal(out, eager)
@@ -165,6 +168,7 @@ def test_captured_graph_replays_the_eager_step(dtype):
         ctx.extract_depth(rgb, f_norm, out=out)
         n1 = ctx.graph_launch_count
         out.zero_()
+        torch.cuda.synchronize()
         ctx.extract_depth(rgb, f_norm, out=out)              # replay, in flight ...
         third = torch.empty_like(out)
         ctx.extract_depth(rgb, f_norm, out=third)            # ... when the new pointer drops its exec
