@@ -214,7 +214,7 @@ int32_t me_op_linear_fp8_residual_layernorm(me_ctx* ctx, int32_t M, int32_t N, i
 int32_t me_op_attention_fp8(me_ctx* ctx, const void* qkv16, uint8_t* out8, uint8_t* out8_scale, int32_t windows,
                             int32_t tokens, int32_t heads);
 /* me_op_attention (prescaled = 0) / me_op_attention_prescaled (1) over the row space of the encoder's merged ViT launches
-   (pipeline.hip MergedVit, common.h RowSegs): qkv16 [rows_total][3*heads*64]; windows are `tokens` rows apart INSIDE a
+   (pipeline.hip MergedVit, gemm_params.h RowSegs): qkv16 [rows_total][3*heads*64]; windows are `tokens` rows apart INSIDE a
    segment -- windows [0, win0) start at row 0, [win0, win0 + win1) at seg1, the rest at seg2 (seg2 == 0: two segments, and
    windows == win0 + win1; seg1 == 0: none, the windows back to back from row 0).  ONE of out16 [rows_total][heads*64] and
    out8 [rows_total][heads*64] e4m3 bytes + out8_scale, one e8m0 byte per 32 columns in the activation layout with

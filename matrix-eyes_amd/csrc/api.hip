@@ -9,10 +9,15 @@
 #include <exception>
 
 #include "../../include/matrix_eyes_hip_ops.h"
-#include "gemm_params.h"
+#include "model.h"
+
+#include "admission.h"
 #include "mx_fp8.h"
 
 using namespace me;
+
+// (admission.h states the act rules of the entries in Act: the ABI's values are the same)
+static_assert((int)ME_ACT_NONE == ACT_NONE && (int)ME_ACT_GELU == ACT_GELU && (int)ME_ACT_RELU == ACT_RELU, "ME_ACT_* are Act");
 
 namespace {
 
@@ -961,8 +966,7 @@ int32_t me_op_conv2d(me_ctx* ctx, const void* in16b, int32_t B, int32_t H, int32
                      const float* res32, const float* res32b, float* out32, void* out16,
                      int32_t border16, int32_t act, int32_t act_both, int32_t tile_cfg) {
     ME_API_BEGIN(ctx)
-    ME_CHECK((k == 1 || k == 3) && (stride == 1 || stride == 2), ME_ERR_BAD_SHAPE,
-             "me_op_conv2d: k=%d stride=%d", k, stride);
+    admit_op_conv2d(k, stride);
     conv2d_launch(ctx, in16b, B, H, W, Cin, w16, Cout, k, stride, bias, res32, res32b, out32, out16, border16, 1, act, act_both, tile_cfg);
     ME_API_END(ctx)
 }
@@ -972,8 +976,7 @@ int32_t me_op_head_final(me_ctx* ctx, const void* in16b, int32_t B, int32_t H, i
                          float clamp_lo, float clamp_hi, float* out32, int32_t tile_cfg) {
     ME_API_BEGIN(ctx)
     ME_CHECK(in16b && w16 && bias && w2 && b2 && out32, ME_ERR_BAD_ARG, "me_op_head_final: null pointer");
-    ME_CHECK(B > 0 && H > 0 && W > 0 && Cin % 64 == 0 && Cmid > 0 && Cmid <= 32 && Cmid % 4 == 0, ME_ERR_BAD_SHAPE,
-             "me_op_head_final: %d x %d x %d, %d -> %d", B, H, W, Cin, Cmid);
+    admit_op_head_final(B, H, W, Cin, Cmid);
     gemm_launch(head_final_params(in16b, B, H, W, Cin, w16, Cmid, bias, w2, b2, f_norm, clamp_lo, clamp_hi, out32), A_CONV, EPI_HEAD_FINAL,
                 ctx->dtype, ctx->stream, tile_cfg);
     ME_API_END(ctx)
@@ -995,12 +998,7 @@ int32_t me_op_conv2d_forms(me_ctx* ctx, const void* in16b, int32_t B, int32_t H,
                            int32_t border16, int32_t out16_parts, int32_t act, int32_t act_both, int32_t tile_cfg) {
     ME_API_BEGIN(ctx)
     ME_CHECK(in16b && w16 && (out32 || out16), ME_ERR_BAD_ARG, "me_op_conv2d_forms: null pointer");
-    ME_CHECK((k == 1 || k == 3) && (stride == 1 || stride == 2) && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 &&
-                 H % stride == 0 && W % stride == 0,
-             ME_ERR_BAD_SHAPE, "me_op_conv2d_forms: %d x %d x %d, %d -> %d, k=%d stride=%d", B, H, W, Cin, Cout, k, stride);
-    ME_CHECK(out16_parts >= 1 && out16_parts <= 3 && (out16_parts == 1 || out16), ME_ERR_BAD_ARG,
-             "me_op_conv2d_forms: out16_parts=%d", out16_parts);
-    ME_CHECK(act == ME_ACT_NONE || act == ME_ACT_RELU, ME_ERR_BAD_ARG, "me_op_conv2d_forms: act=%d", act);
+    admit_op_conv2d_forms(B, H, W, Cin, Cout, k, stride, out16, out16_parts, act);
     conv2d_launch(ctx, in16b, B, H, W, Cin, w16, Cout, k, stride, bias, res32, res32b, out32, out16, border16, out16_parts, act, act_both,
                   tile_cfg);
     ME_API_END(ctx)
@@ -1016,30 +1014,12 @@ int32_t me_op_linear_split(me_ctx* ctx, int32_t M, int32_t N, int32_t K, const v
     ME_API_END(ctx)
 }
 
-// a_wrap > 0: the operand rows are stored a_wrap channels wide and channels a_wrap .. Cin - 1 are read from the row's start
-static void check_a_wrap(const char* who, int32_t Cin, int32_t a_wrap) {
-    ME_CHECK(a_wrap >= 0 && a_wrap % 64 == 0 && (a_wrap == 0 || (a_wrap < Cin && Cin - a_wrap <= a_wrap)), ME_ERR_BAD_SHAPE,
-             "%s: a_wrap=%d of %d channels", who, a_wrap, Cin);
-}
-
 static void conv_transpose2x2_forms(me_ctx* ctx, const void* in16, int32_t B, int32_t H, int32_t W,
                                     int32_t Cin, int32_t a_wrap, const void* w16, int32_t Cout, const float* bias,
                                     float* out32, void* out16, int32_t border16, int32_t act16,
                                     int32_t out_split, int32_t pixel_stride, int32_t lo_off, int32_t tile_cfg) {
     ME_CHECK(in16 && w16 && (out32 || out16), ME_ERR_BAD_ARG, "me_op_conv_transpose2x2_forms: null pointer");
-    // (Cout = 8 k + 4 runs: the epilogue's run-time mode splits the granules that straddle a sub-pixel; pixel_stride and lo_off
-    // stay multiples of 8, so a split output of such a Cout takes both explicitly)
-    ME_CHECK(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cout % 4 == 0, ME_ERR_BAD_SHAPE,
-             "me_op_conv_transpose2x2_forms: %d x %d x %d, %d -> %d", B, H, W, Cin, Cout);
-    ME_CHECK(act16 == ME_ACT_NONE || act16 == ME_ACT_RELU, ME_ERR_BAD_ARG, "me_op_conv_transpose2x2_forms: act16=%d", act16);
-    ME_CHECK((!out_split && !pixel_stride && !lo_off) || out16, ME_ERR_BAD_ARG,
-             "me_op_conv_transpose2x2_forms: a 16-bit layout without a 16-bit output");
-    ME_CHECK(out_split || !lo_off, ME_ERR_BAD_ARG, "me_op_conv_transpose2x2_forms: lo_off without out_split");
-    const int lo = out_split ? (lo_off ? lo_off : Cout) : 0;
-    ME_CHECK(pixel_stride >= 0 && pixel_stride % 8 == 0 && lo % 8 == 0 && (!out_split || lo >= Cout) &&
-                 (!pixel_stride || pixel_stride >= lo + Cout),
-             ME_ERR_BAD_SHAPE, "me_op_conv_transpose2x2_forms: pixel_stride=%d lo_off=%d for %d channels", pixel_stride, lo_off, Cout);
-    check_a_wrap("me_op_conv_transpose2x2_forms_wrap", Cin, a_wrap);
+    admit_op_conv_transpose2x2_forms(B, H, W, Cin, a_wrap, Cout, out16, act16, out_split, pixel_stride, lo_off);
     GemmParams p = convt_params(in16, B, H, W, Cin, w16, Cout, bias, out32, out16, border16 != 0, pixel_stride, act16, false, out_split != 0,
                                 lo_off);
     if (a_wrap) set_a_wrap(p, a_wrap);
@@ -1071,11 +1051,7 @@ int32_t me_op_conv_transpose2x2_pair(me_ctx* ctx, int32_t B, int32_t H, int32_t 
                                      int32_t tile_cfg) {
     ME_API_BEGIN(ctx)
     ME_CHECK(in16_a && w16_a && in16_b && w16_b && out32 && out16, ME_ERR_BAD_ARG, "me_op_conv_transpose2x2_pair: null pointer");
-    ME_CHECK(B > 0 && H > 0 && W > 0 && Cin_a > 0 && Cin_b > 0 && Cout > 0 && Cout % 8 == 0, ME_ERR_BAD_SHAPE,
-             "me_op_conv_transpose2x2_pair: %d x %d x %d, %d + %d -> %d", B, H, W, Cin_a, Cin_b, Cout);
-    ME_CHECK(act16 == ME_ACT_NONE || act16 == ME_ACT_RELU, ME_ERR_BAD_ARG, "me_op_conv_transpose2x2_pair: act16=%d", act16);
-    ME_CHECK(grid_cap >= 0, ME_ERR_BAD_ARG, "me_op_conv_transpose2x2_pair: grid_cap=%d", grid_cap);
-    check_a_wrap("me_op_conv_transpose2x2_pair", Cin_b, a_wrap_b);
+    admit_op_conv_transpose2x2_pair(B, H, W, Cout, Cin_a, Cin_b, a_wrap_b, act16, grid_cap);
     const GemmParams first = convt_params(in16_a, B, H, W, Cin_a, w16_a, Cout, nullptr, nullptr, out16, border16 != 0, 0, act16);
     GemmParams second = convt_params(in16_b, B, H, W, Cin_b, w16_b, Cout, bias_b, nullptr, nullptr, false, 0, ACT_NONE);
     if (a_wrap_b) set_a_wrap(second, a_wrap_b);
@@ -1089,30 +1065,19 @@ int32_t me_op_patch_embed(me_ctx* ctx, const void* patches16, int32_t windows, i
                           const float* bias, const float* pos, float* tokens32, int32_t tile_cfg) {
     ME_API_BEGIN(ctx)
     ME_CHECK(patches16 && W16 && bias && pos && tokens32, ME_ERR_BAD_ARG, "me_op_patch_embed: null pointer");
-    ME_CHECK(windows > 0 && P > 0 && C > 0 && (int64_t)windows * P < (1 << 30), ME_ERR_BAD_SHAPE,
-             "me_op_patch_embed: %d windows of %d patches, dim %d", windows, P, C);
+    admit_op_patch_embed(windows, P, C);
     gemm_launch(patch_embed_params(windows, P, C, patches16, W16, bias, pos, tokens32), A_PLAIN, EPI_PATCH_EMBED, ctx->dtype, ctx->stream,
                 tile_cfg);
     ME_API_END(ctx)
 }
 
-// ---- the layout / element-wise kernels (elementwise.hip), arguments checked here: the launch helpers trust the pipeline ----
-namespace {
-void check_grid(const char* who, int32_t grid) {
-    ME_CHECK(grid >= 8 && grid <= 64 && grid % 8 == 0, ME_ERR_BAD_SHAPE, "%s: grid %d is not a multiple of 8 in [8, 64]", who, grid);
-}
-void check_map(const char* who, int32_t batch, int32_t H, int32_t W, int32_t C) {
-    ME_CHECK(batch > 0 && batch <= 65535 && H > 0 && W > 0 && C > 0 && (int64_t)H * W < (1ll << 31) && (int64_t)C <= 65535 * 32ll,
-             ME_ERR_BAD_SHAPE, "%s: %d x %d x %d x %d", who, batch, H, W, C);
-}
-}  // namespace
-
+// ---- the layout / element-wise kernels (elementwise.hip): the launch helpers trust the pipeline, so an entry checks its pointers
+// here and its shapes in admission.h (admit_grid, admit_map, admit_op_*) ----
 int32_t me_op_bilinear(me_ctx* ctx, const float* src32, void* dst16, int32_t planes, int32_t in_size, int32_t out_size,
                        int32_t align_corners) {
     ME_API_BEGIN(ctx)
     ME_CHECK(src32 && dst16, ME_ERR_BAD_ARG, "me_op_bilinear: null pointer");
-    ME_CHECK(planes > 0 && in_size > 0 && out_size > 0 && in_size <= 32768 && out_size <= 32768, ME_ERR_BAD_SHAPE,
-             "me_op_bilinear: %d planes, %d -> %d", planes, in_size, out_size);
+    admit_op_bilinear(planes, in_size, out_size);
     bilinear_launch(src32, dst16, planes, in_size, out_size, align_corners ? 1 : 0, ctx->dtype, ctx->stream);
     ME_API_END(ctx)
 }
@@ -1121,8 +1086,7 @@ int32_t me_op_patchify(me_ctx* ctx, const void* x0, const void* x1, const void* 
                        int32_t grid) {
     ME_API_BEGIN(ctx)
     ME_CHECK(x0 && x1 && x2 && patches, ME_ERR_BAD_ARG, "me_op_patchify: null pointer");
-    check_grid("me_op_patchify", grid);
-    ME_CHECK(batch > 0 && batch <= 1024, ME_ERR_BAD_SHAPE, "me_op_patchify: batch %d", batch);
+    admit_op_patchify(batch, grid);
     patchify_launch(x0, x1, x2, patches, batch, grid, ctx->dtype, ctx->stream);
     ME_API_END(ctx)
 }
@@ -1130,8 +1094,7 @@ int32_t me_op_patchify(me_ctx* ctx, const void* x0, const void* x1, const void* 
 int32_t me_op_patchify_windows(me_ctx* ctx, const void* xs16, void* patches, int32_t windows, int32_t grid) {
     ME_API_BEGIN(ctx)
     ME_CHECK(xs16 && patches, ME_ERR_BAD_ARG, "me_op_patchify_windows: null pointer");
-    check_grid("me_op_patchify_windows", grid);
-    ME_CHECK(windows > 0 && windows <= 35 * 1024, ME_ERR_BAD_SHAPE, "me_op_patchify_windows: %d windows", windows);
+    admit_op_patchify_windows(windows, grid);
     patchify_windows_launch(xs16, patches, windows, grid, ctx->dtype, ctx->stream);
     ME_API_END(ctx)
 }
@@ -1140,7 +1103,7 @@ int32_t me_op_cls_rows(me_ctx* ctx, float* tokens, const float* cls, const float
                        int32_t dim) {
     ME_API_BEGIN(ctx)
     ME_CHECK(tokens && cls && pos, ME_ERR_BAD_ARG, "me_op_cls_rows: null pointer");
-    ME_CHECK(windows > 0 && tpw > 0 && dim > 0, ME_ERR_BAD_SHAPE, "me_op_cls_rows: %d windows of %d tokens, dim %d", windows, tpw, dim);
+    admit_op_cls_rows(windows, tpw, dim);
     cls_rows_launch(tokens, cls, pos, windows, tpw, dim, ctx->stream);
     ME_API_END(ctx)
 }
@@ -1149,11 +1112,7 @@ int32_t me_op_merge(me_ctx* ctx, const float* src32, const void* src16, void* ds
                     int32_t win0, int32_t steps, int32_t padding, int32_t grid, int32_t dim, int32_t split) {
     ME_API_BEGIN(ctx)
     ME_CHECK(dst16, ME_ERR_BAD_ARG, "me_op_merge: null pointer");
-    check_grid("me_op_merge", grid);
-    ME_CHECK(batch > 0 && dim > 0 && steps >= 1 && steps <= 5 && padding >= 0 && 2 * padding < grid && (steps > 1 || padding == 0) &&
-                 win0 >= 0 && wpi > 0 && win0 + steps * steps <= wpi,
-             ME_ERR_BAD_SHAPE, "me_op_merge: batch %d, windows %d + %d x %d of %d, padding %d, dim %d", batch, win0, steps, steps, wpi,
-             padding, dim);
+    admit_op_merge(batch, wpi, win0, steps, padding, grid, dim);
     merge_launch(src32, src16, dst16, batch, wpi, win0, steps, padding, grid, dim, ctx->dtype, ctx->stream, split ? 1 : 0);
     ME_API_END(ctx)
 }
@@ -1162,7 +1121,7 @@ int32_t me_op_nchw32_to_nhwc(me_ctx* ctx, const float* src, float* dst32, void* 
                              int32_t W, int32_t C, int32_t border, int32_t relu16, int32_t split) {
     ME_API_BEGIN(ctx)
     ME_CHECK(src && (dst32 || dst16) && (dst16 || (!border && !relu16 && !split)), ME_ERR_BAD_ARG, "me_op_nchw32_to_nhwc: null pointer");
-    check_map("me_op_nchw32_to_nhwc", batch, H, W, C);
+    admit_map("me_op_nchw32_to_nhwc", batch, H, W, C);
     nchw32_to_nhwc_launch(src, dst32, dst16, batch, H, W, C, border ? 1 : 0, relu16 ? 1 : 0, ctx->dtype, ctx->stream, split ? 1 : 0);
     ME_API_END(ctx)
 }
@@ -1171,7 +1130,7 @@ int32_t me_op_nhwc16_to_nchw32(me_ctx* ctx, const void* src16, float* dst, int32
                                int32_t C, int32_t border, int32_t split) {
     ME_API_BEGIN(ctx)
     ME_CHECK(src16 && dst, ME_ERR_BAD_ARG, "me_op_nhwc16_to_nchw32: null pointer");
-    check_map("me_op_nhwc16_to_nchw32", batch, H, W, C);
+    admit_map("me_op_nhwc16_to_nchw32", batch, H, W, C);
     nhwc16_to_nchw32_launch(src16, dst, batch, H, W, C, border ? 1 : 0, ctx->dtype, ctx->stream, split ? 1 : 0);
     ME_API_END(ctx)
 }
@@ -1180,7 +1139,7 @@ int32_t me_op_nhwc32_to_nchw32(me_ctx* ctx, const float* src, float* dst, int32_
                                int32_t C) {
     ME_API_BEGIN(ctx)
     ME_CHECK(src && dst, ME_ERR_BAD_ARG, "me_op_nhwc32_to_nchw32: null pointer");
-    check_map("me_op_nhwc32_to_nchw32", batch, H, W, C);
+    admit_map("me_op_nhwc32_to_nchw32", batch, H, W, C);
     nhwc32_to_nchw32_launch(src, dst, batch, H, W, C, ctx->stream);
     ME_API_END(ctx)
 }
@@ -1189,7 +1148,7 @@ int32_t me_op_nhwc32_to_16b(me_ctx* ctx, const float* src, void* dst16b, int32_t
                             int32_t C, int32_t relu) {
     ME_API_BEGIN(ctx)
     ME_CHECK(src && dst16b, ME_ERR_BAD_ARG, "me_op_nhwc32_to_16b: null pointer");
-    check_map("me_op_nhwc32_to_16b", batch, H, W, C);
+    admit_map("me_op_nhwc32_to_16b", batch, H, W, C);
     nhwc32_to_16b_launch(src, dst16b, batch, H, W, C, relu ? 1 : 0, ctx->dtype, ctx->stream);
     ME_API_END(ctx)
 }
@@ -1198,8 +1157,7 @@ int32_t me_op_concat_channels(me_ctx* ctx, const void* a16, const void* b16, voi
                               int32_t Cb) {
     ME_API_BEGIN(ctx)
     ME_CHECK(a16 && b16 && dst16, ME_ERR_BAD_ARG, "me_op_concat_channels: null pointer");
-    ME_CHECK(pixels > 0 && Ca > 0 && Cb > 0, ME_ERR_BAD_SHAPE, "me_op_concat_channels: %lld pixels of %d + %d channels",
-             (long long)pixels, Ca, Cb);
+    admit_op_concat_channels(pixels, Ca, Cb);
     concat_channels_launch(a16, b16, dst16, pixels, Ca, Cb, ctx->stream);
     ME_API_END(ctx)
 }
@@ -1208,9 +1166,7 @@ int32_t me_op_fov_add(me_ctx* ctx, const float* lin, const float* low, void* dst
                       int32_t C, int32_t tpw) {
     ME_API_BEGIN(ctx)
     ME_CHECK(lin && low && dst16b, ME_ERR_BAD_ARG, "me_op_fov_add: null pointer");
-    check_grid("me_op_fov_add", grid);
-    ME_CHECK(batch > 0 && C > 0 && tpw >= grid * grid + 1, ME_ERR_BAD_SHAPE, "me_op_fov_add: batch %d, %d channels, %d tokens per window",
-             batch, C, tpw);
+    admit_op_fov_add(batch, grid, C, tpw);
     fov_add_relu_launch(lin, low, dst16b, batch, grid, C, tpw, ctx->dtype, ctx->stream);
     ME_API_END(ctx)
 }
@@ -1219,8 +1175,7 @@ int32_t me_op_fov_final(me_ctx* ctx, const void* x16, const float* w, const floa
                         int32_t batch, int32_t k, int32_t C) {
     ME_API_BEGIN(ctx)
     ME_CHECK(x16 && w && bias && f_norm, ME_ERR_BAD_ARG, "me_op_fov_final: null pointer");
-    ME_CHECK(batch > 0 && k > 0 && C > 0 && (int64_t)k * k * C < (1ll << 31), ME_ERR_BAD_SHAPE, "me_op_fov_final: batch %d, %d x %d x %d",
-             batch, k, k, C);
+    admit_op_fov_final(batch, k, C);
     fov_final_launch(x16, w, bias, fov_deg, f_norm, batch, k, C, ctx->dtype, ctx->stream);
     ME_API_END(ctx)
 }
@@ -1296,10 +1251,7 @@ int32_t me_op_linear_fp8_residual_layernorm(me_ctx* ctx, int32_t M, int32_t N, i
     ME_API_BEGIN(ctx)
     ME_CHECK(A8 && a_scale && W8 && w_scale && bias && gamma && ln_w && ln_b && x32 && xn8 && xn_scale, ME_ERR_BAD_ARG,
              "me_op_linear_fp8_residual_layernorm: null pointer");
-    const int nseg = seg1 == 0 ? 1 : (seg2 == 0 ? 2 : 3);
-    for (int i = 0; i < nseg; ++i)
-        ME_CHECK(W8[i] && w_scale[i] && bias[i] && gamma[i] && ln_w[i] && ln_b[i], ME_ERR_BAD_ARG,
-                 "me_op_linear_fp8_residual_layernorm: row segment %d without weights", i);
+    admit_segment_weights("me_op_linear_fp8_residual_layernorm", seg1, seg2, W8, w_scale, bias, gamma, ln_w, ln_b);
     GemmParams p = linear_fp8_params(M, N, K, A8, a_scale, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, x32);
     set_segments(p, seg1, seg2, seg_weights(W8, w_scale, bias, gamma));
     set_fused_layernorm(ctx, p, "op.ln.stats", "op.ln.count." + std::to_string(N), LnSet{ln_w[0], ln_b[0], ln_w[1], ln_b[1], ln_w[2], ln_b[2]},
@@ -1313,13 +1265,7 @@ int32_t me_op_linear_segments(me_ctx* ctx, int32_t M, int32_t N, int32_t K, cons
                               void* out16, float* x32, int32_t act, int32_t tile_cfg) {
     ME_API_BEGIN(ctx)
     ME_CHECK(A16 && W16 && bias && (out16 || x32), ME_ERR_BAD_ARG, "me_op_linear_segments: null pointer");
-    ME_CHECK(W16[0] && (seg1 == 0 || W16[1]) && (seg2 == 0 || W16[2]), ME_ERR_BAD_ARG,
-             "me_op_linear_segments: a row segment without weights");
-    ME_CHECK(seg1 >= 0 && seg2 >= 0 && seg1 <= M && seg2 <= M && (seg2 == 0 || (seg1 > 0 && seg2 > seg1)), ME_ERR_BAD_ARG,
-             "me_op_linear_segments: segments %d / %d of %d rows", seg1, seg2, M);
-    if (x32)
-        ME_CHECK(gamma && gamma[0] && (seg1 == 0 || gamma[1]) && (seg2 == 0 || gamma[2]), ME_ERR_BAD_ARG,
-                 "me_op_linear_segments: the residual form takes gamma for every segment");
+    admit_op_linear_segments(M, seg1, seg2, W16, gamma, x32 != nullptr);
     GemmParams p = x32 ? resid_params(M, N, K, A16, nullptr, nullptr, nullptr, x32)
                        : linear_params(M, N, K, A16, nullptr, nullptr, out16, nullptr, act);
     set_segments(p, seg1, seg2, seg_weights(W16, nullptr, bias, x32 ? gamma : nullptr));
@@ -1328,7 +1274,7 @@ int32_t me_op_linear_segments(me_ctx* ctx, int32_t M, int32_t N, int32_t K, cons
 }
 
 // me_op_attention_segments and me_op_layernorm_segments: the row-segmented forms of the merged ViT launches (pipeline.hip
-// MergedVit, common.h RowSegs).  The kernels trust the row map, so a layout that does not fit its buffers is refused here.
+// MergedVit, gemm_params.h RowSegs).  The kernels trust the row map, so a layout that does not fit its buffers is refused (admission.h).
 int32_t me_op_attention_segments(me_ctx* ctx, const void* qkv16, void* out16, uint8_t* out8, uint8_t* out8_scale, int32_t windows,
                                  int32_t tokens, int32_t heads, int32_t prescaled, int64_t rows_total, int64_t seg1, int64_t seg2,
                                  int32_t win0, int32_t win1) {
@@ -1336,20 +1282,7 @@ int32_t me_op_attention_segments(me_ctx* ctx, const void* qkv16, void* out16, ui
     ME_CHECK(qkv16 && (out16 || out8), ME_ERR_BAD_ARG, "me_op_attention_segments: null pointer");
     ME_CHECK(!(out16 && out8), ME_ERR_BAD_ARG, "me_op_attention_segments: ONE of out16 and out8");
     ME_CHECK(!out8 || out8_scale, ME_ERR_BAD_ARG, "me_op_attention_segments: out8 without its scales");
-    ME_CHECK(!out8 || heads % 2 == 0, ME_ERR_BAD_ARG, "me_op_attention_segments: fp8 output with %d heads (an odd number)", heads);
-    ME_CHECK(windows > 0 && tokens > 0 && heads > 0 && rows_total > 0, ME_ERR_BAD_SHAPE,
-             "me_op_attention_segments: windows=%d tokens=%d heads=%d rows=%lld", windows, tokens, heads, (long long)rows_total);
-    ME_CHECK(seg1 >= 0 && seg2 >= 0 && win0 >= 0 && win1 >= 0 && seg1 <= rows_total && seg2 <= rows_total &&
-                 (seg2 == 0 || (seg1 > 0 && seg2 > seg1)),
-             ME_ERR_BAD_ARG, "me_op_attention_segments: segments %lld / %lld of %lld rows, %d / %d windows", (long long)seg1,
-             (long long)seg2, (long long)rows_total, win0, win1);
-    const int64_t T = tokens, last = (int64_t)windows - win0 - win1;  // windows of the last segment
-    bool fits;
-    if (seg1 == 0) fits = windows * T <= rows_total;
-    else if (seg2 == 0) fits = win0 * T <= seg1 && last == 0 && seg1 + win1 * T <= rows_total;
-    else fits = win0 * T <= seg1 && seg1 + win1 * T <= seg2 && last >= 0 && seg2 + last * T <= rows_total;
-    ME_CHECK(fits, ME_ERR_BAD_SHAPE, "me_op_attention_segments: %d windows of %d rows (%d / %d in the first segments) do not fit "
-             "segments %lld / %lld of %lld rows", windows, tokens, win0, win1, (long long)seg1, (long long)seg2, (long long)rows_total);
+    admit_op_attention_segments(out8, windows, tokens, heads, rows_total, seg1, seg2, win0, win1);
     RowSegs segs;
     segs.seg1 = seg1, segs.seg2 = seg2, segs.win0 = win0, segs.win1 = win1;
     attention_launch(qkv16, out16, windows, tokens, heads, ctx->dtype, ctx->stream, &segs, out8, out8_scale,
@@ -1364,14 +1297,8 @@ int32_t me_op_layernorm_segments(me_ctx* ctx, const float* x32, const float* con
     ME_CHECK(x32 && weight && bias && (y16 || y32 || y8), ME_ERR_BAD_ARG, "me_op_layernorm_segments: null pointer");
     ME_CHECK(!(y8 && (y16 || y32)), ME_ERR_BAD_ARG, "me_op_layernorm_segments: ONE of y16 / y32 and y8");
     ME_CHECK(!y8 || yscale, ME_ERR_BAD_ARG, "me_op_layernorm_segments: y8 without its scales");
-    ME_CHECK(rows > 0, ME_ERR_BAD_SHAPE, "me_op_layernorm_segments: %lld rows", (long long)rows);
-    ME_CHECK(seg1 >= 0 && seg2 >= 0 && seg1 <= rows && seg2 <= rows && (seg2 == 0 || (seg1 > 0 && seg2 > seg1)), ME_ERR_BAD_ARG,
-             "me_op_layernorm_segments: segments %lld / %lld of %lld rows", (long long)seg1, (long long)seg2, (long long)rows);
-    const int nseg = seg1 == 0 ? 1 : (seg2 == 0 ? 2 : 3);
-    for (int i = 0; i < nseg; ++i)
-        ME_CHECK(weight[i] && bias[i], ME_ERR_BAD_ARG, "me_op_layernorm_segments: row segment %d without weights", i);
-    const bool wide = dim == 256 || dim == 512 || dim == 1024;
-    ME_CHECK(wide || (!y8 && (dim == 64 || dim == 128)), ME_ERR_BAD_SHAPE, "me_op_layernorm_segments: dim %d", dim);
+    admit_op_layernorm_segments(weight, bias, seg1, seg2, y8, rows, dim);
+    const int nseg = row_segment_count(seg1, seg2);
     RowSegs segs;
     segs.seg1 = seg1, segs.seg2 = seg2;
     if (nseg > 1) segs.w1 = weight[1], segs.b1 = bias[1];
@@ -1388,12 +1315,7 @@ void linear_residual_layernorm_impl(me_ctx* ctx, const char* who, int32_t M, int
                                     const float* const ln_w[3], const float* const ln_b[3], float eps, float* x32, void* xn16,
                                     uint8_t* xn8, uint8_t* xn_scale) {
     ME_CHECK(A16 && W16 && bias && gamma && ln_w && ln_b && x32 && (xn16 || (xn8 && xn_scale)), ME_ERR_BAD_ARG, "%s: null pointer", who);
-    ME_CHECK(seg1 >= 0 && seg2 >= 0 && seg1 <= M && seg2 <= M && (seg2 == 0 || (seg1 > 0 && seg2 > seg1)), ME_ERR_BAD_ARG,
-             "%s: segments %d / %d of %d rows", who, seg1, seg2, M);
-    const int nseg = seg1 == 0 ? 1 : (seg2 == 0 ? 2 : 3);
-    for (int i = 0; i < nseg; ++i)
-        ME_CHECK(W16[i] && bias[i] && gamma[i] && ln_w[i] && ln_b[i], ME_ERR_BAD_ARG, "%s: row segment %d without weights", who, i);
-    ME_CHECK(N == 256 || N == 512 || N == 1024, ME_ERR_BAD_SHAPE, "%s: N = %d not in {256, 512, 1024}", who, N);
+    admit_op_linear_residual_layernorm(who, M, N, seg1, seg2, W16, bias, gamma, ln_w, ln_b);
     GemmParams p = resid_params(M, N, K, A16, nullptr, nullptr, nullptr, x32);
     set_segments(p, seg1, seg2, seg_weights(W16, nullptr, bias, gamma));
     // (an arrival counter advances by N / 256 per launch and must start a launch at a multiple of that: one per N)

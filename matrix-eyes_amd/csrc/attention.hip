@@ -22,6 +22,8 @@
 #include "common.h"
 #include "mx_fp8.h"
 
+#include "admission.h"
+
 namespace me {
 
 namespace {
@@ -1121,12 +1123,7 @@ void attention_launch(const void* qkv, void* out, int32_t windows, int32_t token
                       int32_t dtype, hipStream_t stream, const RowSegs* segs_opt, uint8_t* out8,
                       uint8_t* out8_scale, int64_t out8_mt, bool q_prescaled) {
     const RowSegs segs = segs_opt ? *segs_opt : RowSegs();
-    ME_CHECK(windows > 0 && tokens > 0 && heads > 0, ME_ERR_BAD_SHAPE,
-             "attention: windows=%d tokens=%d heads=%d", windows, tokens, heads);
-    ME_CHECK(!out8 || (out8_scale && out8_mt > 0 && heads % 2 == 0), ME_ERR_BAD_ARG,
-             "attention: fp8 output needs its scale buffer and K = 64 heads a multiple of 128");
-    ME_CHECK((int64_t)windows * heads * ((tokens + 127) / 128) < (1ll << 30), ME_ERR_BAD_SHAPE,
-             "attention: grid too large");
+    admit_attention(windows, tokens, heads, out8, out8_scale, out8_mt);
     const int nqb = (tokens + 127) / 128, ngroups = windows * heads;
     const dim3 grid(8 * nqb * ((ngroups + 7) / 8));
     // ME_ATT_V=3 (development, tools/attn_ab.py): round 5's re-cut (attention3.hip: 48 queries per wave on 16x16x32 MFMAs, three

@@ -8,6 +8,8 @@
 #include <vector>
 
 #include "../../include/matrix_eyes_hip.h"
+#include "error.h"        // Error, fail, ME_CHECK
+#include "gemm_params.h"  // Act, GemmParams, RowSegs and their builders: whatever a launch is described in
 #include "tile_choice.h"  // AMode, EpiKind, CFG_*, cdiv, seg_row_tiles: whatever a launch decision is stated in
 
 namespace me {
@@ -29,25 +31,12 @@ struct Status {
     std::string msg;
 };
 
-// Thrown inside the library, caught at the C ABI; nothing escapes to the caller.
-struct Error {
-    int32_t code;
-    std::string msg;
-};
-
-[[noreturn]] void fail(int32_t code, const char* fmt, ...);
-
 #define ME_HIP(expr)                                                                         \
     do {                                                                                     \
         hipError_t e__ = (expr);                                                             \
         if (e__ != hipSuccess)                                                               \
             ::me::fail(e__ == hipErrorOutOfMemory ? ME_ERR_OOM : ME_ERR_HIP, "%s: %s (%s:%d)", \
                        #expr, hipGetErrorString(e__), __FILE__, __LINE__);                   \
-    } while (0)
-
-#define ME_CHECK(cond, code, ...)                   \
-    do {                                            \
-        if (!(cond)) ::me::fail((code), __VA_ARGS__); \
     } while (0)
 
 // Environment knobs: a switch that is on unless NAME=0, one that is off unless NAME is a non-zero number, a
@@ -162,132 +151,8 @@ __device__ __forceinline__ void wait_vmcnt() {
 // W is always row-major [N][K], K contiguous (the PyTorch Linear layout; conv weights are
 // repacked to [Cout][tap][Cin] at load time).
 // ---------------------------------------------------------------------------------------
-// AMode (A_PLAIN / A_CONV) and EpiKind (EPI_*): tile_choice.h
-
-enum Act : int32_t { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2 };
-
-struct GemmParams {
-    // problem
-    int32_t M, N, K;
-    // A operand
-    const void* A;     // f16/bf16
-    int64_t lda;       // elements (A_PLAIN)
-    // A_CONV geometry: input map [B][Hp][Wp][Cin] with Hp = Hin + 2, Wp = Win + 2 (zero border)
-    int32_t in_Hp, in_Wp, Cin;
-    int32_t out_H, out_W;     // output pixels per image: M = B * out_H * out_W
-    int32_t KH, KW, stride;   // 1x1 or 3x3 (pad (KH-1)/2); stride 1 or 2
-    // W operand
-    const void* W;     // [N][K]
-    // epilogue
-    const float* bias;     // [N] or [Cout] (EPI_CONVT) or null
-    const float* gamma;    // EPI_RESID_SCALE
-    const float* res32;    // optional f32 residual, same row mapping as out32
-    const float* res32b;   // optional second f32 residual
-    const float* pos;      // EPI_PATCH_EMBED: pos_embed [P+1][N]
-    float* out32;          // optional f32 output
-    void* out16;           // optional f16/bf16 output
-    int64_t ldc;           // row stride (elements) of out32/out16/res32 for row-major outputs
-    int64_t ldc16;         // row / pixel stride of out16 when it differs from ldc (0: same)
-    // Split 16-bit output (pipeline.hip "split operands"): besides hi = T(v) at its place, lo = T(v - hi) is
-    // stored lo_off16 elements further on, so that a consumer whose K axis reads [hi | lo] against
-    // duplicated weights sees v to ~2^-22 instead of 2^-11.  0: plain 16-bit output.
-    int32_t lo_off16;
-    int32_t hi2_off16;     // with lo_off16: a second copy of hi this many elements on ([hi | lo | hi] operands)
-    int32_t act;           // activation applied to the f16 output (and f32 for EPI_STORE)
-    int32_t act16_only;    // 1: activation only on the out16 copy (out32 stays raw)
-    int32_t out16_border;  // EPI_STORE/EPI_CONVT: out16 is zero-bordered [B][out_H+2][out_W+2][C]
-    int32_t tokens_per_window;  // EPI_PATCH_EMBED: P
-    int32_t Cout;          // EPI_CONVT: N = 4*Cout
-    // EPI_HEAD_FINAL
-    // f32 [9][ld]: the share of each 3x3 tap in `bias`, taken out again where the tap falls into the zero padding of a layer that
-    // was composed into this convolution at load time (weights.hip compose_head: EPI_HEAD_COMPOSED, ld = 32; compose_features: the
-    // halo tile's EPI_STORE with a bordered 16-bit output, ld = N)
-    const float* tap_bias;
-    const float* w2;       // [N]
-    const float* b2;       // device scalar
-    const float* f_norm;   // device [B] (one per image) or null (= 1): out32[m] = clamp(v / f_norm[b])
-    float clamp_lo, clamp_hi;  // mod.rs:362 clamp(1e-4, 1e4); +-inf for the canonical head output
-    int32_t pixels_per_image;
-    // diagnostic builds only (tools/gemm_stamps.py): per-workgroup s_memrealtime stamps, or null
-    unsigned long long* stamps;
-    // Row segments with their own weights (the three ViTs of the encoder in one launch, pipeline.hip):
-    // rows [0, seg1) use W / bias / gamma, [seg1, seg2) the *_s1 set, [seg2, M) the *_s2 set.  seg1 == 0:
-    // one segment.  seg2 == 0: two.  Both must be multiples of the tile height (checked at launch).
-    int32_t seg1, seg2;
-    const void *W_s1, *W_s2;
-    const float *bias_s1, *bias_s2, *gamma_s1, *gamma_s2;
-    // MX fp8 operands (gemm_fp8.hip): e8m0 block scales of A and W in the per-wave layouts of mx_fp8.h, a_mt =
-    // 128-row tiles of the A scale array; fp8 output (the next GEMM's A operand) with its scale array
-    const uint8_t *a_scale, *w_scale, *w_scale_s1, *w_scale_s2;
-    int32_t a_mt;
-    uint8_t *out8, *out8_scale;
-    int32_t out8_mt;
-    // Algorithmic work of the launch for the profiler (bench.py's roofline): rows that belong to real tokens /
-    // pixels (0: M; the merged ViT row space pads each segment to 256 rows) and the K of the layer itself (0: K; a
-    // split [hi | lo] operand doubles or triples the K the kernel walks without adding algorithmic FLOPs)
-    int32_t flop_rows, flop_k;
-    // Context status word (me_status_flags): bit 0 is set when an f16 operand store met a magnitude beyond 65504
-    // (gemm_launch fills it in from the calling context)
-    unsigned* status;
-    // tile rows of an XCD's patch in the tile walk (gemm_core.h tile_origin); 0: 8
-    int32_t patch_rows;
-    // EPI_STORE, 16-bit output without activation (the qkv linear, vit.rs:58-62): columns n < qcols leave multiplied
-    // by qscale -- Q of the attention kernel arrives scaled by 1/sqrt(head_dim) * log2(e) with ONE rounding, the
-    // product (acc + bias) * qscale rounded to 16 bits, instead of being scaled and rounded again where it is
-    // consumed (attention.hip attention2_kernel).  qcols == 0: off.  A multiple of 64 (whole heads).
-    int32_t qcols;
-    float qscale;
-    // LayerNorm of the updated token rows inside EPI_RESID_SCALE (gemm_core.h resid_ln_epilogue; the 352-row tile, N in
-    // {256, 512, 1024}): besides x += gamma * (A W^T + b) the launch writes ln_out16[m][:] = LayerNorm(x[m][:]) * w + b
-    // with the weights of the row's segment -- the next linear's operand (vit.rs:165-169: norm1 / norm2 of Block::forward).
-    // The N / 256 column tiles of a row tile exchange their partial (mean, M2) through ln_stats ([row tile][column tile]
-    // [352] 8-byte granules) and count their arrivals in ln_count (one word per row tile, 64 bytes apart; the count only
-    // ever grows by N / 256 per launch, so it needs no reset between launches or graph replays).  ln_out16 == null: off.
-    void* ln_out16;
-    const float *ln_w, *ln_b, *ln_w_s1, *ln_b_s1, *ln_w_s2, *ln_b_s2;
-    float ln_eps;
-    unsigned long long* ln_stats;
-    unsigned* ln_count;
-    // polls a workgroup spends waiting for its row tile's other column tiles before it raises ME_STATUS_SYNC_TIMEOUT
-    // (0: 2^20, about 2 s; gemm_launch fills it in from ME_LN_SPIN_LIMIT, a test knob)
-    int32_t ln_spin_limit;
-    // compute units the launch stream may use when that is fewer than the device has (a stream created with a CU mask;
-    // gemm_launch fills it in, gemm.hip stream_cu_count): persistent grids are sized from it.  0: all of them
-    int32_t cu_granted;
-    // query form (gemm.hip gemm_lnf_resident): the launcher writes the number of workgroups it would keep resident
-    // here and returns without launching.  Host pointer; null for a launch
-    int32_t* resident_out;
-    // development A/B (ME_GELU_BATCH=0): fc1's GELU four values at a time instead of a pass's sixteen at once
-    int32_t gelu_per_granule;
-    // persistent kernels: at most this many workgroups (a multiple of 8), so that a launch on another stream finds
-    // free CUs beside this one; 0: as many as are resident
-    int32_t grid_cap;
-    // Deterministic split-K (gemm_core.h gemm_kernel<..., SPLITK>; the 128x128 tile, EPI_STORE): split_k > 1 work items per tile,
-    // each over a K range; every one writes its f32 partial (accumulator layout) to splitk_ws[(tile * split_k + s)][BM * BN] and
-    // counts its arrival in splitk_cnt[tile] (zero before the launch; the last arriver resets it); the LAST arriver sums the
-    // partials in split order -- its own included, so the result does not depend on who is last -- and runs the epilogue.
-    int32_t split_k;
-    float* splitk_ws;
-    unsigned* splitk_cnt;
-    // Tile queue of the launch stream (gemm_launch fills it in), or null for the static tile order.
-    // Word 32 x: next-tile ticket of XCD x (x < 8), word 256: exited workgroups -- one 128-byte line each
-    // (on one line the 512 prologue draws of a launch serialise in a single L2 channel).
-    unsigned* queue;
-    // (the members below stand behind everything older kernels read: their kernel-argument offsets stay what they were)
-    // A_PLAIN rows whose last part repeats their first ([hi | lo | hi] operands, gemm_params.h set_a_parts): K slabs
-    // kt >= a_wrap are read from slab kt - a_wrap of the row, which is then stored a_wrap * 64 elements wide.  0: no wrap.
-    // EPI_CONVT only (the one consumer of such operands).
-    int32_t a_wrap;
-    // Chained second operand set (gemm_core.h gemm_pp_kernel<..., CHAIN>; the 256x256 two-group tile, EPI_CONVT, gemm_params.h
-    // chain_convt): a tile runs the K loop of (A, W, K), stores the 16-bit output act(acc + bias) from the accumulators, runs
-    // the K loop of (A2, W2, K2) on the SAME accumulators and stores out32 = acc + bias2 -- two ConvTransposes over one input
-    // grid summed in one accumulator.  A2 == null: an ordinary launch.
-    const void *A2, *W2;
-    int64_t lda2;
-    int32_t K2, a_wrap2, flop_k2;
-    const float* bias2;
-};
-constexpr int kGemmQueueWords = 9 * 32;
+// AMode (A_PLAIN / A_CONV) and EpiKind (EPI_*): tile_choice.h.  Act, GemmParams and its builders: gemm_params.h.  What a launcher
+// refuses before it launches: admission.h
 
 // Tile configurations of gemm_launch: the CFG_* ids, what each is and admits, and every rule that picks one live in tile_choice.h.
 // The knobs those rules read, as the environment had them when the process first asked (gemm.hip).
@@ -302,8 +167,7 @@ bool head_final_halo_fits(const GemmParams& p);
 // (gemm_*_conv.hip: the 128-channel halo tile with the EPI_HEAD_COMPOSED epilogue).  p: A = bordered [B][H+2][W+2][Cin] 16-bit,
 // W = composed [128][9][Cin], bias = f32 [32], tap_bias = f32 [9][32], w2 / b2 / f_norm / clamp / pixels_per_image (of the
 // FULL-resolution map) as for EPI_HEAD_FINAL, out32 = depth [B][2H][2W]
-void head_composed_launch(const GemmParams& p, int32_t dtype, hipStream_t stream);
-bool head_composed_fits(const GemmParams& p);
+void head_composed_launch(const GemmParams& p, int32_t dtype, hipStream_t stream);  // (what fits: admission.h head_composed_fits)
 // compute units `stream` may use: the bits of its CU mask (hipExtStreamGetCUMask), the device's count when the stream
 // has no mask or the runtime cannot say
 int stream_cu_count(hipStream_t stream);
@@ -329,14 +193,7 @@ const char* gemm_config_name(int cfg);
 // Attention: qkv [rows][3*C] (q | k | v, each [heads][64]), rows = windows * tokens;
 // out [rows][C].  softmax(q*scale . k^T) v per (window, head); head_dim is 64.
 // ---------------------------------------------------------------------------------------
-// Row segments of the encoder's merged ViT launches (pipeline.hip): segment 0 = rows [0, seg1), 1 =
-// [seg1, seg2), 2 = [seg2, ...).  Windows are contiguous (stride `tokens` rows) inside a segment; win0 /
-// win1 are the numbers of windows of segments 0 and 1.  seg1 == 0: no segmentation.
-struct RowSegs {
-    int64_t seg1 = 0, seg2 = 0;
-    int32_t win0 = 0, win1 = 0;
-    const float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;  // LayerNorm weights of 1 and 2
-};
+// RowSegs (the row segments of the encoder's merged ViT launches) and kAttnQScale: gemm_params.h
 // out8 != nullptr: the output is written as MX fp8 bytes [rows][C] + activation-layout block scales (mx_fp8.h,
 // out8_mt = 128-row tiles of the operand) instead of 16-bit `out`
 void attention_launch(const void* qkv, void* out, int32_t windows, int32_t tokens, int32_t heads,
@@ -346,8 +203,6 @@ void attention_launch(const void* qkv, void* out, int32_t windows, int32_t token
 // pipe) that attention_launch reaches only with ME_ATT_V=3; for a pre-scaled Q it runs attention.hip's attention2_kernel
 void attention3_launch(const void* qkv, void* out, int32_t windows, int32_t tokens, int32_t heads, int32_t dtype, hipStream_t stream,
                        const RowSegs& segs, uint8_t* out8, uint8_t* out8_scale, int64_t out8_mt, float defer_thr);
-// 1/sqrt(head_dim) (vit.rs:47) times log2(e): the factor a pre-scaled Q carries (GemmParams::qscale of the qkv launch)
-constexpr float kAttnQScale = 0.125f * 1.44269504088896340736f;
 
 // ---------------------------------------------------------------------------------------
 // Row-wise and layout kernels (elementwise.hip)

@@ -8,6 +8,8 @@
 
 #include "gemm_core.h"
 
+#include "admission.h"  // (behind the HIP headers: tile_choice.h states its functions for both sides under hipcc)
+
 namespace me {
 
 void fail(int32_t code, const char* fmt, ...) {
@@ -161,18 +163,11 @@ int gemm_ln_spin_limit() { static const int spin = env_int("ME_LN_SPIN_LIMIT", 0
 void head_composed_launch_f16(const GemmParams& p, hipStream_t stream);
 void head_composed_launch_bf16(const GemmParams& p, hipStream_t stream);
 
-bool head_composed_fits(const GemmParams& p) {
-    return p.N == 128 && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.Cin % 64 == 0 && p.K == 9 * p.Cin && p.out_H % 16 == 0 &&
-           p.out_W % 16 == 0 && p.M % 256 == 0 && p.M == (p.M / (p.out_H * p.out_W)) * p.out_H * p.out_W;
-}
-
 void head_composed_launch(const GemmParams& p_in, int32_t dtype, hipStream_t stream) {
     GemmParams p = p_in;
     p.resident_out = nullptr, p.queue = nullptr, p.status = current_status_word();
     p.cu_granted = stream_cu_count(stream);
-    ME_CHECK(head_composed_fits(p), ME_ERR_BAD_SHAPE, "composed head: %dx%d map, Cin %d, N %d", p.out_H, p.out_W, p.Cin, p.N);
-    ME_CHECK(p.A && p.W && p.bias && p.tap_bias && p.w2 && p.b2 && p.out32 && p.pixels_per_image == 4 * p.out_H * p.out_W,
-             ME_ERR_BAD_ARG, "composed head: missing operand");
+    admit_head_composed(p);
     if (log_launches()) fprintf(stderr, "gemm_launch conv head_composed M=%d N=%d K=%d\n", p.M, p.N, p.K);
     // algorithmic FLOPs: every output phase reads a 2 x 2 window of the 3 x 3 one (4 of 9 taps carry weights): the dense launch
     // executes 9 / 4 of them; counted here are the FLOPs of the two layers it replaces at their own shapes (SURVEY App. B:
@@ -216,64 +211,8 @@ void gemm_launch(const GemmParams& p_in, AMode amode, EpiKind epi, int32_t dtype
     p.gelu_per_granule = !env_on("ME_GELU_BATCH");  // (read per launch: the tests flip it inside one process)
     static const int patch_rows = env_int("ME_GEMM_PATCH_ROWS", 0);  // A/B knob
     p.patch_rows = patch_rows;
-    ME_CHECK(p.M > 0 && p.N > 0 && p.K > 0, ME_ERR_BAD_SHAPE, "gemm: empty problem %dx%dx%d", p.M,
-             p.N, p.K);
-    ME_CHECK(p.K % 64 == 0, ME_ERR_BAD_SHAPE, "gemm: K=%d is not a multiple of 64", p.K);
-    ME_CHECK(p.M < (1 << 30) && p.N < (1 << 30), ME_ERR_BAD_SHAPE, "gemm: %dx%d too large", p.M, p.N);
-    ME_CHECK(p.N % 4 == 0, ME_ERR_BAD_SHAPE, "gemm: N=%d is not a multiple of 4", p.N);
-    ME_CHECK(p.A && p.W, ME_ERR_BAD_ARG, "gemm: null operand");
-    if (amode == A_CONV) {
-        ME_CHECK(p.Cin % 64 == 0 && p.K == p.KH * p.KW * p.Cin, ME_ERR_BAD_SHAPE,
-                 "conv: Cin=%d K=%d KHxKW=%dx%d", p.Cin, p.K, p.KH, p.KW);
-        ME_CHECK(p.out_H > 0 && p.out_W > 0 && p.M % (p.out_H * p.out_W) == 0, ME_ERR_BAD_SHAPE,
-                 "conv: M=%d is not a multiple of %dx%d", p.M, p.out_H, p.out_W);
-    } else {
-        // (a_wrap: the row ends where the wrapped slabs start over)
-        ME_CHECK(p.a_wrap >= 0 && p.a_wrap < p.K / 64 && (p.a_wrap == 0 || (epi == EPI_CONVT && p.K - p.a_wrap * 64 <= p.a_wrap * 64)),
-                 ME_ERR_BAD_ARG, "gemm: a_wrap=%d of %d slabs", p.a_wrap, p.K / 64);
-        ME_CHECK(p.lda % 8 == 0 && p.lda >= (p.a_wrap ? p.a_wrap * 64 : p.K), ME_ERR_BAD_SHAPE, "gemm: lda=%lld K=%d",
-                 (long long)p.lda, p.K);
-    }
-    if (p.A2) {
-        // a chained operand set: what the kernel's two passes assume (which tile: tile_choice.h config_refusal, below)
-        ME_CHECK(p.W2 && p.out16 && p.out32 && !p.bias && !p.lo_off16 && p.seg1 == 0 && p.act != ACT_GELU, ME_ERR_BAD_ARG,
-                 "gemm: a chained operand set takes an unbiased first set with a plain 16-bit output, and an f32 output");
-        ME_CHECK(p.K2 > 0 && p.K2 % 64 == 0 && p.a_wrap2 >= 0 && p.a_wrap2 < p.K2 / 64 &&
-                     (p.a_wrap2 == 0 || p.K2 - p.a_wrap2 * 64 <= p.a_wrap2 * 64) && p.lda2 % 8 == 0 &&
-                     p.lda2 >= (p.a_wrap2 ? p.a_wrap2 * 64 : p.K2),
-                 ME_ERR_BAD_SHAPE, "gemm: chained operand set K=%d lda=%lld a_wrap=%d", p.K2, (long long)p.lda2, p.a_wrap2);
-        p.queue = nullptr;  // (static tile order: a pass is not a tile the queue could hand out)
-    }
-    // The ConvTranspose epilogue places an 8-column granule by the sub-pixel and channel of its first column (gemm_core.h EpiLane
-    // q / co).  With Cout = 8 k + 4 every other sub-pixel boundary falls inside a granule: the run-time epilogue mode places such a
-    // granule's halves separately (tests/test_gpu_redzone.py found the unsplit granule: bias read from behind the vector, four
-    // channels in the neighbouring pixel, the sub-pixel's first four never written).  The chained launch has compiled-in modes
-    // only and keeps whole granules; a half-granule (four columns, the unit of every store here) may not straddle anything.
-    if (epi == EPI_CONVT) {
-        ME_CHECK(p.Cout > 0 && p.Cout % 4 == 0, ME_ERR_BAD_SHAPE, "convt: Cout=%d is not a multiple of 4", p.Cout);
-        ME_CHECK(!p.A2 || p.Cout % 8 == 0, ME_ERR_BAD_SHAPE, "convt: a chained launch takes Cout in multiples of 8, not %d", p.Cout);
-    }
-    if (epi == EPI_HEAD_FINAL) ME_CHECK(p.N <= 32, ME_ERR_BAD_SHAPE, "head: N=%d > 32", p.N);
-    if (p.tap_bias)  // the epilogue needs the output pixel's coordinates: the bordered 16-bit output has them
-        ME_CHECK(amode == A_CONV && epi == EPI_STORE && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.out16 && p.out16_border && p.bias &&
-                     p.N % 8 == 0 && !p.out32 && !p.res32 && !p.res32b && !p.lo_off16 && !p.hi2_off16 && p.act != ACT_GELU,
-                 ME_ERR_BAD_ARG, "conv: per-tap bias shares take a 3x3 stride-1 convolution with a bordered 16-bit output and nothing else");
-    if (p.ln_out16) {
-        // (that it runs on the 352-row tile's residual epilogue: tile_choice.h config_refusal, below)
-        ME_CHECK((p.N == 256 || p.N == 512 || p.N == 1024) && p.ldc == p.N && p.ln_w && p.ln_b && p.ln_stats && p.ln_count && p.bias &&
-                     p.gamma && p.res32 && p.out32,
-                 ME_ERR_BAD_ARG, "gemm: the fused LayerNorm takes N in {256, 512, 1024} with its weights, statistics and counters");
-        ME_CHECK(p.seg1 == 0 || (p.ln_w_s1 && p.ln_b_s1 && (p.seg2 == 0 || (p.ln_w_s2 && p.ln_b_s2))), ME_ERR_BAD_ARG,
-                 "gemm: a row segment without LayerNorm weights");
-        // out8 beside ln_out16: the normalised rows leave as MX fp8 + activation-layout scales instead of 16-bit
-        if (p.out8)
-            ME_CHECK(p.out8_scale && (int64_t)p.out8_mt * 128 >= p.M, ME_ERR_BAD_ARG,
-                     "gemm: the fused LayerNorm's fp8 output needs its block scales (%d tiles of 128 rows for %d rows)", p.out8_mt, p.M);
-    }
-    if (p.qcols)
-        ME_CHECK(epi == EPI_STORE && p.qcols % 64 == 0 && p.qcols <= p.N && p.out16 && !p.out32 && p.act == ACT_NONE &&
-                     !p.lo_off16 && !p.hi2_off16,
-                 ME_ERR_BAD_ARG, "gemm: scaled leading columns (qcols = %d) take a plain 16-bit output", p.qcols);
+    admit_gemm(p, amode, epi);  // (admission.h)
+    if (p.A2) p.queue = nullptr;  // (a chained operand set runs the static tile order: a pass is not a tile the queue could hand out)
     // which tile, and whether it takes this problem (tile_choice.h): nothing is launched on a refusal
     const TileProblem problem = tile_problem(p, amode, epi);
     const int cfg = resolve_config(problem, force_cfg, tile_knobs());

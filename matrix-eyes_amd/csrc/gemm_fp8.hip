@@ -23,6 +23,8 @@
 
 #include "gemm_core.h"
 
+#include "admission.h"
+
 namespace me {
 
 typedef int v8i __attribute__((ext_vector_type(8)));
@@ -558,34 +560,9 @@ void gemm_fp8_launch(const GemmParams& p_in, EpiKind epi, hipStream_t stream) {
     // the 256-row tile takes whole tiles only (M and the row segments multiples of 256); the 352-row tile clamps its rows, its
     // row segments start on a 16-row MFMA tile
     const bool whole256 = p.M % 256 == 0 && p.seg1 % 256 == 0 && p.seg2 % 256 == 0;
-    ME_CHECK(p.M > 0 && p.N > 0 && p.N % 256 == 0 && p.K % 128 == 0 && p.K >= 256, ME_ERR_BAD_SHAPE,
-             "fp8 gemm: M=%d N=%d K=%d (N a multiple of 256; K a multiple of 128 and >= 256)", p.M, p.N, p.K);
-    ME_CHECK(p.A && p.W && p.a_scale && p.w_scale && p.a_mt * 128 >= p.M, ME_ERR_BAD_ARG, "fp8 gemm: operands");
-    ME_CHECK(p.lda % 16 == 0 && p.lda >= p.K, ME_ERR_BAD_SHAPE, "fp8 gemm: lda=%lld", (long long)p.lda);
-    ME_CHECK(p.seg1 % 16 == 0 && p.seg2 % 16 == 0 && p.seg1 >= 0 && p.seg2 >= 0 && p.seg1 <= p.M && p.seg2 <= p.M, ME_ERR_BAD_ARG,
-             "fp8 gemm: row segments %d / %d of %d rows", p.seg1, p.seg2, p.M);
-    // a caller mistake here would be a device fault, not a status code
-    ME_CHECK(p.seg1 == 0 || (p.W_s1 && p.w_scale_s1), ME_ERR_BAD_ARG, "fp8 gemm: row segment 1 without weights / scales");
-    ME_CHECK(p.seg2 == 0 || (p.seg1 != 0 && p.seg2 > p.seg1 && p.W_s2 && p.w_scale_s2), ME_ERR_BAD_ARG,
-             "fp8 gemm: row segment 2 without weights / scales");
-    if (epi == EPI_RESID_SCALE) {
-        ME_CHECK(p.gamma && p.res32 && p.out32 && p.bias, ME_ERR_BAD_ARG, "fp8 gemm: the residual form takes bias, gamma, res32 and out32");
-        ME_CHECK((p.seg1 == 0 || (p.gamma_s1 && p.bias_s1)) && (p.seg2 == 0 || (p.gamma_s2 && p.bias_s2)), ME_ERR_BAD_ARG,
-                 "fp8 gemm: a row segment without bias / gamma");
-    } else {
-        ME_CHECK((p.seg1 == 0 || p.bias_s1) && (p.seg2 == 0 || p.bias_s2), ME_ERR_BAD_ARG, "fp8 gemm: a row segment without bias");
-    }
+    admit_gemm_fp8(p, epi);  // (admission.h; the output forms of the store epilogue included)
     // the residual form with the LayerNorm of the updated rows (GemmParams::ln_out16 / out8 as in gemm_launch): the tall tile only
     const bool lnf = epi == EPI_RESID_SCALE && (p.ln_out16 || p.out8);
-    if (lnf) {
-        ME_CHECK((p.N == 256 || p.N == 512 || p.N == 1024) && p.ldc == p.N && p.ln_w && p.ln_b && p.ln_stats && p.ln_count, ME_ERR_BAD_ARG,
-                 "fp8 gemm: the fused LayerNorm takes N in {256, 512, 1024} with its weights, statistics and counters");
-        ME_CHECK(p.seg1 == 0 || (p.ln_w_s1 && p.ln_b_s1 && (p.seg2 == 0 || (p.ln_w_s2 && p.ln_b_s2))), ME_ERR_BAD_ARG,
-                 "fp8 gemm: a row segment without LayerNorm weights");
-        if (p.out8)
-            ME_CHECK(p.out8_scale && (int64_t)p.out8_mt * 128 >= p.M, ME_ERR_BAD_ARG,
-                     "fp8 gemm: the fused LayerNorm's fp8 output needs its block scales (%d tiles of 128 rows for %d rows)", p.out8_mt, p.M);
-    }
     // the 352-row tile where the 256-row one cannot run, or where tile_choice.h rates it cheaper (ME_FP8_TALL read per launch: the tests flip it
     // inside one process)
     const bool tall = lnf || !whole256 || fp8_tall_wins(p.M, p.N, p.seg1, p.seg2, env_int("ME_FP8_TALL", -1));
@@ -606,12 +583,9 @@ void gemm_fp8_launch(const GemmParams& p_in, EpiKind epi, hipStream_t stream) {
         else launch_pp8<EPI_RESID_SCALE, 0>(p, stream);
     } else if (epi == EPI_STORE) {
         if (p.out8) {
-            ME_CHECK(p.out8_scale && p.out8_mt * 128 >= p.M && p.bias, ME_ERR_BAD_ARG, "fp8 gemm: fp8 output");
             if (tall) launch_pp8t<EPI_STORE, 1, false>(p, stream);
             else launch_pp8<EPI_STORE, 1>(p, stream);
         } else {
-            ME_CHECK(p.out16 && !p.out32 && !p.res32 && p.bias && !p.out16_border, ME_ERR_BAD_ARG,
-                     "fp8 gemm: the 16-bit output form takes bias and out16 only");
             if (tall) launch_pp8t<EPI_STORE, 0, false>(p, stream);
             else launch_pp8<EPI_STORE, 0>(p, stream);
         }
@@ -663,8 +637,7 @@ __global__ void quantize_f16_kernel(const f16* __restrict__ src, uint8_t* __rest
 
 void quantize_f16_to_fp8_launch(const void* src16, uint8_t* dst8, uint8_t* scales, int64_t rows, int32_t K,
                                 int32_t weight_layout, hipStream_t stream) {
-    ME_CHECK(K % 128 == 0 && rows > 0, ME_ERR_BAD_SHAPE, "fp8 quantise: rows=%lld K=%d", (long long)rows, K);
-    if (weight_layout) ME_CHECK(rows % 64 == 0, ME_ERR_BAD_SHAPE, "fp8 quantise: %lld weight rows", (long long)rows);
+    admit_quantize_fp8(rows, K, weight_layout);
     const int64_t tiles = weight_layout ? rows / 64 : cdiv(rows, 128);
     const int64_t total = rows * (K / 32);
     ProfScope prof(stream, "quantize_f16_kernel", 0.0, (double)rows * K * 3.03);

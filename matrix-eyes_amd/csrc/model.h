@@ -447,6 +447,14 @@ void free_weight_pack(me_ctx* ctx);
 struct CaptureAbort {};
 // persistent device buffer for a pipeline site; zero-filled when (re)allocated
 void* site_buf(me_ctx* ctx, const std::string& name, size_t bytes);
+// gemm_params.h set_fused_layernorm with the two scratch buffers taken from the context (count_site: one per N, the counter's stride)
+inline void set_fused_layernorm(me_ctx* ctx, GemmParams& p, const std::string& stats_site, const std::string& count_site,
+                                const LnSet& ln, float eps, void* xn16, uint8_t* xn8, uint8_t* xn_scale) {
+    const LnScratchBytes bytes = ln_scratch_bytes(p);
+    void* stats = site_buf(ctx, stats_site, (size_t)bytes.stats);
+    void* count = site_buf(ctx, count_site, (size_t)bytes.count);
+    set_fused_layernorm(p, ln, eps, xn16, xn8, xn_scale, (unsigned long long*)stats, (unsigned*)count);
+}
 
 // host-or-device pointer helpers
 bool is_device_ptr(const void* p);

@@ -8,7 +8,7 @@
 #include <algorithm>
 #include <memory>
 
-#include "gemm_params.h"
+#include "model.h"
 
 namespace me {
 
