@@ -555,8 +555,9 @@ int32_t me_mesh_vertices(me_ctx* ctx, const float* depth, int32_t width, int32_t
                          uint32_t original_height, float* uv, float* xyz);
 
 /* output.rs:100-112 + 195-261 output_mesh with ObjWriter (:484-630) / PlyWriter (:385-482):
-   indexes the mesh on the GPU and writes `destination_path` (".obj" or ".ply", case-insensitive,
+   indexes the mesh on the GPU and writes `destination_path` (".obj", ".ply" or ".glb", case-insensitive,
    anything else is ME_ERR_BAD_ARG; for ".obj" in texture mode also "<stem>.mtl" next to it).
+   ".glb" is not a format of the reference's: a glTF 2.0 binary mesh, described at me_mesh_glb_bytes.
    depth [height,width] is DepthMap.data (already clamped).  vertex_colors: NULL, or u8
    [height*width,3] = the source image resized to the depth map (only read in ME_VERTEX_COLOR
    mode; me_resize_lanczos3_rgb8 makes it, output.rs:206-218). Text output is byte-identical to
@@ -567,8 +568,8 @@ int32_t me_output_mesh(me_ctx* ctx, const float* depth, int32_t width, int32_t h
                        const char* destination_path, const char* source_path, int32_t vertex_mode,
                        const uint8_t* vertex_colors);
 
-/* Write-behind for me_output_mesh(".obj" and ".ply") (BASELINE configs[4]: a batch of images, each ending in a file of
-   70 - 450 MB).  files_in_flight >= 2: the call returns once the file's bytes sit in pinned host memory; a host thread
+/* Write-behind for me_output_mesh(".obj", ".ply" and ".glb") (BASELINE configs[4]: a batch of images, each ending in a
+   file of 70 - 450 MB; a .glb of up to 94 MB).  files_in_flight >= 2: the call returns once the file's bytes sit in pinned host memory; a host thread
    writes the file (and an OBJ's .mtl) while the caller goes on to the next image.  That many pinned buffers are used in turn, so that many files
    can be in flight; the next call waits for the oldest (1 is taken as 2) -- and for any pending write to its own
    destination path -- before it starts any work of its own.  A failed write is reported (ME_ERR_IO, me_last_error) by
@@ -612,11 +613,30 @@ int32_t me_mesh_ply_bytes(me_ctx* ctx, const float* depth, int32_t width, int32_
                           uint32_t original_width, uint32_t original_height, int32_t vertex_mode,
                           const uint8_t* vertex_colors, const uint8_t** bytes_dev, int64_t* nbytes);
 
-/* Where the last me_output_mesh(".obj" or ".ply") call on this context spent its time, host wall clock in milliseconds:
+/* The glTF 2.0 binary file of me_output_mesh(".glb") without the file.  A 12-byte header, one JSON chunk padded with
+   spaces to a length that is 4 mod 16, and one BIN chunk, whose payload therefore starts at a multiple of 16 in the
+   file.  BIN holds, each at a multiple of 16 with zeros between: the positions, nvertices x 3 little-endian f32
+   (x, -y, -z: the sign flips of the reference's writers, output.rs:450, and glTF's camera convention); in
+   ME_VERTEX_COLOR mode with vertex_colors, nvertices x (r, g, b, 255) u8 (without them no colour section and no COLOR_0,
+   as the PLY records fall back to 24 bytes); in ME_VERTEX_TEXTURE mode nvertices x 2 f32, the uv of me_mesh_vertices
+   unchanged (glTF's v runs downwards), and a material whose texture is the image {"uri": source_path}, JSON-escaped
+   but otherwise as given (the string the .mtl has behind map_Kd: relative to the caller's directory, not embedded);
+   then the faces as 3 x nfaces little-endian u32 in the reference's emission order.  The position accessor's min / max
+   are the exact f32 bounds of the written values, reduced on the GPU and printed as the OBJ writer prints a number.
+   An empty mesh is a valid asset with no geometry and no BIN chunk.  ME_ERR_BAD_ARG, nothing written: a bound that is
+   not finite (JSON cannot hold it), a file of 2^32 bytes or more.  *bytes_dev: DEVICE address, owned by the context,
+   valid until its next mesh call; *nbytes: the size of the file.  me_output_mesh(".glb") is these bytes copied to the
+   host once and written to the file. */
+int32_t me_mesh_glb_bytes(me_ctx* ctx, const float* depth, int32_t width, int32_t height,
+                          uint32_t original_width, uint32_t original_height, const char* source_path,
+                          int32_t vertex_mode, const uint8_t* vertex_colors, const uint8_t** bytes_dev,
+                          int64_t* nbytes);
+
+/* Where the last me_output_mesh(".obj", ".ply" or ".glb") call on this context spent its time, host wall clock in milliseconds:
    ms_out[0] mesh indexing + vertex kernels (incl. their read-back of the counts), [1] the kernels that format the OBJ
-   text or pack the PLY records, [2] the D2H copy of the file's bytes into pinned memory, [3] the file write (the host
+   text, pack the PLY records or pack the GLB sections (the read-back of the GLB's position bounds included), [2] the D2H copy of the file's bytes into pinned memory, [3] the file write (the host
    kernel's page-cache copy; with write-behind, the hand-over to the writing thread); *text_bytes (optional): the size
-   of the file.  (A call served by a host serialiser -- ME_OBJ_HOST_FORMAT, ME_PLY_HOST_FORMAT -- is not reported.) */
+   of the file.  (A call served by a host serialiser -- ME_OBJ_HOST_FORMAT, ME_PLY_HOST_FORMAT, ME_GLB_HOST_FORMAT -- is not reported.) */
 int32_t me_last_mesh_timing(const me_ctx* ctx, double ms_out[4], int64_t* text_bytes);
 
 #ifdef __cplusplus

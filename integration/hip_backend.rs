@@ -253,7 +253,8 @@ impl<'d> DepthMap<'d> {
         })
     }
 
-    /// output.rs:195-261 output_mesh with ObjWriter / PlyWriter (:385-630); vertex_mode = ME_VERTEX_*
+    /// output.rs:195-261 output_mesh with ObjWriter / PlyWriter (:385-630); vertex_mode = ME_VERTEX_*.  A ".glb"
+    /// destination_path (any letter case) is written as a glTF 2.0 binary mesh; ".obj" and ".ply" as the reference does.
     pub fn output_mesh(&self, destination_path: &str, source_path: &str, vertex_mode: i32, vertex_colors: Option<&[u8]>) -> Result<(), HipError> {
         let dst = CString::new(destination_path).unwrap();
         let src = CString::new(source_path).unwrap();

@@ -304,5 +304,12 @@ void obj_vertex_colors_launch(const int32_t* vindex, const uint8_t* pixel_rgb, i
 int64_t ply_pack_bytes(int64_t nverts, bool with_rgb, int64_t nfaces, int64_t header_bytes);
 void ply_pack_launch(const float* xyz, const uint8_t* vertex_rgb, int64_t nverts, const int32_t* faces, int64_t nfaces,
                      int64_t header_bytes, uint8_t* out, hipStream_t stream);
+// glTF binary meshes on the device (glb_format.hip, layout in glb_format.h).  glb_bounds_run: the exact bounds of the
+// written positions (x, -y, -z) of nverts > 0 vertices as sign keys (glb_format.h sign_key: three minima, three maxima),
+// reduced in bounds_dev (24 bytes of device memory) and read back: it synchronises.  glb_pack_launch: every section of
+// BIN (`second`: me_glb::Second, what stands between positions and indices), its gaps zeroed, from `bin` on, 16-byte aligned.
+void glb_bounds_run(const float* xyz, int64_t nverts, int32_t* bounds_dev, int32_t keys[6], hipStream_t stream);
+void glb_pack_launch(const float* xyz, const float* uv, const uint8_t* vertex_rgb, const int32_t* faces, int64_t nverts,
+                     int64_t nfaces, int second, uint8_t* bin, hipStream_t stream);
 
 }  // namespace me

@@ -1,8 +1,9 @@
 // The mesh files serialised on the host (reference src/output.rs:385-630 PlyWriter, ObjWriter): the A/B of the device
-// formatters (ME_OBJ_HOST_FORMAT, ME_PLY_HOST_FORMAT; mesh_writer.hip write_host_mesh).  Every line and record is the
-// text the kernels run -- obj_format.h format_line, ply_format.h vertex_record / face_record -- so only the headers,
-// the .mtl and the path rules are spelled out here.  Plain C++17: tests/mesh_format_host.cpp includes it with
-// ME_OBJ_HOST and ME_PLY_HOST defined and needs no HIP.
+// formatters (ME_OBJ_HOST_FORMAT, ME_PLY_HOST_FORMAT, ME_GLB_HOST_FORMAT; mesh_writer.hip write_host_mesh).  Every line,
+// record and unit is the text the kernels run -- obj_format.h format_line, ply_format.h vertex_record / face_record,
+// glb_format.h pack_unit -- so only the headers, the .mtl and the path rules are spelled out here.  Plain C++17:
+// tests/mesh_format_host.cpp includes it with ME_OBJ_HOST and ME_PLY_HOST defined, tests/glb_format_host.cpp with
+// ME_GLB_HOST too (glb_format.h is in host mode under any compiler but hipcc), and neither needs HIP.
 #pragma once
 #include <ctype.h>
 #include <stdint.h>
@@ -10,6 +11,7 @@
 
 #include <string>
 
+#include "glb_format.h"
 #include "obj_format.h"
 #include "ply_format.h"
 
@@ -100,6 +102,47 @@ template <typename Visit>
 void each_ply_section(const me_ply::PackArgs& a, Visit&& visit) {
     visit(a.nverts, &append_ply_vertex, (const void*)&a);
     visit(a.nfaces, &append_ply_face, (const void*)&a);
+}
+
+// A .glb mesh (glb_format.h), one thread.  The formats a mesh destination's suffix selects:
+enum MeshFormat { kFormatObj = 0, kFormatPly = 1, kFormatGlb = 2 };
+
+// what stands between positions and indices: colours follow the colour array, as the PLY records do; UVs the mode
+inline int glb_second(bool texture_mode, bool with_color) {
+    return texture_mode ? me_glb::kUvs : with_color ? me_glb::kColors : me_glb::kNone;
+}
+
+// The file's size checked against the u32 of its header: "" when it fits.
+inline std::string glb_size_error(const me_glb::Layout& l, int64_t json_bytes) {
+    const int64_t bytes = me_glb::file_bytes(l, json_bytes);
+    return bytes < me_glb::kMaxFileBytes ? std::string() : "a .glb file of " + std::to_string(bytes) + " bytes cannot state its length";
+}
+inline const char* glb_bounds_error() { return "a .glb file cannot hold a position bound that is not finite"; }
+
+// The whole file on the host: the bounds, the JSON and BIN unit by unit, by the routines the kernels run.  Returns ""
+// and fills `file`, or the reason the mesh is refused (nothing written).  The arrays may be null where their count is 0.
+inline std::string glb_file_on_host(const float* xyz, const float* uv, const uint8_t* rgb, const int32_t* faces, int64_t nverts,
+                                    int64_t nfaces, bool texture_mode, const char* source_path, std::string& file) {
+    const me_glb::Layout l = me_glb::layout_of(nverts, nverts ? nfaces : 0, glb_second(texture_mode, rgb != nullptr));
+    int32_t bounds[6];
+    me_glb::bounds_identity(bounds);
+    for (int64_t i = 0; i < nverts; ++i) me_glb::bounds_add_vertex(xyz, i, bounds);
+    if (nverts && !me_glb::bounds_finite(bounds)) return glb_bounds_error();
+    const std::string json = me_glb::json_text(l, texture_mode, source_path, bounds);
+    const std::string size_error = glb_size_error(l, (int64_t)json.size());
+    if (!size_error.empty()) return size_error;
+    file = me_glb::front_text(l, json);
+    if (nverts == 0) return "";
+    const size_t front = file.size();
+    file.resize(front + (size_t)l.bin_bytes + 16);   // 16 bytes of slack so that BIN can be moved to an aligned address
+    // the units are aligned 16-byte stores: pack at the first 16-byte aligned address at or behind BIN's place, move down
+    uint8_t* const at = (uint8_t*)&file[front];
+    uint8_t* const bin = at + ((16 - ((uintptr_t)at & 15)) & 15);
+    const me_glb::PackArgs a = {xyz, uv, rgb, faces, l, bin};
+    for (int64_t u = 0; u < me_glb::total_units(l); ++u) me_glb::pack_unit(a, u);
+    memmove(at, bin, (size_t)l.bin_bytes);
+    file.resize(front + (size_t)l.bin_bytes);
+    return "";
 }
 
 }  // namespace me_mesh_host

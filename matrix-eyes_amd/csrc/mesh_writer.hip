@@ -1,8 +1,9 @@
 // output.rs:195-261 output_mesh and its two writers (ObjWriter :484-630, PlyWriter :385-482).
-// Vertex ids, faces and coordinates come from the GPU kernels in output.hip, the OBJ text from obj_format.hip and the
-// PLY records from ply_format.hip; this file drives them and hands the finished bytes, copied to the host once, to the
-// file writer (file_write.hip, write-behind included).  The host-side serialisers (mesh_host_format.h: the same line
-// and record text, run on the host) stay as the A/B of both (ME_OBJ_HOST_FORMAT, ME_PLY_HOST_FORMAT).
+// Vertex ids, faces and coordinates come from the GPU kernels in output.hip, the OBJ text from obj_format.hip, the
+// PLY records from ply_format.hip and a glTF binary's sections (".glb": not a format of the reference's) from
+// glb_format.hip; this file drives them and hands the finished bytes, copied to the host once, to the
+// file writer (file_write.hip, write-behind included).  The host-side serialisers (mesh_host_format.h: the same line,
+// record and unit text, run on the host) stay as the A/B of each (ME_OBJ_HOST_FORMAT, ME_PLY_HOST_FORMAT, ME_GLB_HOST_FORMAT).
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -108,18 +109,48 @@ DeviceFile ply_bytes_on_device(me_ctx* ctx, const DeviceMesh& m, const MeshReque
     return {(const uint8_t*)file, bytes};
 }
 
+// The .glb file in device memory (site buffer "out.glbbytes"): the bounds of the written positions come back to the host
+// (24 bytes, right behind the counts build_mesh read back), the host builds the JSON around them and copies it in with
+// the chunk headers, and one launch packs every section of BIN behind it.  An empty mesh is the JSON chunk alone.
+DeviceFile glb_bytes_on_device(me_ctx* ctx, const DeviceMesh& m, const MeshRequest& r, const char* source_path) {
+    const bool tex = r.vertex_mode == ME_VERTEX_TEXTURE;
+    const me_glb::Layout l = me_glb::layout_of(m.nverts, m.nverts ? m.nfaces : 0, glb_second(tex, r.with_color()));
+    int32_t bounds[6];
+    me_glb::bounds_identity(bounds);
+    if (m.nverts) {
+        glb_bounds_run(m.xyz, m.nverts, (int32_t*)site_buf(ctx, "out.glb.bounds", 32), bounds, ctx->stream);
+        ME_CHECK(me_glb::bounds_finite(bounds), ME_ERR_BAD_ARG, "%s", glb_bounds_error());
+    }
+    const std::string json = me_glb::json_text(l, tex, source_path, bounds);
+    const std::string size_error = glb_size_error(l, (int64_t)json.size());
+    ME_CHECK(size_error.empty(), ME_ERR_BAD_ARG, "%s", size_error.c_str());
+    const std::string front = me_glb::front_text(l, json);
+    const int64_t bytes = me_glb::file_bytes(l, (int64_t)json.size());
+    char* file = file_site_buf(ctx, "out.glbbytes", bytes);
+    ME_HIP(hipMemcpyAsync(file, front.data(), front.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (m.nverts) {
+        const uint8_t* vrgb = vertex_colors_on_device(ctx, m, r);
+        glb_pack_launch(m.xyz, m.uv, vrgb, m.faces, m.nverts, m.nfaces, l.second, (uint8_t*)file + front.size(), ctx->stream);
+    }
+    return {(const uint8_t*)file, bytes};
+}
+
 using Clock = std::chrono::steady_clock;
 double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
 
-// The file's bytes are produced on the GPU too (OBJ: the text, obj_format.hip; PLY: the binary records, ply_format.hip);
+// The file's bytes are produced on the GPU too (OBJ: the text, obj_format.hip; PLY: the binary records, ply_format.hip;
+// GLB: the BIN sections, glb_format.hip, behind the JSON the host builds from the bounds the GPU reduced);
 // one D2H copy into pinned memory, one file write.  With write-behind this call's bytes go into the pinned buffer whose
 // earlier write has finished (waited for here, a failure of it reported here), and a host thread writes the file while
 // the caller moves on.
-void write_device_mesh(me_ctx* ctx, const DeviceMesh& mesh, const MeshRequest& r, const std::string& dest, bool obj,
+void write_device_mesh(me_ctx* ctx, const DeviceMesh& mesh, const MeshRequest& r, const std::string& dest, MeshFormat format,
                        const char* source_path, Clock::time_point t_entry) {
+    const bool obj = format == kFormatObj;
     static const bool timing = getenv("ME_OBJ_TIMING") != nullptr;  // diagnostic: the legs on stderr
     const auto t0 = Clock::now();
-    const DeviceFile t = obj ? obj_text_on_device(ctx, mesh, r, file_stem(dest)) : ply_bytes_on_device(ctx, mesh, r);
+    const DeviceFile t = obj                    ? obj_text_on_device(ctx, mesh, r, file_stem(dest))
+                         : format == kFormatPly ? ply_bytes_on_device(ctx, mesh, r)
+                                                : glb_bytes_on_device(ctx, mesh, r, source_path);
     PinnedFile file;
     file.dest = dest, file.bytes = (size_t)t.bytes, file.slot = ctx->write_behind ? ctx->write_next : 0;
     if (obj && r.vertex_mode == ME_VERTEX_TEXTURE) file.side_path = mtl_path(dest), file.side_text = mtl_text(source_path);
@@ -161,11 +192,12 @@ std::vector<uint8_t> host_vertex_colors(me_ctx* ctx, const DeviceMesh& mesh, con
     return colors;
 }
 
-// ME_OBJ_HOST_FORMAT=1 / ME_PLY_HOST_FORMAT=1: the mesh comes back to the host and mesh_host_format.h serialises it (the
-// same bytes; the A/B of each device formatter).  OBJ sections are formatted by up to 12 threads; a PLY record is a byte
-// shuffle per item, not worth the second copy.
-void write_host_mesh(me_ctx* ctx, const DeviceMesh& mesh, const MeshRequest& r, const std::string& dest, bool obj,
+// ME_OBJ_HOST_FORMAT=1 / ME_PLY_HOST_FORMAT=1 / ME_GLB_HOST_FORMAT=1: the mesh comes back to the host and
+// mesh_host_format.h serialises it (the same bytes; the A/B of each device formatter).  OBJ sections are formatted by up
+// to 12 threads; a PLY record is a byte shuffle per item, not worth the second copy; a GLB is made whole by one thread.
+void write_host_mesh(me_ctx* ctx, const DeviceMesh& mesh, const MeshRequest& r, const std::string& dest, MeshFormat format,
                      const char* source_path) {
+    const bool obj = format == kFormatObj;
     const int64_t nverts = mesh.nverts, nfaces = mesh.nfaces;
     std::vector<float> uv((size_t)nverts * 2), xyz((size_t)nverts * 3);
     std::vector<int32_t> faces((size_t)nfaces * 3);
@@ -183,7 +215,13 @@ void write_host_mesh(me_ctx* ctx, const DeviceMesh& mesh, const MeshRequest& r, 
     const auto add = [&](bool threads) {
         return [&sections, threads](int64_t count, AppendItem item, const void* args) { sections.push_back({count, item, args, threads}); };
     };
-    if (obj) {
+    if (format == kFormatGlb) {
+        std::string file;
+        const std::string refused = glb_file_on_host(xyz.data(), uv.data(), rgb, faces.data(), nverts, nfaces,
+                                                     r.vertex_mode == ME_VERTEX_TEXTURE, source_path, file);
+        ME_CHECK(refused.empty(), ME_ERR_BAD_ARG, "%s", refused.c_str());
+        write_sections(dest, file, nullptr, 0);
+    } else if (obj) {
         const bool tex = r.vertex_mode == ME_VERTEX_TEXTURE;
         const ObjSections text(uv.data(), xyz.data(), rgb, faces.data(), nverts, nfaces, tex);
         text.each(add(true));
@@ -277,6 +315,20 @@ extern "C" int32_t me_mesh_ply_bytes(me_ctx* ctx, const float* depth, int32_t wi
     ME_API_END(ctx)
 }
 
+extern "C" int32_t me_mesh_glb_bytes(me_ctx* ctx, const float* depth, int32_t width, int32_t height,
+                                     uint32_t original_width, uint32_t original_height, const char* source_path,
+                                     int32_t vertex_mode, const uint8_t* vertex_colors, const uint8_t** bytes_dev,
+                                     int64_t* nbytes) {
+    ME_API_BEGIN(ctx)
+    const MeshRequest r = {depth, width, height, original_width, original_height, vertex_mode, vertex_colors};
+    check_mesh_args("me_mesh_glb_bytes", depth && source_path && bytes_dev && nbytes, r);
+    OutputScope out_scope(ctx, depth);
+    const DeviceFile t = glb_bytes_on_device(ctx, build_mesh(ctx, r), r, source_path);
+    ME_HIP(hipStreamSynchronize(ctx->stream));
+    *bytes_dev = t.dev, *nbytes = t.bytes;
+    ME_API_END(ctx)
+}
+
 // Its own catch block: an exception that is not an me::Error is an I/O failure here (ME_ERR_IO, not ME_API_END's ME_ERR_BAD_ARG)
 extern "C" int32_t me_output_mesh(me_ctx* ctx, const float* depth, int32_t width, int32_t height,
                                   uint32_t original_width, uint32_t original_height,
@@ -288,8 +340,9 @@ extern "C" int32_t me_output_mesh(me_ctx* ctx, const float* depth, int32_t width
         const MeshRequest r = {depth, width, height, original_width, original_height, vertex_mode, vertex_colors};
         check_mesh_args("me_output_mesh", depth && destination_path && source_path, r);
         const std::string dest(destination_path);
-        const bool ply = ends_with_ci(dest, ".ply"), obj = ends_with_ci(dest, ".obj");
-        ME_CHECK(ply || obj, ME_ERR_BAD_ARG, "mesh destination must end in .obj or .ply: %s", destination_path);
+        const bool ply = ends_with_ci(dest, ".ply"), obj = ends_with_ci(dest, ".obj"), glb = ends_with_ci(dest, ".glb");
+        ME_CHECK(ply || obj || glb, ME_ERR_BAD_ARG, "mesh destination must end in .obj, .ply or .glb: %s", destination_path);
+        const MeshFormat format = obj ? kFormatObj : ply ? kFormatPly : kFormatGlb;
         OutputScope out_scope(ctx, depth);
         const auto t_entry = Clock::now();
         if (ctx->write_behind) {
@@ -303,8 +356,9 @@ extern "C" int32_t me_output_mesh(me_ctx* ctx, const float* depth, int32_t width
         const DeviceMesh mesh = build_mesh(ctx, r);
         static const bool obj_host_format = getenv("ME_OBJ_HOST_FORMAT") != nullptr;
         static const bool ply_host_format = getenv("ME_PLY_HOST_FORMAT") != nullptr;
-        if (obj ? obj_host_format : ply_host_format) write_host_mesh(ctx, mesh, r, dest, obj, source_path);
-        else write_device_mesh(ctx, mesh, r, dest, obj, source_path, t_entry);
+        static const bool glb_host_format = getenv("ME_GLB_HOST_FORMAT") != nullptr;
+        if (obj ? obj_host_format : ply ? ply_host_format : glb_host_format) write_host_mesh(ctx, mesh, r, dest, format, source_path);
+        else write_device_mesh(ctx, mesh, r, dest, format, source_path, t_entry);
     } catch (const me::Error& e) {
         ctx->last_error = e.msg;
         return e.code;

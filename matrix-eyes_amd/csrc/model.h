@@ -296,7 +296,7 @@ struct me_ctx {
     };
     std::vector<WriteSlot> write_slots = std::vector<WriteSlot>(1);
     int write_next = 0;
-    // legs of the last me_output_mesh call that made its file on the device (.obj or .ply), host wall clock: [0] mesh
+    // legs of the last me_output_mesh call that made its file on the device (.obj, .ply or .glb), host wall clock: [0] mesh
     // indexing + vertex kernels, [1] the kernels that format the text or pack the records, [2] D2H copy of the file,
     // [3] file write, or handing it to the write-behind thread (me_last_mesh_timing)
     double mesh_ms[4] = {0, 0, 0, 0};

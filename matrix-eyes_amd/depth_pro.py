@@ -273,7 +273,7 @@ class Context:
         return bool(fused.value), int(fallbacks.value)
 
     def last_mesh_timing(self):
-        """legs of the last output_mesh(".obj" or ".ply") call in ms: {mesh, format, d2h, file} and the file's size"""
+        """legs of the last output_mesh(".obj", ".ply" or ".glb") call in ms: {mesh, format, d2h, file} and the file's size"""
         ms = (C.c_double * 4)()
         n = C.c_int64()
         self._check(self.lib.me_last_mesh_timing(self._h, ms, C.byref(n)))
@@ -286,7 +286,7 @@ class Context:
         self._check(self.lib.me_ctx_set_output_overlap(self._h, 1 if on else 0))
 
     def set_write_behind(self, files_in_flight=2):
-        """OBJ and PLY files written by host threads behind the caller, up to `files_in_flight` at a time; 0 / False: the
+        """OBJ, PLY and GLB files written by host threads behind the caller, up to `files_in_flight` at a time; 0 / False: the
         synchronous form (matrix_eyes_hip.h me_ctx_set_write_behind)."""
         self._check(self.lib.me_ctx_set_write_behind(self._h, int(files_in_flight)))
 

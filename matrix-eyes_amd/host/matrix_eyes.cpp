@@ -243,7 +243,7 @@ DepthMap::DepthMap(const Device& device, std::vector<float> inverse_depth, size_
 
 void DepthMap::output_image(const std::string& destination_path, const std::string& source_path,
                             ImageOutputFormat image_format, VertexMode vertex_mode) const {
-    if (ends_with_ci(destination_path, ".ply") || ends_with_ci(destination_path, ".obj"))
+    if (ends_with_ci(destination_path, ".ply") || ends_with_ci(destination_path, ".obj") || ends_with_ci(destination_path, ".glb"))
         return output_mesh(destination_path, source_path, vertex_mode);
     if (image_format.kind == ImageOutputFormat::DepthMap) return output_depth_map(destination_path);
     return output_stereogram(destination_path, image_format.resize_scale, image_format.amplitude);

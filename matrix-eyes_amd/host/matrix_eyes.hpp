@@ -158,7 +158,7 @@ public:
     DepthMap(const Device& device, std::vector<float> inverse_depth, size_t rows, size_t cols,
              uint32_t original_width, uint32_t original_height);
     std::pair<float, float> inverse_depth_range() const { return {min_, max_}; }  // :69-75
-    // output.rs:100-121: .ply / .obj by suffix, else the image format
+    // output.rs:100-121: .ply / .obj (and .glb, a glTF 2.0 binary mesh) by suffix, else the image format
     void output_image(const std::string& destination_path, const std::string& source_path,
                       ImageOutputFormat image_format, VertexMode vertex_mode) const;
 

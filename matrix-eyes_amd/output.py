@@ -206,7 +206,7 @@ class DepthMap:
         jpeg_encoder = resolve_jpeg_encoder(jpeg_encoder)
         noise_source = resolve_noise_source(noise_source)
         low = destination_path.lower()
-        if low.endswith(".ply") or low.endswith(".obj"):
+        if low.endswith((".ply", ".obj", ".glb")):   # (.glb: glTF 2.0 binary, beyond the reference's two)
             return self.output_mesh(destination_path, source_path, vertex_mode, resampler=resampler)
         from PIL import Image
         jpeg = low.endswith(".jpg") or low.endswith(".jpeg")
@@ -239,7 +239,7 @@ class DepthMap:
                                             noise_source=noise_source)).save(destination_path, **save_args)
 
     def output_mesh(self, destination_path: str, source_path: str, vertex_mode: VertexMode, resampler=None):
-        """output.rs:195-261 with ObjWriter / PlyWriter."""
+        """output.rs:195-261 with ObjWriter / PlyWriter; a ".glb" destination is a glTF 2.0 binary mesh (mesh_glb_bytes)."""
         resampler = resolve_resampler(resampler)
         colors = None
         if vertex_mode == VertexMode.Color:   # output.rs:206-218
@@ -265,6 +265,18 @@ class DepthMap:
             self.ctx.handle, C.c_void_p(self.data.ctypes.data), self.data_width, self.data_height, self.original_width,
             self.original_height, int(vertex_mode), C.c_void_p(colors.ctypes.data) if colors is not None else None,
             C.byref(ptr), C.byref(n)))
+        return _device_file(ptr, n, self.data)
+
+    def mesh_glb_bytes(self, source_path: str = "", vertex_mode: VertexMode = VertexMode.Plain, colors=None) -> bytes:
+        """The glTF 2.0 binary file output_mesh(".glb") writes, as `bytes` (me_mesh_glb_bytes: the sections packed on the
+        GPU).  source_path: the picture a VertexMode.Texture material names; colors: as for mesh_ply_bytes."""
+        if colors is not None:
+            colors = np.ascontiguousarray(colors, dtype=np.uint8)
+        ptr, n = C.c_void_p(), C.c_int64()
+        self.ctx._check(self.ctx.lib.me_mesh_glb_bytes(
+            self.ctx.handle, C.c_void_p(self.data.ctypes.data), self.data_width, self.data_height, self.original_width,
+            self.original_height, str(source_path).encode(), int(vertex_mode),
+            C.c_void_p(colors.ctypes.data) if colors is not None else None, C.byref(ptr), C.byref(n)))
         return _device_file(ptr, n, self.data)
 
 
@@ -339,6 +351,16 @@ class DeviceDepthMap:
             self.ctx.handle, C.c_void_p(self.data.data_ptr()), self.data_width, self.data_height, self.original_width,
             self.original_height, int(vertex_mode), C.c_void_p(colors.data_ptr()) if colors is not None else None,
             C.byref(ptr), C.byref(n)))
+        return _device_file(ptr, n, self.data)
+
+    def mesh_glb_bytes(self, source_path: str = "", vertex_mode: VertexMode = VertexMode.Plain, colors=None):
+        """The glTF 2.0 binary file's bytes as a CUDA uint8 tensor (me_mesh_glb_bytes; a copy of the context-owned
+        buffer).  colors: CUDA u8 [rows, cols, 3] or None, read in VertexMode.Color only."""
+        ptr, n = C.c_void_p(), C.c_int64()
+        self.ctx._check(self.ctx.lib.me_mesh_glb_bytes(
+            self.ctx.handle, C.c_void_p(self.data.data_ptr()), self.data_width, self.data_height, self.original_width,
+            self.original_height, str(source_path).encode(), int(vertex_mode),
+            C.c_void_p(colors.data_ptr()) if colors is not None else None, C.byref(ptr), C.byref(n)))
         return _device_file(ptr, n, self.data)
 
     def stereogram(self, amplitude: float, noise=None, out=None, key=None, size=None):
